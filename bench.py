@@ -2,7 +2,7 @@
 
 Workloads (BASELINE.json configs):
   --mode fwd     (default) C2: mha_fwd B=4 H=32 S=4096 D=128 bf16 causal; one step = one
-                 forward over the batch.  The default line also carries driver-timed
+                 forward over the batch.  With --full the line also carries driver-timed
                  sub-results for C3 ("fwd_bwd"), C4 ("varlen"), C5 ("decode", full caches, and
                  "decode_ragged", cache lengths U[1, 32768]) and the fp8 forward, each with its
                  own roofline and CPU baseline (median of 3 runs), because the metric names fwd
@@ -15,6 +15,21 @@ Workloads (BASELINE.json configs):
                  (north_star's fp8 GEMMs; an extension, priced against the 5 PF fp8 peak).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--mode ...] [--scaling weak|strong]
+                  [--full] [--dump-outputs DIR]
+
+A plain run does what the headline figure needs and no more: set up, clock-ramp prewarm, W warmup
+steps, K timed steps, one JSON line (metric, value, unit, ms_per_step, config, kernel, device).
+  --full         everything else, each a run of its own after the timed steps: the HIP-event
+                 pass behind "roofline", the GPU clock / power monitor ("gpu_clock"), the CPU
+                 baseline, the sub-results of the default mode and, at --gpus N > 1, the timed
+                 all-gather.  --no-extras / --no-cpu-baseline / --no-monitor take single parts
+                 out again.
+  --dump-outputs DIR   after the timed steps, what the last timed step returned to its caller
+                 (out, softmax_lse; dq, dk, dv, softmax_d for fwdbwd) as DIR/<name>.npy in
+                 float32: whole arrays while they fit 48 MiB together, else a fixed sample of
+                 each (one element per equal stride of the flattened array, offsets from a CPU
+                 generator seeded with 0, the same in every run).  The inputs are seeded, so
+                 equal arguments give equal inputs run to run.
 
 Multi-GPU (one process per GPU, RCCL = torch.distributed "nccl" over xGMI).  With --gpus N > 1
 and no WORLD_SIZE in the environment this process is only a launcher: before touching the GPU
@@ -70,6 +85,13 @@ def parse(argv=None):
     ap.add_argument("--mode", choices=["fwd", "fwdbwd", "varlen", "decode", "fwd_fp8"],
                     default="fwd")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: roofline (HIP-event "
+                         "pass), GPU clock monitor, CPU baseline, the default mode's sub-results, "
+                         "the timed all-gather at --gpus N > 1")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32; a "
+                         "fixed seeded sample of arrays that do not fit 48 MiB together)")
     ap.add_argument("--batch", type=int, default=0, help="default: 4 (fwd), 8 (decode)")
     ap.add_argument("--heads", type=int, default=32)
     ap.add_argument("--seqlen", type=int, default=0, help="default: 4096 (fwd), 32768 (decode)")
@@ -89,9 +111,9 @@ def parse(argv=None):
                          "256 MiB Infinity Cache on their own)")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=6.0,
                     help="CPU budget per baseline (split over 3 runs; the median is reported)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without CPU baselines")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the C3/C4/C5 sub-results of the default (fwd) line")
+                    help="--full without the C3/C4/C5 sub-results of the default (fwd) line")
     ap.add_argument("--graph", choices=["on", "off"], default="off",
                     help="replay one step as a captured hipGraph")
     ap.add_argument("--opt", action="append", default=[],
@@ -104,7 +126,10 @@ def parse(argv=None):
     ap.add_argument("--selftest-cpu", action="store_true",
                     help="launcher/aggregation self-test on CPU (gloo, a tiny matmul step): "
                          "NOT a benchmark; used by tests/test_bench_launcher.py")
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return a
 
 
 # ----------------------------------------------------------------------------- host info
@@ -251,16 +276,18 @@ def workload_dense(a, mode, dev, rank, world):
         qs, _ = sharding.head_shards(H, H, world)[rank]
         Hr, shard = qs.size, f"heads [{qs.start}, {qs.stop}) of {H}"
     g = torch.Generator(device=dev).manual_seed(1234 + rank)
+    gd = torch.Generator(device=dev).manual_seed(4321 + rank)    # dout: seeded like q / k / v
     nrot = a.rotate or 2
     sets = []
     for _ in range(nrot):
         q, k, v = (torch.randn(B, S, Hr, D, device=dev, dtype=torch.bfloat16, generator=g)
                    for _ in range(3))
         out = torch.empty_like(q)
-        dout = torch.randn_like(q)
+        dout = torch.randn(B, S, Hr, D, device=dev, dtype=torch.bfloat16, generator=gd)
         sets.append((q, k, v, out, dout))
     nxt = _rotating(sets)
     res = {}
+    keep_grads = bool(getattr(a, "dump_outputs", None))
     wl = a.window_left
     alibi = (torch.tensor([2.0 ** (-8.0 * (i + 1) / H) for i in range(H)], device=dev)[:Hr]
              if a.alibi else None)
@@ -294,9 +321,18 @@ def workload_dense(a, mode, dev, rank, world):
     def fwdbwd():
         q, k, v, out, dout = nxt()
         r = pa.fwd(q, k, v, out, alibi, 0.0, scale, causal, wl, -1, 0.0, False, None)
-        pa.bwd(dout, q, k, v, out, r[5], None, None, None, alibi, 0.0, scale, causal, wl, -1,
-               0.0, False, None, None)
+        g = pa.bwd(dout, q, k, v, out, r[5], None, None, None, alibi, 0.0, scale, causal, wl, -1,
+                   0.0, False, None, None)
         res["r"] = r
+        if keep_grads:      # otherwise freed at once, as a training step would
+            res["g"] = g
+
+    def outputs():      # what the last step returned: fwd_kvcache (out, lse), fwd (out, .., lse, ..)
+        r = res["r"]
+        o = {"out": r[0], "softmax_lse": r[1] if len(r) == 2 else r[5]}
+        if mode == "fwdbwd":
+            o.update(zip(("dq", "dk", "dv", "softmax_d"), res["g"]))
+        return o
 
     ff = fwd_flops(B, Hr, S, S, D, causal)
     if wl >= 0:    # (sq = sk) row pos sees keys max(0, pos - wl) .. pos (causal) or .. pos + wl
@@ -309,6 +345,7 @@ def workload_dense(a, mode, dev, rank, world):
     glob_b = B * world if a.scaling == "weak" else B
     return dict(step=fwd if mode == "fwd" else fwdbwd, units=ff * mult, bound="mfma",
                 out=lambda: sets[0][3], gather_dim=0 if a.scaling == "weak" else 2,
+                outputs=outputs,
                 config={"workload": f"mha_{mode} B={B} H={H} S={S} D={D} bf16 {cs}",
                         "global_batch": glob_b, "seq_len": S, "heads": H, "head_dim": D,
                         "rank_shard": shard, "input_sets": nrot,
@@ -338,14 +375,19 @@ def workload_fp8(a, dev, rank, world):
         out = torch.empty(B, S, H, D, device=dev, dtype=torch.bfloat16)
         sets.append((xs, out))
     nxt = _rotating(sets)
+    res = {}
+    keep = bool(getattr(a, "dump_outputs", None))
 
     def step():
         (q, qs), (k, ks), (v, vs) = (x for x in nxt()[0])
-        pa.fwd_fp8(q, k, v, None, qs, ks, vs, scale, causal, -1, -1, False)
+        r = pa.fwd_fp8(q, k, v, None, qs, ks, vs, scale, causal, -1, -1, False)
+        if keep:            # otherwise freed at once
+            res["r"] = r
 
     cs = "causal" if causal else "non-causal"
     return dict(step=step, units=fwd_flops(B, H, S, S, D, causal), bound="mfma8",
                 out=lambda: sets[0][1], gather_dim=0,
+                outputs=lambda: dict(zip(("out", "softmax_lse"), res["r"])),
                 config={"workload": f"mha_fwd fp8-e4m3 Q/K/V B={B} H={H} S={S} D={D} {cs}, "
                                     f"bf16 out", "global_batch": B * world, "seq_len": S,
                         "heads": H, "head_dim": D, "input_sets": a.rotate or 2,
@@ -375,14 +417,19 @@ def workload_varlen(a, dev, rank, world):
                for _ in range(3))
     out = torch.empty_like(q)
     mx = max(lens)
+    res = {}
+    keep = bool(getattr(a, "dump_outputs", None))
 
     def step():
-        pa.varlen_fwd(q, k, v, out, cu, cu, None, None, None, mx, mx, 0.0, scale, False,
-                      causal, -1, -1, 0.0, False, None)
+        r = pa.varlen_fwd(q, k, v, out, cu, cu, None, None, None, mx, mx, 0.0, scale, False,
+                          causal, -1, -1, 0.0, False, None)
+        if keep:            # otherwise freed at once
+            res["r"] = r
 
     fl = sum(fwd_flops(1, H, s, s, D, causal) for s in lens)
     cs = "causal" if causal else "non-causal"
     return dict(step=step, units=fl, bound="mfma", out=lambda: out, gather_dim=0,
+                outputs=lambda: {"out": res["r"][0], "softmax_lse": res["r"][5]},
                 config={"workload": f"mha_varlen_fwd 32 ragged seqs, lengths {min(lens)}-{max(lens)} "
                                     f"(U[1024,7168] draw, seed {rank}, rescaled to total 131072) "
                                     f"H={H} D={D} bf16 {cs}",
@@ -431,14 +478,18 @@ def workload_decode(a, dev, rank, world):
             c[i:i + t.shape[0]] = (t.float() / sc_).to(torch.float8_e4m3fn).view(torch.uint8)
     q = torch.randn(B, 1, H, D, device=dev, dtype=torch.bfloat16, generator=g)
     res = {}
+    keep = bool(getattr(a, "dump_outputs", None))
 
     def step():
-        res["o"] = pa.fwd_kvcache_fp8(q, kc, vc, seqlens, table, ks, vs, scale, False, -1, -1,
-                                      0)[0]
+        r = pa.fwd_kvcache_fp8(q, kc, vc, seqlens, table, ks, vs, scale, False, -1, -1, 0)
+        res["o"] = r[0]
+        if keep:            # otherwise the lse is freed at once
+            res["lse"] = r[1]
 
     step()
     nbytes = int(lens.sum()) * HK * D * 2 + 2 * B * H * D * 2 + table.numel() * 4 + B * 4
     return dict(step=step, units=nbytes, bound="hbm", out=lambda: res["o"], gather_dim=0,
+                outputs=lambda: {"out": res["o"], "softmax_lse": res["lse"]},
                 config={"workload": f"paged-KV decode B={B}/GPU H={H} Hk={HK} Sq=1 "
                                     f"cache={'U[1,%d]' % S if a.ragged else S} page={page} "
                                     f"D={D} fp8-e4m3fn K/V (scale 1/16), q bf16",
@@ -489,6 +540,38 @@ def event_ms(step, steps, stream):
     torch.cuda.synchronize()
     ts = sorted(s.elapsed_time(e) for s, e in evs)
     return ts[len(ts) // 2], ts[0], ts[-1]
+
+
+DUMP_BYTES = 48 << 20      # float32 bytes of one dump, all arrays together
+
+
+def sample_outputs(outs):
+    """{name: float32 CPU tensor} of a step's outputs for --dump-outputs: every array whole
+    while they fit DUMP_BYTES together; otherwise an array above its equal share is cut to a
+    fixed sample of that many elements (one flat index in each of that many equal strides, the
+    offsets from a CPU generator seeded with 0, so every run of the same arguments picks the
+    same elements), gathered on the device."""
+    share = DUMP_BYTES // 4 // max(1, len(outs))
+    whole = sum(t.numel() for t in outs.values()) * 4 <= DUMP_BYTES
+    g = torch.Generator().manual_seed(0)
+    got = {}
+    for name, t in outs.items():
+        flat = t.detach().reshape(-1)
+        if not whole and flat.numel() > share:
+            stride = flat.numel() // share            # one pick in each of `share` strides
+            idx = torch.arange(share) * stride + torch.randint(stride, (share,), generator=g)
+            got[name] = flat[idx.to(flat.device)].float().cpu()
+        else:
+            got[name] = flat.float().cpu().view(t.shape)
+    return got
+
+
+def write_outputs(got, d, rank, world):
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for name, t in got.items():
+        np.save(os.path.join(d, name + (f".rank{rank}" if world > 1 else "") + ".npy"),
+                t.numpy())
 
 
 class ClockMonitor:
@@ -622,7 +705,7 @@ def roofline(w, ev, mode):
 def sub_result(a, mode, dev, stream, **over):
     """A driver-timed sub-result (same method as the main line, rank-local, 1 GPU), with its
     own CPU baseline; `over` overrides arguments (e.g. ragged=True)."""
-    a = argparse.Namespace(**{**vars(a), **over})
+    a = argparse.Namespace(**{**vars(a), "dump_outputs": None, **over})
     w = build_workload(a, mode, dev, 0, 1)
     step = w["step"]
     t_pw = time.time()
@@ -725,7 +808,7 @@ def main(argv=None):
     # starts) no child process is started at all
     profiled = any(k.startswith("ROCPROF") for k in os.environ) or \
         "rocprof" in os.environ.get("LD_PRELOAD", "")
-    if world == 1 and not a.no_monitor and not profiled:
+    if a.full and world == 1 and not a.no_monitor and not profiled:
         MONITOR = ClockMonitor()         # before this process touches the GPU
     try:
         return run(a, world, rank, local)
@@ -783,7 +866,9 @@ def run(a, world, rank, local):
     if dist:
         dist.barrier()
     elapsed = time.perf_counter() - t0
-    ev_ms = event_ms(step, a.steps, stream)
+    # the last timed step's outputs, sampled before any later pass runs the step again
+    dumped = sample_outputs(w["outputs"]()) if a.dump_outputs else None
+    ev_ms = event_ms(step, a.steps, stream) if a.full else None
     t_end = time.time()
     kern = last_kernel()
 
@@ -799,8 +884,11 @@ def run(a, world, rank, local):
     value = total_units * a.steps / elapsed / scale_u
     ms_per_step = elapsed / a.steps * 1e3
 
+    if dumped is not None:
+        write_outputs(dumped, a.dump_outputs, rank, world)
+
     allgather = None
-    if dist:
+    if dist and a.full:
         out = w["out"]()
         gd = w["gather_dim"]
         # RCCL all-gather of every rank's output shard over xGMI (assembling the full output)
@@ -826,7 +914,7 @@ def run(a, world, rank, local):
                                                 / scale_u, 2)}
 
     extras = {}
-    if rank == 0 and a.mode == "fwd" and world == 1 and not a.no_extras:
+    if a.full and rank == 0 and a.mode == "fwd" and world == 1 and not a.no_extras:
         extras["fwd_bwd"] = sub_result(a, "fwdbwd", dev, stream)
         extras["varlen"] = sub_result(a, "varlen", dev, stream)
         extras["decode"] = sub_result(a, "decode", dev, stream)
@@ -868,17 +956,20 @@ def run(a, world, rank, local):
             "options": dict(o.split("=") for o in a.opt),
             "library": capi.lib().fmha_version().decode(),
             "config": w["config"],
-            "roofline": roofline(w, ev_ms, a.mode + ("_ragged" if a.ragged else "")),
             "kernel": kern,
             "device": device_info(dev),
-            "gpu_clock": clock_stats(t_pw + 0.2, t_end),
         }
+        if a.full:
+            line["roofline"] = roofline(w, ev_ms, a.mode + ("_ragged" if a.ragged else ""))
+            line["gpu_clock"] = clock_stats(t_pw + 0.2, t_end)
+        if a.dump_outputs:
+            line["dumped_outputs"] = {n: list(t.shape) for n, t in dumped.items()}
         if dist:
             line["rccl"] = {"backend": dist.get_backend(), "world_size": dist.get_world_size()}
         line.update(extras)
         if allgather:
             line["allgather"] = allgather
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             line["cpu_baseline"] = w["cpu"]()
         print(json.dumps(line), flush=True)
     if dist:

@@ -1,5 +1,6 @@
-# One lease at HEAD: the GPU parity suite (+ parity report) and smoke, the default bench line
-# (all sub-results), the forward schedule A/B (tools/lease_ab.sh without its bench), and the
+# One lease at HEAD: the GPU parity suite (+ parity report) and smoke, the full bench line
+# (bench.py --full, all sub-results) and the forward schedule A/B (tools/lease_ab.sh, which logs
+# to $XFA_EVIDENCE_DIR, default evidence_out), and the
 # rocprofv3 stats + PMC passes of every mode, for profiles/<tag>_* (summarised on the CPU side by
 # tools/pmc_report.py).   usage: bash tools/gpu_evidence.sh <tag>
 set -o pipefail
