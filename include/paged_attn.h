@@ -143,7 +143,7 @@ const char* fmha_version(void);
  * power of two >= 8: 4 auto, the default = 3 where no row has a right window and the cache is
  * not paged, else 2; 3 the 8-wave ping-pong kernel on the 16x16x32 MFMA (not paged); 2 the
  * 8-wave ping-pong kernel on 32x32x16; 1 the 4-wave kernel (variants build); 0 neither), fp8_w4 (fp8 forward: 1 the 4-wave kernel, the default; 2 the
- * 8-wave ping-pong kernel; 0 the 8-wave compiler-scheduled one), comb_row (0/1), bwd_order (0/1),
+ * 8-wave ping-pong kernel, dense launches only; 0 the 8-wave compiler-scheduled one), comb_row (0/1), bwd_order (0/1),
  * bwd_desc (0/1), dec_fold (0/1: the decode split combine folded into the split launch). */
 int fmha_set_option(const char* name, int value);
 /* Current value of a knob, or -1 (with fmha_last_error set) for an unknown name. */
@@ -174,6 +174,22 @@ void fmha_fwd_fp8(void* q, void* k, void* v, void* o, void* softmax_lse, float q
                   int32_t batch_size, int32_t num_heads, int32_t num_heads_k, int32_t head_size,
                   float softmax_scale, int window_size_left, int window_size_right, bool out_fp16,
                   hipStream_t stream);
+
+/* fmha_fwd_fp8 over packed variable-length sequences (2.5): q [total_q, heads, 128] and k/v
+ * [total_k, heads_k, 128] in OCP fp8 e4m3fn bytes, cu_seqlens_q / cu_seqlens_k int32
+ * [batch + 1] (both required), seqused_k int32 [batch] or NULL (keys [0, seqused_k[b]) of the
+ * slot cu_seqlens_k describes).  o: bf16 or fp16 [total_q, heads, 128]; softmax_lse fp32
+ * [heads, total_q] (unpadded, as fmha_varlen_fwd_ex; total_q addresses it) or NULL.  A sequence
+ * without keys gets O = 0 and LSE = +inf, one without queries writes nothing.  Windows are
+ * normalised against max_seqlen_k.  head_size must be 128; no ALiBi / softcap / dropout / paged
+ * K/V. */
+void fmha_varlen_fwd_fp8(void* q, void* k, void* v, void* o, void* softmax_lse,
+                         void* cu_seqlens_q, void* cu_seqlens_k, void* seqused_k,
+                         float q_scale, float k_scale, float v_scale,
+                         int32_t max_seqlen_q, int32_t max_seqlen_k, int32_t total_q,
+                         int32_t batch_size, int32_t num_heads, int32_t num_heads_k, int32_t head_size,
+                         float softmax_scale, int window_size_left, int window_size_right,
+                         bool out_fp16, hipStream_t stream);
 
 /* Varlen forward with the fields the reference's varlen C entry drops (paged_attn.cpp:423-433):
  * LSE out (fp32 [num_heads, total_q], unpadded as export.cpp:827; total_q = cu_seqlens_q[batch]

@@ -39,6 +39,7 @@ from .interface import (  # noqa: E402
     flash_attn_fp8_func,
     flash_attn_func,
     flash_attn_kvpacked_func,
+    flash_attn_varlen_fp8_func,
     flash_attn_varlen_func,
     flash_attn_varlen_kvpacked_func,
     flash_attn_with_kvcache,
@@ -50,6 +51,7 @@ __all__ = [
     "flash_attn_fp8_func",
     "flash_attn_kvpacked_func",
     "flash_attn_varlen_func",
+    "flash_attn_varlen_fp8_func",
     "flash_attn_varlen_kvpacked_func",
     "flash_attn_with_kvcache",
 ]

@@ -30,6 +30,8 @@ _SIGS = {
                          f32, vp],
     "fmha_fwd_fp8": [vp, vp, vp, vp, vp, f32, f32, f32, i32, i32, i32, i32, i32, i32, f32,
                      C.c_int, C.c_int, b_, vp],
+    "fmha_varlen_fwd_fp8": [vp, vp, vp, vp, vp, vp, vp, vp, f32, f32, f32, i32, i32, i32, i32,
+                            i32, i32, i32, f32, C.c_int, C.c_int, b_, vp],
     "fmha_varlen_fwd_ex_v2": [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, i32, i32, i32, i32,
                            i32, i32, i32, i32, f32, C.c_int, C.c_int, f32, b_, vp, f32, vp],
     "fmha_page_kvcache_fwd_ex_v2": [vp, vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32,

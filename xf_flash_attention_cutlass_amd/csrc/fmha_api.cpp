@@ -391,7 +391,7 @@ const char* fmha_last_error(void) { return g_err.c_str(); }
 int fmha_last_status(void) { return g_status; }
 int fmha_last_num_splits(void) { return g_last_splits; }
 const char* fmha_last_kernel(void) { return g_last_kernel; }
-const char* fmha_version(void) { return XFA_VARIANTS ? "xf-fmha-gfx950 2.4 (variants)" : "xf-fmha-gfx950 2.4"; }
+const char* fmha_version(void) { return XFA_VARIANTS ? "xf-fmha-gfx950 2.5 (variants)" : "xf-fmha-gfx950 2.5"; }
 
 void fmha_set_rng_state(uint64_t seed, uint64_t offset) {
     g_seed = seed;
@@ -594,6 +594,71 @@ void fmha_fwd_fp8(void* q, void* k, void* v, void* o, void* softmax_lse, float q
         hip_ok(launch_fwd_fp8(p, out_fp16, stream), "fp8 forward launch");
     } catch (...) {
         fail(9, "internal error in fmha_fwd_fp8");
+    }
+}
+
+void fmha_varlen_fwd_fp8(void* q, void* k, void* v, void* o, void* softmax_lse,
+                         void* cu_seqlens_q, void* cu_seqlens_k, void* seqused_k,
+                         float q_scale, float k_scale, float v_scale,
+                         int32_t max_seqlen_q, int32_t max_seqlen_k, int32_t total_q,
+                         int32_t batch_size, int32_t num_heads, int32_t num_heads_k, int32_t head_size,
+                         float softmax_scale, int window_size_left, int window_size_right,
+                         bool out_fp16, hipStream_t stream) {
+    try {
+        begin_fwd();
+        if (!check_common(q, k, v, o, batch_size, num_heads, num_heads_k, head_size)) return;
+        REQUIRE(cu_seqlens_q && cu_seqlens_k, "cu_seqlens_q and cu_seqlens_k must be given");
+        REQUIRE(head_size == 128, "the fp8 forward supports head_size 128 (got %d)", head_size);
+        REQUIRE(q_scale > 0.f && k_scale > 0.f && v_scale > 0.f, "fp8 descales must be positive");
+        REQUIRE(max_seqlen_q > 0, "max_seqlen_q must be positive (got %d)", max_seqlen_q);
+        REQUIRE(max_seqlen_k > 0, "max_seqlen_k must be positive (got %d): nothing to attend to", max_seqlen_k);
+        REQUIRE(!softmax_lse || total_q > 0, "total_q must be given to address the LSE");
+        if (!slab_ok("q", max_seqlen_q, (int64_t)num_heads * head_size, 1) ||
+            !slab_ok("k/v", max_seqlen_k, (int64_t)num_heads_k * head_size, 1) ||
+            !slab_ok("o", max_seqlen_q, (int64_t)num_heads * head_size, 2) ||
+            (softmax_lse && !slab_ok("softmax_lse", total_q, num_heads, 4))) return;
+        FwdParams p{};
+        p.q = q; p.k = k; p.v = v; p.o = o;
+        p.lse = (float*)softmax_lse;
+        const int h = num_heads, hk = num_heads_k, d = head_size;
+        // packed rows: element (= byte, for q/k/v) strides, no batch stride
+        p.q_row = (int64_t)h * d; p.q_head = d; p.q_batch = 0;
+        p.o_row = (int64_t)h * d; p.o_head = d; p.o_batch = 0;
+        p.k_row = (int64_t)hk * d; p.k_head = d; p.k_batch = 0;
+        p.v_row = (int64_t)hk * d; p.v_head = d; p.v_batch = 0;
+        // unpadded LSE [num_heads, total_q], as fmha_varlen_fwd_ex
+        p.lse_batch = 0;
+        p.lse_head = total_q;
+        p.cu_seqlens_q = (const int*)cu_seqlens_q;
+        p.cu_seqlens_k = (const int*)cu_seqlens_k;
+        p.seqused_k = (const int*)seqused_k;
+        p.b = batch_size; p.h = h; p.hk = hk; p.group = h / hk; p.d = d;
+        p.seqlen_q = max_seqlen_q; p.seqlen_k = max_seqlen_k;
+        p.alibi_causal = set_windows(window_size_left, window_size_right, max_seqlen_k);
+        p.wl = window_size_left; p.wr = window_size_right;
+        set_scales(p, softmax_scale, 0.f);
+        p.q_scale = q_scale; p.k_scale = k_scale; p.v_scale = v_scale;
+        Options& op = options();
+        p.device = current_device();
+        p.num_cus = num_cus(p.device);
+        p.persist_per_cu = op.fwd_persistent.load();
+        p.order = op.fwd_order.load();
+        p.max_slack = (float)op.fwd_slack.load();
+        p.num_splits = 1;
+        p.fwd4 = op.fp8_w4.load();
+        p.xcdq = op.fwd_xcdq.load();
+        // ragged items balance from the dynamic item queue (fwd_dyn >= 1, as the bf16 varlen
+        // launches); fwd_dyn = 0 keeps the static persistent schedules
+        p.work_ctr = nullptr;
+        if (op.fwd_dyn.load() >= 1) {
+            p.work_ctr = counter_get(stream);
+            REQUIRE(p.work_ctr, "could not allocate the item-queue counters");
+        }
+        g_last_splits = 1;
+        g_last_kernel[0] = 0;
+        hip_ok(launch_fwd_fp8(p, out_fp16, stream), "fp8 varlen forward launch");
+    } catch (...) {
+        fail(9, "internal error in fmha_varlen_fwd_fp8");
     }
 }
 

@@ -162,6 +162,26 @@ struct FwdParams {
     int64_t* rng_out;
 };
 
+// Sequence `bidx` of a packed (varlen / seqused_k) launch: first row and length on the q and the
+// k side, as workgroup-uniform scalars (the fp8 kernels build buffer descriptors from them).
+// VARLEN = false (a dense launch's instantiation): offsets 0 and the launch's lengths, folded
+// at compile time, so the dense kernels carry none of this.
+struct SeqRange { int q_off, sq, k_off, sk; };
+template <bool VARLEN>
+__device__ __forceinline__ SeqRange seq_range(const FwdParams& p, const int bidx) {
+    SeqRange r{0, p.seqlen_q, 0, p.seqlen_k};
+    if constexpr (VARLEN) {
+        if (p.cu_seqlens_q) { r.q_off = p.cu_seqlens_q[bidx]; r.sq = p.cu_seqlens_q[bidx + 1] - r.q_off; }
+        if (p.cu_seqlens_k) { r.k_off = p.cu_seqlens_k[bidx]; r.sk = p.cu_seqlens_k[bidx + 1] - r.k_off; }
+        if (p.seqused_k) r.sk = p.seqused_k[bidx];
+        r.q_off = __builtin_amdgcn_readfirstlane(r.q_off);
+        r.sq = __builtin_amdgcn_readfirstlane(r.sq);
+        r.k_off = __builtin_amdgcn_readfirstlane(r.k_off);
+        r.sk = __builtin_amdgcn_readfirstlane(max(r.sk, 0));
+    }
+    return r;
+}
+
 struct CombineParams {
     const float* oaccum;
     const float* lseaccum;

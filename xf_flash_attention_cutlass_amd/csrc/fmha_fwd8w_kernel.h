@@ -53,7 +53,7 @@ __device__ __forceinline__ int v8w_swz(int row) { return (((row >> 1) & 1) | (((
 __device__ __forceinline__ int v8w_off(int row, int chunk) { return row * 128 + 16 * (chunk ^ v8w_swz(row)); }
 
 // One (batch x kv head, 256-row query block) item.
-template <bool F16>
+template <bool F16, bool VARLEN>
 __device__ __forceinline__ void fwd8w_item(const FwdParams& p, char* smem, const int bh, const int m_block XFA_F8_ACC_PARAM) {
     constexpr int HD = 128;
     int tid = threadIdx.x;
@@ -65,11 +65,13 @@ __device__ __forceinline__ void fwd8w_item(const FwdParams& p, char* smem, const
 
     const int bidx = bh / p.hk;
     const int hk_i = bh - bidx * p.hk;
-    const int sq = p.seqlen_q, sk = p.seqlen_k;
+    // varlen / seqused_k: this sequence's rows of the packed tensors (dense: q_off = k_off = 0)
+    const SeqRange sr = seq_range<VARLEN>(p, bidx);
+    const int q_off = sr.q_off, sq = sr.sq, k_off = sr.k_off, sk = sr.sk;
     const int G = p.group;
     const int rows_total = sq * G;
     const int row0 = m_block * kFwd8wRows;
-    if (row0 >= rows_total) return;          // workgroup-uniform
+    if (row0 >= rows_total) return;          // workgroup-uniform (also sq <= 0)
     const int diag = sk - sq;
     auto lim_r = [&](int pos) { return p.wr >= 0 ? min(sk, pos + diag + p.wr + 1) : sk; };
 
@@ -104,30 +106,33 @@ __device__ __forceinline__ void fwd8w_item(const FwdParams& p, char* smem, const
     }
 
     if (ntl <= 0) {
-        // no visible key for any row: O = 0, LSE = +inf (the reference's empty-row output)
+        // no visible key for any row (or a sequence without keys): O = 0, LSE = +inf (the
+        // reference's empty-row output)
         typedef __attribute__((ext_vector_type(4))) unsigned u4;
-        char* oseq = reinterpret_cast<char*>(p.o) + (int64_t)bidx * p.o_batch * 2;
+        char* oseq = reinterpret_cast<char*>(p.o) + ((int64_t)bidx * p.o_batch + (int64_t)q_off * p.o_row) * 2;
 #pragma unroll
         for (int rb = 0; rb < 2; ++rb) {
             if (ooff[rb] == kOOB) continue;
 #pragma unroll
             for (int c = 0; c < 8; ++c) *reinterpret_cast<u4*>(oseq + ooff[rb] + 32 * c) = u4{0, 0, 0, 0};
-            if (p.lse && hh == 0) p.lse[(int64_t)bidx * p.lse_batch + loff[rb] / 4] = INFINITY;
+            if (p.lse && hh == 0) p.lse[(int64_t)bidx * p.lse_batch + q_off + loff[rb] / 4] = INFINITY;
         }
         return;
     }
 
-    const char* qseq = reinterpret_cast<const char*>(p.q) + (int64_t)bidx * p.q_batch;
-    char* oseq = reinterpret_cast<char*>(p.o) + (int64_t)bidx * p.o_batch * 2;
+    // bases and extents of this sequence's own rows: a lane past them reads zeros and stores
+    // nothing (never the next sequence's rows)
+    const char* qseq = reinterpret_cast<const char*>(p.q) + (int64_t)bidx * p.q_batch + (int64_t)q_off * p.q_row;
+    char* oseq = reinterpret_cast<char*>(p.o) + ((int64_t)bidx * p.o_batch + (int64_t)q_off * p.o_row) * 2;
     const uint32_t qbytes = (uint32_t)((int64_t)(sq - 1) * p.q_row + (int64_t)(p.h - 1) * p.q_head + HD);
     const uint32_t obytes = (uint32_t)(((int64_t)(sq - 1) * p.o_row + (int64_t)(p.h - 1) * p.o_head + HD) * 2);
     const i32x4 qsrd = fwd8w_srd(qseq, qbytes), osrd = fwd8w_srd(oseq, obytes);
-    const float* lseq = p.lse ? p.lse + (int64_t)bidx * p.lse_batch : p.lse;
+    const float* lseq = p.lse ? p.lse + (int64_t)bidx * p.lse_batch + q_off : p.lse;
     const int64_t lbytes = p.lse ? ((int64_t)(p.h - 1) * p.lse_head + sq) * 4 : 0;
     const i32x4 lsrd = fwd8w_srd(lseq, (uint32_t)min(lbytes, (int64_t)kOOB - 1));
     const int k_row = (int)p.k_row, v_row = (int)p.v_row;
-    const char* kseq = reinterpret_cast<const char*>(p.k) + (int64_t)bidx * p.k_batch + (int64_t)hk_i * p.k_head;
-    const char* vseq = reinterpret_cast<const char*>(p.v) + (int64_t)bidx * p.v_batch + (int64_t)hk_i * p.v_head;
+    const char* kseq = reinterpret_cast<const char*>(p.k) + (int64_t)bidx * p.k_batch + (int64_t)k_off * p.k_row + (int64_t)hk_i * p.k_head;
+    const char* vseq = reinterpret_cast<const char*>(p.v) + (int64_t)bidx * p.v_batch + (int64_t)k_off * p.v_row + (int64_t)hk_i * p.v_head;
     const int nk = min(sk, ntl * kBlockN);
     const uint32_t kvbytes = (uint32_t)((nk - 1) * k_row + HD);
     const int kblo = __builtin_amdgcn_readfirstlane((int)(uint32_t)(uint64_t)kseq);
@@ -173,7 +178,7 @@ __device__ __forceinline__ void fwd8w_item(const FwdParams& p, char* smem, const
 
 // Persistent grid (one workgroup per CU): XCD-grouped (n-1-i, i) row-block pairs, or (fwd_dyn
 // = 2) the per-XCD dynamic item queues, as the bf16 kernels.
-template <bool F16>
+template <bool F16, bool VARLEN>
 __global__ void __launch_bounds__(256, 1) fmha_fwd8w_kernel(const FwdParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __shared__ int s_claim[2];
@@ -218,7 +223,7 @@ __global__ void __launch_bounds__(256, 1) fmha_fwd8w_kernel(const FwdParams p) {
             bh = blockIdx.x;
             m_block = gridDim.y - 1 - blockIdx.y;
         }
-        fwd8w_item<F16>(p, smem, bh, m_block XFA_F8_ACC_ARG);
+        fwd8w_item<F16, VARLEN>(p, smem, bh, m_block XFA_F8_ACC_ARG);
     }
 #ifdef XFA_FWD8_STAMPS
     if ((threadIdx.x & 63) < 8) atomicAdd(&g_fwd8_stamps[(threadIdx.x >> 6) * 8 + (threadIdx.x & 63)], (unsigned long long)acc);

@@ -1,5 +1,7 @@
 // fmha_fwd_fp8.hip — launches of the fp8 (e4m3fn) Q/K/V forward (fmha_fwd_fp8_kernel.h), D = 128,
 // bf16 or fp16 output; persistent XCD-paired grid as the bf16 forward.
+#include <algorithm>
+
 #include "fmha_fwd_fp8_kernel.h"
 #include "fmha_fwd8w_kernel.h"
 #if XFA_VARIANTS
@@ -10,8 +12,9 @@
 namespace xfa {
 
 // 4-wave fp8 forward (fmha_fwd8w_kernel.h): no left window (the 8-wave kernel's masked loop
-// handles those)
-template <bool F16>
+// handles those).  VARLEN: the instantiation that reads cu_seqlens / seqused_k (a dense launch
+// runs the one without, whose code the packed path does not touch)
+template <bool F16, bool VARLEN>
 static hipError_t launch_fp8_w4(const FwdParams& p, hipStream_t st) {
     const int n_mb = (p.seqlen_q * p.group + kFwd8wRows - 1) / kFwd8wRows;
     FwdParams pp = p;
@@ -25,9 +28,9 @@ static hipError_t launch_fp8_w4(const FwdParams& p, hipStream_t st) {
         grid = dim3(p.num_cus, 1, 1);
     }
     static std::atomic<unsigned long long> attr_done{0};
-    once_per_device(attr_done, p.device, [&] { (void)hipFuncSetAttribute((const void*)fmha_fwd8w_kernel<F16>, hipFuncAttributeMaxDynamicSharedMemorySize, kFwd8wSmem); });
+    once_per_device(attr_done, p.device, [&] { (void)hipFuncSetAttribute((const void*)fmha_fwd8w_kernel<F16, VARLEN>, hipFuncAttributeMaxDynamicSharedMemorySize, kFwd8wSmem); });
     note_launch("fmha_fwd8w_kernel", pp.persistent, pp.xcd_queues, grid.x, grid.y, grid.z, 256);
-    hipLaunchKernelGGL((fmha_fwd8w_kernel<F16>), grid, dim3(256), kFwd8wSmem, st, pp);
+    hipLaunchKernelGGL((fmha_fwd8w_kernel<F16, VARLEN>), grid, dim3(256), kFwd8wSmem, st, pp);
     return hipGetLastError();
 }
 
@@ -54,7 +57,7 @@ static hipError_t launch_fp8_pp(const FwdParams& p, hipStream_t st) {
 }
 #endif
 
-template <typename T>
+template <typename T, bool VARLEN>
 static hipError_t launch_fp8_t(const FwdParams& p, hipStream_t st) {
     constexpr int NW = 8;
     const bool mask = p.wl >= 0 || p.wr >= 0;
@@ -67,17 +70,24 @@ static hipError_t launch_fp8_t(const FwdParams& p, hipStream_t st) {
     if (p.persist_per_cu > 0) {
         const int items = p.b * p.hk * n_mb;
         const int slots = p.num_cus * p.persist_per_cu;
-        if (items > slots) {
+        if (VARLEN && p.work_ctr) {
+            // varlen: ragged items from one dynamic queue (as the bf16 varlen launches), once
+            // there are more items than CUs
+            if (items > p.num_cus) {
+                pp.persistent = 3;
+                grid = dim3(std::min(items, slots), 1, 1);
+            }
+        } else if (items > slots) {
             pp.persistent = (p.order == 1 && slots % 8 == 0) ? 2 : 1;
             grid = dim3(slots, 1, 1);
         }
     }
     const size_t smem = 8 * (size_t)kFp8Tile;     // K and V, four buffers each
-    void (*kern)(const FwdParams) = mask ? fmha_fwd_fp8_kernel<T, NW, true> : fmha_fwd_fp8_kernel<T, NW, false>;
+    void (*kern)(const FwdParams) = mask ? fmha_fwd_fp8_kernel<T, NW, true, VARLEN> : fmha_fwd_fp8_kernel<T, NW, false, VARLEN>;
     static std::atomic<unsigned long long> attr_done{0};
     once_per_device(attr_done, p.device, [&] {
-        (void)hipFuncSetAttribute((const void*)fmha_fwd_fp8_kernel<T, NW, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        (void)hipFuncSetAttribute((const void*)fmha_fwd_fp8_kernel<T, NW, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+        (void)hipFuncSetAttribute((const void*)fmha_fwd_fp8_kernel<T, NW, true, VARLEN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+        (void)hipFuncSetAttribute((const void*)fmha_fwd_fp8_kernel<T, NW, false, VARLEN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
     });
     note_launch("fmha_fwd_fp8_kernel<8 waves>", pp.persistent, 0, grid.x, grid.y, grid.z, NW * 64);
     hipLaunchKernelGGL(kern, grid, dim3(NW * 64), smem, st, pp);
@@ -86,12 +96,17 @@ static hipError_t launch_fp8_t(const FwdParams& p, hipStream_t st) {
 
 hipError_t launch_fwd_fp8(const FwdParams& p, bool out_fp16, hipStream_t st) {
 #if XFA_VARIANTS
-    if (p.fwd4 == 2 && p.k_row == p.v_row && (p.wl < 0 || p.wl >= p.seqlen_k))
+    // (the ping-pong kernel's prologue is dense only: a varlen launch goes to the 4-wave kernel)
+    if (p.fwd4 == 2 && !p.cu_seqlens_q && p.k_row == p.v_row && (p.wl < 0 || p.wl >= p.seqlen_k))
         return out_fp16 ? launch_fp8_pp<true>(p, st) : launch_fp8_pp<false>(p, st);
 #endif
-    if (p.fwd4 && p.k_row == p.v_row && (p.wl < 0 || p.wl >= p.seqlen_k))
-        return out_fp16 ? launch_fp8_w4<true>(p, st) : launch_fp8_w4<false>(p, st);
-    return out_fp16 ? launch_fp8_t<_Float16>(p, st) : launch_fp8_t<__bf16>(p, st);
+    const bool w4 = p.fwd4 && p.k_row == p.v_row && (p.wl < 0 || p.wl >= p.seqlen_k);
+    if (p.cu_seqlens_q) {
+        if (w4) return out_fp16 ? launch_fp8_w4<true, true>(p, st) : launch_fp8_w4<false, true>(p, st);
+        return out_fp16 ? launch_fp8_t<_Float16, true>(p, st) : launch_fp8_t<__bf16, true>(p, st);
+    }
+    if (w4) return out_fp16 ? launch_fp8_w4<true, false>(p, st) : launch_fp8_w4<false, false>(p, st);
+    return out_fp16 ? launch_fp8_t<_Float16, false>(p, st) : launch_fp8_t<__bf16, false>(p, st);
 }
 
 }  // namespace xfa

@@ -47,7 +47,7 @@ __device__ __forceinline__ int v8_off(int row, int chunk) {      // V tile image
 
 constexpr int kFp8Tile = 64 * 128;        // bytes of one K (or V) tile: 64 keys x D = 128
 
-template <typename T, int NW, bool MASK>
+template <typename T, int NW, bool MASK, bool VARLEN>
 __device__ __forceinline__ void fwd8_item(const FwdParams& p, char* smem, const int bh,
                                           const int m_block) {
     constexpr int HD = 128;
@@ -67,11 +67,13 @@ __device__ __forceinline__ void fwd8_item(const FwdParams& p, char* smem, const 
 
     const int bidx = bh / p.hk;
     const int hk_i = bh - bidx * p.hk;
-    const int sq = p.seqlen_q, sk = p.seqlen_k;
+    // varlen / seqused_k: this sequence's rows of the packed tensors (dense: q_off = k_off = 0)
+    const SeqRange sr = seq_range<VARLEN>(p, bidx);
+    const int q_off = sr.q_off, sq = sr.sq, k_off = sr.k_off, sk = sr.sk;
     const int G = p.group;
     const int rows_total = sq * G;
     const int row0 = m_block * BM;
-    if (row0 >= rows_total) return;
+    if (row0 >= rows_total) return;          // workgroup-uniform (also sq <= 0)
     const int diag = sk - sq;
     auto lim_r = [&](int pos) { return (MASK && p.wr >= 0) ? min(sk, pos + diag + p.wr + 1) : sk; };
     auto lim_l = [&](int pos) { return (MASK && p.wl >= 0) ? max(0, pos + diag - p.wl) : 0; };
@@ -99,7 +101,8 @@ __device__ __forceinline__ void fwd8_item(const FwdParams& p, char* smem, const 
     // ---- Q fragments: lane holds Q[row][64 s + 32 hh .. +31] (fp8 bytes) for s = 0, 1
     i32x8 qf[2];
     {
-        const char* qseq = reinterpret_cast<const char*>(p.q) + (int64_t)bidx * p.q_batch;
+        // base and extent of this sequence's own rows (a lane past them reads zeros)
+        const char* qseq = reinterpret_cast<const char*>(p.q) + (int64_t)bidx * p.q_batch + (int64_t)q_off * p.q_row;
         const uint32_t qbytes = (uint32_t)((int64_t)(sq - 1) * p.q_row + (int64_t)(p.h - 1) * p.q_head + HD);
         const __amdgpu_buffer_rsrc_t qr = make_rsrc(qseq, qbytes);
         const int qo = row_ok ? (int)((int64_t)pos * p.q_row + (int64_t)head * p.q_head) + 32 * hh : kOOB;
@@ -113,8 +116,8 @@ __device__ __forceinline__ void fwd8_item(const FwdParams& p, char* smem, const 
     // ---- K / V tiles by LDS-DMA: piece g (8 rows x 8 chunks) of a tile, lane l lands at
     // g KiB + 16 l, i.e. row 8 g + l / 8, image chunk l % 8, fetched from the source chunk the
     // image XOR places there
-    const char* kseq = reinterpret_cast<const char*>(p.k) + (int64_t)bidx * p.k_batch + (int64_t)hk_i * p.k_head;
-    const char* vseq = reinterpret_cast<const char*>(p.v) + (int64_t)bidx * p.v_batch + (int64_t)hk_i * p.v_head;
+    const char* kseq = reinterpret_cast<const char*>(p.k) + (int64_t)bidx * p.k_batch + (int64_t)k_off * p.k_row + (int64_t)hk_i * p.k_head;
+    const char* vseq = reinterpret_cast<const char*>(p.v) + (int64_t)bidx * p.v_batch + (int64_t)k_off * p.v_row + (int64_t)hk_i * p.v_head;
     const uint32_t kbytes = (uint32_t)((int64_t)(sk > 0 ? sk - 1 : 0) * p.k_row + HD);
     const uint32_t vbytes = (uint32_t)((int64_t)(sk > 0 ? sk - 1 : 0) * p.v_row + HD);
     const __amdgpu_buffer_rsrc_t krs = make_rsrc(kseq, kbytes);
@@ -540,22 +543,30 @@ __device__ __forceinline__ void fwd8_item(const FwdParams& p, char* smem, const 
     const bool empty = (l_full == 0.f) || (l_full != l_full);
     const float inv = empty ? 1.f : p.v_scale / l_full;
     if (!row_ok) return;
-    T* orow = reinterpret_cast<T*>(p.o) + (int64_t)bidx * p.o_batch + (int64_t)pos * p.o_row +
+    T* orow = reinterpret_cast<T*>(p.o) + (int64_t)bidx * p.o_batch + (int64_t)(q_off + pos) * p.o_row +
               (int64_t)head * p.o_head;
     store_o_row16<T, ND>(orow, acc_o, inv, HD, hh);
     if (p.lse && hh == 0)
-        p.lse[(int64_t)bidx * p.lse_batch + (int64_t)head * p.lse_head + pos] =
+        p.lse[(int64_t)bidx * p.lse_batch + (int64_t)head * p.lse_head + q_off + pos] =
             empty ? INFINITY : (m_sc + __log2f(l_full)) * kLn2;
 }
 
-template <typename T, int NW, bool MASK>
+template <typename T, int NW, bool MASK, bool VARLEN>
 __global__ void __launch_bounds__(NW * 64, 2) fmha_fwd_fp8_kernel(const FwdParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    __shared__ int s_claim[2];
     const int nbh = p.b * p.hk;
     const int g = gridDim.x;
     for (int k = 0;; ++k) {
         int bh, m_block;
-        if (p.persistent == 2) {         // XCD-grouped (n-1-i, i) row-block pairs (fmha_fwd_kernel.h)
+        if (VARLEN && p.persistent == 3) {   // varlen: one dynamic item queue, last row blocks first
+            if (threadIdx.x == 0) s_claim[k & 1] = atomicAdd(p.work_ctr + 2, 1);
+            __syncthreads();
+            const int q = __builtin_amdgcn_readfirstlane(s_claim[k & 1]);
+            if (q >= nbh * p.n_mblocks) break;
+            bh = q % nbh;
+            m_block = p.n_mblocks - 1 - q / nbh;
+        } else if (p.persistent == 2) {  // XCD-grouped (n-1-i, i) row-block pairs (fmha_fwd_kernel.h)
             const int nm = p.n_mblocks, npair = (nm + 1) >> 1;
             const int bid = (int)blockIdx.x;
             const int v = (bid & 7) * (g >> 3) + (bid >> 3);
@@ -575,7 +586,15 @@ __global__ void __launch_bounds__(NW * 64, 2) fmha_fwd_fp8_kernel(const FwdParam
             bh = blockIdx.x;
             m_block = gridDim.y - 1 - blockIdx.y;
         }
-        fwd8_item<T, NW, MASK>(p, smem, bh, m_block);
+        fwd8_item<T, NW, MASK, VARLEN>(p, smem, bh, m_block);
+    }
+    if (VARLEN && p.persistent == 3 && threadIdx.x == 0) {
+        // the grid's last workgroup resets the queue counters for the next launch on the stream
+        const int total = (int)(gridDim.x * gridDim.y * gridDim.z);
+        if (atomicAdd(p.work_ctr + 1, 1) == total - 1) {
+            for (int i = 2; i < 10; ++i) atomicExch(p.work_ctr + i, 0);
+            atomicExch(p.work_ctr + 1, 0);
+        }
     }
 }
 

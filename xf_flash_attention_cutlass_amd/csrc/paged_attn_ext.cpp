@@ -751,6 +751,72 @@ mha_fwd_fp8(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
     return {out, lse};
 }
 
+// fp8 e4m3fn forward over packed sequences (extension): q [total_q, h, 128], k/v
+// [total_k, hk, 128], cu_seqlens int32 [b + 1], optional seqused_k int32 [b]; returns
+// {out [total_q, h, 128] (out dtype), lse [h, total_q]}.
+std::vector<at::Tensor>
+mha_varlen_fwd_fp8(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+                   c10::optional<at::Tensor>& out_, const at::Tensor& cu_seqlens_q,
+                   const at::Tensor& cu_seqlens_k, c10::optional<at::Tensor>& seqused_k,
+                   int max_seqlen_q, const int max_seqlen_k, const float q_scale,
+                   const float k_scale, const float v_scale, const float softmax_scale,
+                   bool is_causal, int window_size_left, int window_size_right, const bool out_fp16) {
+    TORCH_CHECK(q.element_size() == 1 && k.element_size() == 1 && v.element_size() == 1,
+                "fp8 varlen forward: q, k and v must be float8_e4m3fn (or uint8 bytes)");
+    CHECK_DEVICE(q); CHECK_DEVICE(k); CHECK_DEVICE(v);
+    CHECK_CONTIGUOUS(q); CHECK_CONTIGUOUS(k); CHECK_CONTIGUOUS(v);
+    TORCH_CHECK(q.dim() == 3 && k.dim() == 3 && v.dim() == 3, "q, k, v must be [total, h, d]");
+    TORCH_CHECK(cu_seqlens_q.dtype() == torch::kInt32, "cu_seqlens_q must have dtype int32");
+    TORCH_CHECK(cu_seqlens_k.dtype() == torch::kInt32, "cu_seqlens_k must have dtype int32");
+    CHECK_DEVICE(cu_seqlens_q); CHECK_DEVICE(cu_seqlens_k);
+    CHECK_CONTIGUOUS(cu_seqlens_q); CHECK_CONTIGUOUS(cu_seqlens_k);
+    TORCH_CHECK(cu_seqlens_q.device() == q.device() && cu_seqlens_k.device() == q.device(),
+                "cu_seqlens must be on q's device");
+    const int total_q = q.size(0), num_heads = q.size(1), d = q.size(2);
+    const int total_k = k.size(0), num_heads_k = k.size(1);
+    const int batch_size = cu_seqlens_q.numel() - 1;
+    TORCH_CHECK(batch_size > 0, "batch size must be positive");
+    TORCH_CHECK(d == 128, "fp8 forward supports head_size 128");
+    CHECK_SHAPE(k, total_k, num_heads_k, d);
+    CHECK_SHAPE(v, total_k, num_heads_k, d);
+    CHECK_SHAPE(cu_seqlens_q, batch_size + 1);
+    CHECK_SHAPE(cu_seqlens_k, batch_size + 1);
+    TORCH_CHECK(num_heads % num_heads_k == 0, "Number of heads in key/value must divide number of heads in query");
+    TORCH_CHECK(max_seqlen_q > 0 && max_seqlen_k > 0, "max_seqlen_q and max_seqlen_k must be positive");
+    at::Tensor seqused;
+    if (seqused_k.has_value()) {
+        seqused = seqused_k.value();
+        TORCH_CHECK(seqused.dtype() == torch::kInt32, "seqused_k must have dtype int32");
+        TORCH_CHECK(seqused.is_cuda() && seqused.device() == q.device(), "seqused_k must be on q's device");
+        TORCH_CHECK(seqused.is_contiguous(), "seqused_k must be contiguous");
+        CHECK_SHAPE(seqused, batch_size);
+    }
+    if (max_seqlen_q == 1) is_causal = false;
+    if (is_causal) window_size_right = 0;
+    if (window_size_left >= max_seqlen_k) window_size_left = -1;
+    if (window_size_right >= max_seqlen_k) window_size_right = -1;
+    const c10::DeviceGuard device_guard(q.device());
+    const auto odt = out_fp16 ? torch::kFloat16 : torch::kBFloat16;
+    at::Tensor out;
+    if (out_.has_value()) {
+        out = out_.value();
+        TORCH_CHECK(out.dtype() == odt, "out has the wrong dtype");
+        CHECK_DEVICE(out); CHECK_CONTIGUOUS(out);
+        CHECK_SHAPE(out, total_q, num_heads, d);
+    } else {
+        out = torch::empty({total_q, num_heads, d}, q.options().dtype(odt));
+    }
+    auto lse = torch::empty({num_heads, total_q}, q.options().dtype(at::kFloat));
+    if (total_q == 0) return {out, lse};
+    fmha_varlen_fwd_fp8(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), lse.data_ptr(),
+                        cu_seqlens_q.data_ptr(), cu_seqlens_k.data_ptr(),
+                        seqused.defined() ? seqused.data_ptr() : nullptr, q_scale, k_scale, v_scale,
+                        max_seqlen_q, max_seqlen_k, total_q, batch_size, num_heads, num_heads_k, d,
+                        softmax_scale, window_size_left, window_size_right, out_fp16, cur_stream());
+    raise_if_failed("varlen_fwd_fp8");
+    return {out, lse};
+}
+
 PYBIND11_MODULE(paged_attn, m) {
     m.doc() = "FlashAttention for MI355X (gfx950): hand-written HIP kernels behind the paged_attn C ABI";
     m.def("fwd", &mha_fwd, "Forward pass");
@@ -768,5 +834,6 @@ PYBIND11_MODULE(paged_attn, m) {
     m.def("varlen_bwd", &mha_varlen_bwd, "Backward pass (variable length)");
     m.def("fwd_kvcache_fp8", &mha_fwd_kvcache_fp8, "Paged decode over an fp8 e4m3fn K/V cache");
     m.def("fwd_fp8", &mha_fwd_fp8, "Forward pass over fp8 e4m3fn q/k/v (fp8 MFMA)");
-    m.def("version", []() { return std::string(fmha_version()); });
+    m.def("varlen_fwd_fp8", &mha_varlen_fwd_fp8, "Forward pass over packed fp8 e4m3fn q/k/v (variable length)");
+    m.def("version",[]() { return std::string(fmha_version()); });
 }

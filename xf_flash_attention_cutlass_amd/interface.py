@@ -126,13 +126,56 @@ class _FlashAttnVarlenFunc(torch.autograd.Function):
         return (dq, dk, dv) + (None,) * 13
 
 
+def flash_attn_varlen_fp8_func(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k,
+                               q_descale=None, k_descale=None, v_descale=None,
+                               softmax_scale=None, causal=False, window_size=(-1, -1),
+                               out_dtype=torch.bfloat16, return_lse=False, seqused_k=None):
+    """Packed fp8 e4m3fn q [total_q, h, 128], k/v [total_k, hk, 128], cu_seqlens int32 [b + 1],
+    per-tensor descales (floats or one-element tensors; None = 1.0), optional seqused_k int32
+    [b]: the fp8-MFMA forward over variable-length sequences.  Forward only; the LSE is
+    [h, total_q]."""
+    if q.requires_grad or k.requires_grad or v.requires_grad:
+        raise NotImplementedError("the fp8 forward has no backward")
+    if out_dtype not in (torch.bfloat16, torch.float16):
+        raise ValueError("out_dtype must be bfloat16 or float16")
+    if softmax_scale is None:
+        softmax_scale = q.shape[-1] ** (-0.5)
+
+    def _f(x):
+        return 1.0 if x is None else float(x)
+    q, k, v = (_maybe_contiguous(x) for x in (q, k, v))
+    out, lse = paged_attn.varlen_fwd_fp8(q, k, v, None, cu_seqlens_q, cu_seqlens_k, seqused_k,
+                                         int(max_seqlen_q), int(max_seqlen_k), _f(q_descale),
+                                         _f(k_descale), _f(v_descale), softmax_scale, causal,
+                                         int(window_size[0]), int(window_size[1]),
+                                         out_dtype == torch.float16)
+    return (out, lse) if return_lse else out
+
+
 def flash_attn_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k,
                            dropout_p=0.0, softmax_scale=None, causal=False,
                            window_size=(-1, -1), softcap=0.0, alibi_slopes=None,
-                           deterministic=False, return_attn_probs=False, block_table=None):
-    """Packed q [total_q, h, d], k/v [total_k, hk, d], cu_seqlens int32 (test.py:102-149)."""
+                           deterministic=False, return_attn_probs=False, block_table=None, *,
+                           q_descale=None, k_descale=None, v_descale=None,
+                           out_dtype=torch.bfloat16):
+    """Packed q [total_q, h, d], k/v [total_k, hk, d], cu_seqlens int32 (test.py:102-149).
+
+    Extension: float8_e4m3fn q/k/v (with per-tensor descales) run the fp8-MFMA varlen forward
+    (forward only, d = 128, no ALiBi / softcap / dropout / block_table); out is `out_dtype`."""
     if softmax_scale is None:
         softmax_scale = q.shape[-1] ** (-0.5)
+    if q.dtype == torch.float8_e4m3fn:
+        # refuse what the fp8 forward lacks instead of dropping it
+        if dropout_p != 0.0 or softcap != 0.0 or alibi_slopes is not None or block_table is not None:
+            raise NotImplementedError("fp8 q/k/v: dropout, softcap, ALiBi and block_table are not "
+                                      f"supported (dropout_p={dropout_p}, softcap={softcap}, "
+                                      f"alibi={'set' if alibi_slopes is not None else None}, "
+                                      f"block_table={'set' if block_table is not None else None})")
+        out, lse = flash_attn_varlen_fp8_func(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q,
+                                              max_seqlen_k, q_descale, k_descale, v_descale,
+                                              softmax_scale, causal, window_size, out_dtype,
+                                              return_lse=True)
+        return out if not return_attn_probs else (out, lse, None)
     out, lse, s_dmask = _FlashAttnVarlenFunc.apply(
         q, k, v, cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), int(max_seqlen_k), dropout_p,
         softmax_scale, causal, tuple(int(w) for w in window_size), softcap, alibi_slopes,
