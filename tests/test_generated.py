@@ -31,6 +31,33 @@ def test_generated_body_matches_generator(tmp_path, gen, body):
     assert out.read_bytes() == open(os.path.join(CSRC, body), "rb").read()
 
 
+def test_generators_keep_no_state(tmp_path):
+    """One process, every generator: what a generator emits depends on its options alone, not on
+    which modules were imported before it or on what was emitted before it (each body is an object
+    of its own: no generator assigns into another's namespace or keeps options between emits)."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import gen_fwd4, gen_fwd8, gen_fwd8pp, gen_fwdpp, gen_fwdpp16  # noqa: E401
+    gens = [(gen_fwd4, "fmha_fwd4_body.h"), (gen_fwd8, "fmha_fwd8_body.h"), (gen_fwdpp, "fmha_fwdpp_body.h"),
+            (gen_fwdpp16, "fmha_fwdpp16_body.h"), (gen_fwd8pp, "fmha_fwd8pp_body.h")]
+    committed = {body: open(os.path.join(CSRC, body), "rb").read() for _, body in gens}
+
+    def check_defaults(order, tag):
+        for n, (gen, body) in enumerate(order):
+            out = tmp_path / f"{tag}{n}_{body}"
+            gen.emit(str(out))
+            assert out.read_bytes() == committed[body], (tag, body)
+
+    check_defaults(gens, "fwd")
+    check_defaults(gens[::-1], "rev")
+    # a non-default body (stamps: no paged functions), then the default one (dense and paged)
+    stamps = tmp_path / "stamps.h"
+    gen_fwdpp.emit(str(stamps), stamps=True)
+    text = stamps.read_text()
+    assert "XFA_FWDPP_STAMPS" in text and "fwdpp_pg_item_" not in text
+    assert stamps.read_bytes() != committed["fmha_fwdpp_body.h"]
+    check_defaults(gens, "after")
+
+
 @pytest.mark.parametrize("body", ["fmha_fwd4_body.h", "fmha_fwd8_body.h", "fmha_fwdpp_body.h",
                                   "fmha_fwdpp16_body.h", "fmha_fwd8pp_body.h"])
 def test_return_addresses_guarded(body):
@@ -60,15 +87,14 @@ def test_return_address_guard_assembles(tmp_path, back, ret_first, ok):
     assumes fails to assemble (the guards sit at the end of the statement, as the generators
     emit them)."""
     sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import gen_fwd4
-    gen_fwd4.GUARDS.clear()
+    import asmgen
+    guards = []
     stub = ["s_getpc_b64 s[10:11]", ".Lpc%=:", "s_add_u32 s10, s10, .Lret%= - .Lpc%="]
-    stub += gen_fwd4.addc_ret(11, ".Lret%=", ".Lpc%=", back) + ["s_setpc_b64 s[10:11]"]
+    stub += asmgen.addc_ret(guards, 11, ".Lret%=", ".Lpc%=", back) + ["s_setpc_b64 s[10:11]"]
     ret = [".Lret%=:", "v_mov_b32 v1, 0", "s_branch .Lend%="]
     body = (["s_branch .Lx%="] + ret + [".Lx%=:"] + stub if ret_first else
             ["s_branch .Lx%="] + [".Lx%=:"] + stub + ret)
-    body += [".Lend%=:"] + gen_fwd4.GUARDS
-    gen_fwd4.GUARDS.clear()
+    body += [".Lend%=:"] + guards
     src = tmp_path / "t.hip"
     src.write_text("#include <hip/hip_runtime.h>\n__global__ void k(int* o) {\n  asm volatile(\n" +
                    "".join(f'    "{b}\\n"\n' for b in body) +

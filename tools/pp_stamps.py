@@ -15,7 +15,8 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-CLASSES = ["M run", "M->V wait", "V run", "V->M wait", "prologue", "tail", "epilogue"]
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from gen_fwdpp import ST_NAMES as CLASSES  # noqa: E402
 
 
 def main():
