@@ -159,7 +159,8 @@ def main():
     for i, p in enumerate(a.libs):
         med = statistics.median(times[i])
         rate = (f"{dbytes / med / 1e9:.3f} TB/s" if a.mode == "decode" else f"{fl / med / 1e9:.1f} TFLOP/s")
-        print(f"{a.mode} {os.path.basename(p)}: median {med:.4f} ms  min {min(times[i]):.4f}  -> {rate}")
+        print(f"{a.mode} {os.path.basename(p)}: median {med:.4f} ms  min {min(times[i]):.4f}  max {max(times[i]):.4f}"
+              f"  -> {rate}")
 
 
 if __name__ == "__main__":

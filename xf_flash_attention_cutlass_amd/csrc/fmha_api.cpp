@@ -191,7 +191,8 @@ hipError_t dispatch_bwd(const BwdParams& p, bool bf16, hipStream_t st) {
 
 // Score scaling as set_params_fprop_strided (paged_attn.cpp:93-102): with softcap the
 // kernel computes tanh(s * scale / cap) and then scales by cap.
-void set_scales(FwdParams& p, float softmax_scale, float softcap) {
+template <typename P>
+void set_scales(P& p, float softmax_scale, float softcap) {
     float scale_softmax;
     if (softcap > 0.f) { p.softcap_pre = softmax_scale / softcap; scale_softmax = softcap; }
     else { p.softcap_pre = 0.f; scale_softmax = softmax_scale; }
@@ -199,7 +200,6 @@ void set_scales(FwdParams& p, float softmax_scale, float softcap) {
     p.alibi_mul = 1.f / scale_softmax;
 }
 
-// Window normalisation (paged_attn.cpp:116-120): causal <=> wl < 0 && wr == 0.
 template <typename P>
 static LseAlibiParams lse_alibi_params(const P& p, float sign) {
     LseAlibiParams a{};
@@ -217,6 +217,7 @@ static LseAlibiParams lse_alibi_params(const FwdParams& p, float sign) {
     return a;
 }
 
+// Window normalisation (paged_attn.cpp:116-120): causal <=> wl < 0 && wr == 0.
 // Returns the reference's is_causal (before the normalisation), which picks its ALiBi form.
 bool set_windows(int& wl, int& wr, int seqlen_k) {
     const bool causal = wl < 0 && wr == 0;
@@ -239,15 +240,50 @@ bool check_common(const void* q, const void* k, const void* v, const void* o, in
     return true;
 }
 
-void dense_strides(FwdParams& p, int sq, int sk, int h, int hk, int d) {
-    p.q_row = (int64_t)h * d;  p.q_head = d; p.q_batch = (int64_t)sq * h * d;
-    p.k_row = (int64_t)hk * d; p.k_head = d; p.k_batch = (int64_t)sk * hk * d;
-    p.v_row = (int64_t)hk * d; p.v_head = d; p.v_batch = (int64_t)sk * hk * d;
-    p.o_row = (int64_t)h * d;  p.o_head = d; p.o_batch = (int64_t)sq * h * d;
-    p.lse_batch = (int64_t)h * sq; p.lse_head = sq;
+// ---- the forward packer: what every entry fills the same way, then one layout each ----------
+// pointers, shape, windows, scales, ALiBi
+void fwd_common(FwdParams& p, void* q, void* k, void* v, void* o, void* lse, int b, int h, int hk,
+                int d, int seqlen_q, int seqlen_k, int wl, int wr, float softmax_scale,
+                float softcap, const void* alibi, int alibi_bstride) {
+    p.q = q; p.k = k; p.v = v; p.o = o; p.lse = (float*)lse;
+    p.b = b; p.h = h; p.hk = hk; p.group = h / hk; p.d = d;
+    p.seqlen_q = seqlen_q; p.seqlen_k = seqlen_k;
+    p.alibi_causal = set_windows(wl, wr, seqlen_k);
+    p.wl = wl; p.wr = wr;
+    set_scales(p, softmax_scale, softcap);
+    p.alibi = (const float*)alibi; p.alibi_bstride = alibi_bstride;
 }
 
-// Split scratch + launch (shared by every forward entry).
+// contiguous rows [.., heads, d] (element strides; fp8 elements are bytes, so q/k/v strides are
+// byte strides too), LSE [.., seqlen_q]; the batch strides are the layout's
+void row_strides(FwdParams& p, int h, int hk, int d) {
+    p.q_row = (int64_t)h * d;  p.q_head = d;
+    p.k_row = (int64_t)hk * d; p.k_head = d;
+    p.v_row = (int64_t)hk * d; p.v_head = d;
+    p.o_row = (int64_t)h * d;  p.o_head = d;
+}
+void dense_strides(FwdParams& p, int sq, int sk, int h, int hk, int d) {
+    row_strides(p, h, hk, d);
+    p.q_batch = p.o_batch = (int64_t)sq * h * d;
+    p.k_batch = p.v_batch = (int64_t)sk * hk * d;
+    p.lse_batch = (int64_t)h * sq; p.lse_head = sq;
+}
+// packed rows: no batch stride (cu_seqlens give the offsets); unpadded LSE [num_heads, total_q]
+// (export.cpp:827): index = h * total_q + q_off + pos
+void packed_strides(FwdParams& p, int h, int hk, int d, int total_q) {
+    row_strides(p, h, hk, d);
+    p.q_batch = p.o_batch = p.k_batch = p.v_batch = 0;
+    p.lse_batch = 0; p.lse_head = total_q;
+}
+// paged K/V: the "batch" stride is the page stride (paged_attn.cpp:506-507); pages are per
+// sequence, so there is no k offset
+void paged_kv(FwdParams& p, const void* block_table, int bt_stride, int page, int hk, int d) {
+    p.block_table = (const int*)block_table;
+    p.bt_stride = bt_stride;
+    p.page_size = page;
+    p.k_batch = p.v_batch = (int64_t)page * hk * d;
+}
+
 // Dropout RNG state of the calling thread (fmha_set_rng_state); read by every forward /
 // backward call with p_dropout > 0.
 thread_local uint64_t g_seed = 0, g_offset = 0;
@@ -291,18 +327,33 @@ void run_sdmask(const FwdParams& p, void* s, bool bf16, hipStream_t st) {
            "return_softmax launch");
 }
 
-void run_fwd(FwdParams& p, bool bf16, hipStream_t st, int num_splits_req) {
+// The one place that reads the schedule knobs every forward launch shares.  p.fwd4 carries
+// either kernel-choice knob: fwd_w4 on the bf16 / fp16 forward, fp8_w4 on the fp8 one (their
+// launchers are separate, so the field never means both).
+void load_schedule(FwdParams& p, const std::atomic<int>& w4) {
     Options& o = options();
     p.device = current_device();
     p.num_cus = num_cus(p.device);
-    p.waves = o.fwd_waves.load();
-    p.fwd4 = o.fwd_w4.load();
+    p.fwd4 = w4.load();
     p.persist_per_cu = o.fwd_persistent.load();
     p.order = o.fwd_order.load();
     p.xcdq = o.fwd_xcdq.load();
+    p.max_slack = (float)o.fwd_slack.load();
+}
+// ... and takes the item-queue counter where fwd_dyn reaches `dyn_min`; `code`: the status of
+// a failed allocation
+bool take_item_queue(FwdParams& p, hipStream_t st, int dyn_min, int code) {
+    if (options().fwd_dyn.load() < dyn_min) return true;
+    p.work_ctr = counter_get(st);
+    return p.work_ctr || fail(code, "could not allocate the item-queue counters");
+}
+
+void run_fwd(FwdParams& p, bool bf16, hipStream_t st, int num_splits_req) {
+    Options& o = options();
+    load_schedule(p, o.fwd_w4);
+    p.waves = o.fwd_waves.load();
     p.prio_hi = o.fwd_prio.load();
     p.pipe = o.fwd_pipe.load();
-    p.max_slack = (float)o.fwd_slack.load();
     const int n_blocks = (p.seqlen_k + kBlockN - 1) / kBlockN;
     if (p.drop) num_splits_req = 1;       // no split-KV with dropout (paged_attn.cpp:180)
     int splits = num_splits_req;
@@ -332,7 +383,6 @@ void run_fwd(FwdParams& p, bool bf16, hipStream_t st, int num_splits_req) {
     if (!p.decode) splits = std::max(1, std::min(splits, std::min(128, std::max(1, n_blocks))));
     p.num_splits = splits;
     g_last_splits = splits;
-    g_last_kernel[0] = 0;
     // Ragged caches (per-sequence lengths): the b * splits slots of a kv-head group are shared
     // in proportion to the sequences' key tiles, up to 128 splits for one sequence
     // (fmha_decode_kernel.h dec_slot); equal lengths give the same splits as without.
@@ -369,18 +419,38 @@ void run_fwd(FwdParams& p, bool bf16, hipStream_t st, int num_splits_req) {
     // profiles/r06_window_dyn_ab.log), and the non-causal ALiBi launches (32x32x16 body, +0.5 to
     // +3.2 % on two boxes; non-causal softcap measured -0.4 % and keeps the pairs:
     // r06_noncausal_feat_ab.log)
-    p.work_ctr = nullptr;
-    const int dyn = o.fwd_dyn.load();
     const bool nc16 = p.d == 128 && p.wr < 0 && p.fwd4 == 4 && !p.alibi && !(p.softcap_pre > 0.f);
     const bool ncab = p.d == 128 && p.wr < 0 && p.fwd4 == 4 && p.alibi;
     const bool win = p.d == 128 && p.fwd4 == 4 && p.wl >= 0 && p.wl < p.seqlen_k;  // causal: wl = seqlen_k
-    if (!p.decode && splits == 1 && (dyn == 2 || (dyn == 1 && (p.cu_seqlens_q || nc16 || ncab || win)))) {
-        p.work_ctr = counter_get(st);
-        if (!p.work_ctr) { fail(3, "could not allocate the item-queue counters"); return; }
-    }
+    const int dyn_min = (p.cu_seqlens_q || nc16 || ncab || win) ? 1 : 2;
+    if (!p.decode && splits == 1 && !take_item_queue(p, st, dyn_min, 3)) return;
     if (!hip_ok(dispatch_fwd(p, bf16, st), "forward launch")) return;
     // causal ALiBi: the LSE in the reference's convention (+slope key, mask_hip.h:163-164)
     if (p.lse && p.alibi && p.alibi_causal) hip_ok(launch_lse_alibi(lse_alibi_params(p, +1.f), st), "LSE ALiBi pass");
+}
+
+// The fp8 forward's launch (one pass, D = 128): the schedule knobs with fp8_w4 as the kernel
+// choice and none of fwd_waves / fwd_prio / fwd_pipe, which its kernels do not read
+void run_fwd_fp8(FwdParams& p, float q_scale, float k_scale, float v_scale, int dyn_min,
+                 bool out_fp16, hipStream_t st, const char* what) {
+    p.q_scale = q_scale; p.k_scale = k_scale; p.v_scale = v_scale;
+    load_schedule(p, options().fp8_w4);
+    p.num_splits = 1;
+    if (!take_item_queue(p, st, dyn_min, 1)) return;
+    g_last_splits = 1;
+    hip_ok(launch_fwd_fp8(p, out_fp16, st), what);
+}
+
+// One knob of XFA_KNOBS by name (nullptr: unknown)
+struct Knob { const char* name; std::atomic<int>* slot; int lo, hi; };
+const Knob* find_knob(const char* name) {
+    Options& o = options();
+#define XFA_KNOB_ROW(n, def, lo, hi) {#n, &o.n, lo, hi},
+    static const Knob knobs[] = {XFA_KNOBS(XFA_KNOB_ROW)};
+#undef XFA_KNOB_ROW
+    for (const Knob& k : knobs)
+        if (!strcmp(name, k.name)) return &k;
+    return nullptr;
 }
 
 }  // namespace
@@ -412,49 +482,27 @@ int fmha_set_option(const char* name, int value) {
     clear_error();
     if (!name) { fail(1, "option name is null"); return -1; }
     Options& o = options();
-    struct Knob { const char* name; std::atomic<int>* slot; int lo, hi; };
-    const Knob knobs[] = {
-        {"fwd_waves", &o.fwd_waves, 4, 8},       {"fwd_prio", &o.fwd_prio, 0, 1},
-        {"fwd_persistent", &o.fwd_persistent, 0, 8}, {"fwd_slack", &o.fwd_slack, 0, 16},
-        {"fwd_order", &o.fwd_order, 0, 1},       {"fwd_dyn", &o.fwd_dyn, 0, 2},
-        {"fwd_xcdq", &o.fwd_xcdq, 0, 1},         {"fwd_pipe", &o.fwd_pipe, 0, 2},
-        {"fwd_decode", &o.fwd_decode, 0, 1},     {"dec_wg_per_cu", &o.dec_wg_per_cu, 1, 16},
-        {"dec_hmaj", &o.dec_hmaj, 0, 2},
-        {"dec_mr", &o.dec_mr, 16, 32},           {"fwd_w4", &o.fwd_w4, 0, 4},
-        {"bwd_order", &o.bwd_order, 0, 1},       {"bwd_desc", &o.bwd_desc, 0, 1},
-        {"dec_fold", &o.dec_fold, 0, 1},        {"dec_bal", &o.dec_bal, 0, 1},
-        {"fp8_w4", &o.fp8_w4, 0, 2},           {"comb_row", &o.comb_row, 0, 1},
-    };
-    for (const Knob& k : knobs) {
-        if (strcmp(name, k.name)) continue;
-        if (value < k.lo || value > k.hi || (k.slot == &o.fwd_waves && value != 4 && value != 8) ||
-            (k.slot == &o.dec_mr && value != 16 && value != 32)) {
-            fail(1, "option %s: value %d out of range [%d, %d]", name, value, k.lo, k.hi);
-            return -1;
-        }
-        if (!XFA_VARIANTS && ((k.slot == &o.fwd_w4 && value == 1) || (k.slot == &o.fp8_w4 && value == 2))) {
-            fail(1, "option %s = %d selects a kernel only the variants build has "
-                    "(lib/variants/libpaged-attention.so, build.py --variants)", name, value);
-            return -1;
-        }
-        k.slot->store(value);
-        return 0;
+    const Knob* k = find_knob(name);
+    if (!k) { fail(1, "unknown option '%s'", name); return -1; }
+    // two knobs take only the ends of their range
+    const bool ends_only = k->slot == &o.fwd_waves || k->slot == &o.dec_mr;
+    if (value < k->lo || value > k->hi || (ends_only && value != k->lo && value != k->hi)) {
+        fail(1, "option %s: value %d out of range [%d, %d]", name, value, k->lo, k->hi);
+        return -1;
     }
-    fail(1, "unknown option '%s'", name);
-    return -1;
+    if (!XFA_VARIANTS && ((k->slot == &o.fwd_w4 && value == 1) || (k->slot == &o.fp8_w4 && value == 2))) {
+        fail(1, "option %s = %d selects a kernel only the variants build has "
+                "(lib/variants/libpaged-attention.so, build.py --variants)", name, value);
+        return -1;
+    }
+    k->slot->store(value);
+    return 0;
 }
 
 int fmha_get_option(const char* name) {
     clear_error();
-    Options& o = options();
     if (!name) { fail(1, "option name is null"); return -1; }
-#define XFA_GET(n) if (!strcmp(name, #n)) return o.n.load();
-    XFA_GET(fwd_waves) XFA_GET(fwd_prio) XFA_GET(fwd_persistent) XFA_GET(fwd_slack)
-    XFA_GET(fwd_order) XFA_GET(fwd_dyn) XFA_GET(fwd_xcdq) XFA_GET(fwd_pipe) XFA_GET(fwd_decode)
-    XFA_GET(dec_wg_per_cu) XFA_GET(dec_hmaj) XFA_GET(dec_mr) XFA_GET(fwd_w4)
-    XFA_GET(bwd_order) XFA_GET(bwd_desc) XFA_GET(dec_fold) XFA_GET(dec_bal) XFA_GET(fp8_w4)
-    XFA_GET(comb_row)
-#undef XFA_GET
+    if (const Knob* k = find_knob(name)) return k->slot->load();
     fail(1, "unknown option '%s'", name);
     return -1;
 }
@@ -476,16 +524,10 @@ void fmha_fwd(void* q_ptr, void* k_ptr, void* v_ptr, void* o_ptr, void* alibi_sl
         if (!slab_ok("q/o", seqlen_q, (int64_t)num_heads * head_size, 2) ||
             !slab_ok("k/v", seqlen_k, (int64_t)num_heads_k * head_size, 2)) return;
         FwdParams p{};
-        p.q = q_ptr; p.k = k_ptr; p.v = v_ptr; p.o = o_ptr;
-        p.lse = (float*)softmax_lse_ptr;
+        fwd_common(p, q_ptr, k_ptr, v_ptr, o_ptr, softmax_lse_ptr, batch_size, num_heads, num_heads_k,
+                   head_size, seqlen_q, seqlen_k, window_size_left, window_size_right, softmax_scale,
+                   softcap, alibi_slopes_ptr, batch_size > 1 ? num_heads : 0);   // paged_attn.cpp:375
         dense_strides(p, seqlen_q, seqlen_k, num_heads, num_heads_k, head_size);
-        p.b = batch_size; p.h = num_heads; p.hk = num_heads_k; p.group = num_heads / num_heads_k;
-        p.d = head_size; p.seqlen_q = seqlen_q; p.seqlen_k = seqlen_k;
-        p.alibi_causal = set_windows(window_size_left, window_size_right, seqlen_k);
-        p.wl = window_size_left; p.wr = window_size_right;
-        set_scales(p, softmax_scale, softcap);
-        p.alibi = (const float*)alibi_slopes_ptr;
-        p.alibi_bstride = batch_size > 1 ? num_heads : 0;   // paged_attn.cpp:375
         if (!set_dropout(p, p_dropout, softcap)) return;
         run_fwd(p, !is_fp16, stream, num_splits);
         if (return_softmax && g_status == 0) run_sdmask(p, p_ptr, !is_fp16, stream);
@@ -526,20 +568,14 @@ void fmha_fwd_strided(void* q, void* k, void* v, void* o, void* alibi_slopes, vo
         if (!slab("q", seqlen_q, st[1], st[2], num_heads) || !slab("k", seqlen_k, st[4], st[5], num_heads_k) ||
             !slab("v", seqlen_k, st[7], st[8], num_heads_k) || !slab("o", seqlen_q, st[10], st[11], num_heads)) return;
         FwdParams p{};
-        p.q = q; p.k = k; p.v = v; p.o = o;
-        p.lse = (float*)softmax_lse;
+        fwd_common(p, q, k, v, o, softmax_lse, batch_size, num_heads, num_heads_k, head_size,
+                   seqlen_q, seqlen_k, window_size_left, window_size_right, softmax_scale, softcap,
+                   alibi_slopes, batch_size > 1 ? num_heads : 0);
         p.q_batch = st[0]; p.q_row = st[1]; p.q_head = st[2];
         p.k_batch = st[3]; p.k_row = st[4]; p.k_head = st[5];
         p.v_batch = st[6]; p.v_row = st[7]; p.v_head = st[8];
         p.o_batch = st[9]; p.o_row = st[10]; p.o_head = st[11];
         p.lse_batch = (int64_t)num_heads * seqlen_q; p.lse_head = seqlen_q;
-        p.b = batch_size; p.h = num_heads; p.hk = num_heads_k; p.group = num_heads / num_heads_k;
-        p.d = head_size; p.seqlen_q = seqlen_q; p.seqlen_k = seqlen_k;
-        p.alibi_causal = set_windows(window_size_left, window_size_right, seqlen_k);
-        p.wl = window_size_left; p.wr = window_size_right;
-        set_scales(p, softmax_scale, softcap);
-        p.alibi = (const float*)alibi_slopes;
-        p.alibi_bstride = batch_size > 1 ? num_heads : 0;
         REQUIRE(!s_dmask || (p_dropout > 0.f && softmax_lse), "s_dmask needs p_dropout > 0 and softmax_lse");
         if (!set_dropout(p, p_dropout, softcap)) return;
         run_fwd(p, !is_fp16, stream, num_splits);
@@ -564,34 +600,11 @@ void fmha_fwd_fp8(void* q, void* k, void* v, void* o, void* softmax_lse, float q
             !slab_ok("k/v", seqlen_k, (int64_t)num_heads_k * head_size, 1) ||
             !slab_ok("o", seqlen_q, (int64_t)num_heads * head_size, 2)) return;
         FwdParams p{};
-        p.q = q; p.k = k; p.v = v; p.o = o;
-        p.lse = (float*)softmax_lse;
-        // element strides; fp8 elements are bytes, so q/k/v strides are byte strides too
+        fwd_common(p, q, k, v, o, softmax_lse, batch_size, num_heads, num_heads_k, head_size,
+                   seqlen_q, seqlen_k, window_size_left, window_size_right, softmax_scale, 0.f, nullptr, 0);
         dense_strides(p, seqlen_q, seqlen_k, num_heads, num_heads_k, head_size);
-        p.b = batch_size; p.h = num_heads; p.hk = num_heads_k; p.group = num_heads / num_heads_k;
-        p.d = head_size; p.seqlen_q = seqlen_q; p.seqlen_k = seqlen_k;
-        p.alibi_causal = set_windows(window_size_left, window_size_right, seqlen_k);
-        p.wl = window_size_left; p.wr = window_size_right;
-        set_scales(p, softmax_scale, 0.f);
-        p.q_scale = q_scale; p.k_scale = k_scale; p.v_scale = v_scale;
-        Options& op = options();
-        p.device = current_device();
-        p.num_cus = num_cus(p.device);
-        p.persist_per_cu = op.fwd_persistent.load();
-        p.order = op.fwd_order.load();
-        p.max_slack = (float)op.fwd_slack.load();
-        p.num_splits = 1;
-        p.fwd4 = op.fp8_w4.load();
-        p.xcdq = op.fwd_xcdq.load();
         // fwd_dyn = 2: the dynamic per-XCD item queues for the dense fp8 launch too
-        p.work_ctr = nullptr;
-        if (op.fwd_dyn.load() == 2) {
-            p.work_ctr = counter_get(stream);
-            REQUIRE(p.work_ctr, "could not allocate the item-queue counters");
-        }
-        g_last_splits = 1;
-        g_last_kernel[0] = 0;
-        hip_ok(launch_fwd_fp8(p, out_fp16, stream), "fp8 forward launch");
+        run_fwd_fp8(p, q_scale, k_scale, v_scale, 2, out_fp16, stream, "fp8 forward launch");
     } catch (...) {
         fail(9, "internal error in fmha_fwd_fp8");
     }
@@ -618,45 +631,16 @@ void fmha_varlen_fwd_fp8(void* q, void* k, void* v, void* o, void* softmax_lse,
             !slab_ok("o", max_seqlen_q, (int64_t)num_heads * head_size, 2) ||
             (softmax_lse && !slab_ok("softmax_lse", total_q, num_heads, 4))) return;
         FwdParams p{};
-        p.q = q; p.k = k; p.v = v; p.o = o;
-        p.lse = (float*)softmax_lse;
-        const int h = num_heads, hk = num_heads_k, d = head_size;
-        // packed rows: element (= byte, for q/k/v) strides, no batch stride
-        p.q_row = (int64_t)h * d; p.q_head = d; p.q_batch = 0;
-        p.o_row = (int64_t)h * d; p.o_head = d; p.o_batch = 0;
-        p.k_row = (int64_t)hk * d; p.k_head = d; p.k_batch = 0;
-        p.v_row = (int64_t)hk * d; p.v_head = d; p.v_batch = 0;
-        // unpadded LSE [num_heads, total_q], as fmha_varlen_fwd_ex
-        p.lse_batch = 0;
-        p.lse_head = total_q;
+        fwd_common(p, q, k, v, o, softmax_lse, batch_size, num_heads, num_heads_k, head_size,
+                   max_seqlen_q, max_seqlen_k, window_size_left, window_size_right, softmax_scale, 0.f,
+                   nullptr, 0);
+        packed_strides(p, num_heads, num_heads_k, head_size, total_q);
         p.cu_seqlens_q = (const int*)cu_seqlens_q;
         p.cu_seqlens_k = (const int*)cu_seqlens_k;
         p.seqused_k = (const int*)seqused_k;
-        p.b = batch_size; p.h = h; p.hk = hk; p.group = h / hk; p.d = d;
-        p.seqlen_q = max_seqlen_q; p.seqlen_k = max_seqlen_k;
-        p.alibi_causal = set_windows(window_size_left, window_size_right, max_seqlen_k);
-        p.wl = window_size_left; p.wr = window_size_right;
-        set_scales(p, softmax_scale, 0.f);
-        p.q_scale = q_scale; p.k_scale = k_scale; p.v_scale = v_scale;
-        Options& op = options();
-        p.device = current_device();
-        p.num_cus = num_cus(p.device);
-        p.persist_per_cu = op.fwd_persistent.load();
-        p.order = op.fwd_order.load();
-        p.max_slack = (float)op.fwd_slack.load();
-        p.num_splits = 1;
-        p.fwd4 = op.fp8_w4.load();
-        p.xcdq = op.fwd_xcdq.load();
         // ragged items balance from the dynamic item queue (fwd_dyn >= 1, as the bf16 varlen
         // launches); fwd_dyn = 0 keeps the static persistent schedules
-        p.work_ctr = nullptr;
-        if (op.fwd_dyn.load() >= 1) {
-            p.work_ctr = counter_get(stream);
-            REQUIRE(p.work_ctr, "could not allocate the item-queue counters");
-        }
-        g_last_splits = 1;
-        g_last_kernel[0] = 0;
-        hip_ok(launch_fwd_fp8(p, out_fp16, stream), "fp8 varlen forward launch");
+        run_fwd_fp8(p, q_scale, k_scale, v_scale, 1, out_fp16, stream, "fp8 varlen forward launch");
     } catch (...) {
         fail(9, "internal error in fmha_varlen_fwd_fp8");
     }
@@ -681,41 +665,24 @@ void fmha_varlen_fwd_ex(void* q, void* k, void* v, void* o, void* softmax_lse,
         if (max_seqlen_k == 0) { fail(1, "max_seqlen_k == 0: nothing to attend to"); return; }
         if (!slab_ok("q/o", max_seqlen_q, (int64_t)num_heads * head_size, 2) ||
             (!block_table && !slab_ok("k/v", max_seqlen_k, (int64_t)num_heads_k * head_size, 2))) return;
-        FwdParams p{};
-        p.q = q; p.k = k; p.v = v; p.o = o; p.lse = (float*)softmax_lse;
-        const int h = num_heads, hk = num_heads_k, d = head_size;
-        p.q_row = (int64_t)h * d; p.q_head = d; p.q_batch = 0;
-        p.o_row = (int64_t)h * d; p.o_head = d; p.o_batch = 0;
-        p.k_row = (int64_t)hk * d; p.k_head = d; p.k_batch = 0;
-        p.v_row = (int64_t)hk * d; p.v_head = d; p.v_batch = 0;
-        p.cu_seqlens_q = (const int*)cu_seqlens_q;
         if (block_table) {
             REQUIRE(page_block_size > 0, "page_block_size must be positive");
-            p.block_table = (const int*)block_table;
-            p.bt_stride = block_table_stride;
-            p.page_size = page_block_size;
-            p.k_batch = (int64_t)page_block_size * hk * d;
-            p.v_batch = (int64_t)page_block_size * hk * d;
-            // key lengths from seqused_k or cu_seqlens_k; pages are per sequence (no k offset)
-            p.cu_seqlens_k = (const int*)cu_seqlens_k;
+            // key lengths from seqused_k or cu_seqlens_k
             REQUIRE(seqused_k || cu_seqlens_k, "paged varlen needs seqused_k or cu_seqlens_k");
-        } else {
-            p.cu_seqlens_k = (const int*)cu_seqlens_k;
         }
-        p.seqused_k = (const int*)seqused_k;
-        p.b = batch_size; p.h = h; p.hk = hk; p.group = h / hk; p.d = d;
-        p.seqlen_q = max_seqlen_q; p.seqlen_k = max_seqlen_k;
-        p.alibi_causal = set_windows(window_size_left, window_size_right, max_seqlen_k);
-        p.wl = window_size_left; p.wr = window_size_right;
-        set_scales(p, softmax_scale, softcap);
-        p.alibi = (const float*)alibi_slopes; p.alibi_bstride = alibi_batch_stride;
-        // unpadded LSE [num_heads, total_q] (export.cpp:827): index = h*total_q + q_off + pos
-        p.lse_batch = 0;
-        p.lse_head = total_q;
         REQUIRE(!softmax_lse || total_q > 0, "total_q must be given to address the LSE");
         REQUIRE(!s_dmask || (p_dropout > 0.f && softmax_lse && !block_table),
                 "s_dmask needs p_dropout > 0, softmax_lse and a non-paged K/V");
         REQUIRE(p_dropout == 0.f || !block_table, "dropout over a paged K/V cache is not supported");
+        FwdParams p{};
+        fwd_common(p, q, k, v, o, softmax_lse, batch_size, num_heads, num_heads_k, head_size,
+                   max_seqlen_q, max_seqlen_k, window_size_left, window_size_right, softmax_scale,
+                   softcap, alibi_slopes, alibi_batch_stride);
+        packed_strides(p, num_heads, num_heads_k, head_size, total_q);
+        if (block_table) paged_kv(p, block_table, block_table_stride, page_block_size, num_heads_k, head_size);
+        p.cu_seqlens_q = (const int*)cu_seqlens_q;
+        p.cu_seqlens_k = (const int*)cu_seqlens_k;
+        p.seqused_k = (const int*)seqused_k;
         if (!set_dropout(p, p_dropout, softcap)) return;
         run_fwd(p, !is_fp16, stream, 1);
         if (s_dmask && g_status == 0) run_sdmask(p, s_dmask, !is_fp16, stream);
@@ -762,22 +729,13 @@ void fmha_page_kvcache_fwd_ex(void* q, void* kcache, void* vcache, void* o, void
         if (!slab_ok("q/o", seqlen_q, (int64_t)num_heads * head_size, 2) ||
             !slab_ok("kcache/vcache page", page_block_size, (int64_t)num_heads_k * head_size, kv_dtype == 1 ? 1 : 2)) return;
         FwdParams p{};
-        const int h = num_heads, hk = num_heads_k, d = head_size;
-        p.q = q; p.k = kcache; p.v = vcache; p.o = o; p.lse = (float*)softmax_lse;
-        dense_strides(p, seqlen_q, max_seqlen_k, h, hk, d);
-        p.k_batch = (int64_t)page_block_size * hk * d;   // page stride (paged_attn.cpp:506-507)
-        p.v_batch = (int64_t)page_block_size * hk * d;
-        p.block_table = (const int*)block_table;
-        p.bt_stride = block_table_stride;
-        p.page_size = page_block_size;
+        fwd_common(p, q, kcache, vcache, o, softmax_lse, batch_size, num_heads, num_heads_k, head_size,
+                   seqlen_q, max_seqlen_k, window_size_left, window_size_right, softmax_scale, softcap,
+                   alibi_slopes, alibi_batch_stride);
+        dense_strides(p, seqlen_q, max_seqlen_k, num_heads, num_heads_k, head_size);
+        paged_kv(p, block_table, block_table_stride, page_block_size, num_heads_k, head_size);
         p.seqused_k = (const int*)cache_seqlens;         // non-cumulative (paged_attn.cpp:518-519)
         p.leftpad_k = (const int*)cache_leftpad;
-        p.b = batch_size; p.h = h; p.hk = hk; p.group = h / hk; p.d = d;
-        p.seqlen_q = seqlen_q; p.seqlen_k = max_seqlen_k;
-        p.alibi_causal = set_windows(window_size_left, window_size_right, max_seqlen_k);
-        p.wl = window_size_left; p.wr = window_size_right;
-        set_scales(p, softmax_scale, softcap);
-        p.alibi = (const float*)alibi_slopes; p.alibi_bstride = alibi_batch_stride;
         p.kv_fp8 = kv_dtype == 1; p.k_scale = k_scale; p.v_scale = v_scale;
         run_fwd(p, !is_fp16, stream, num_splits);
     } catch (...) {
@@ -921,20 +879,73 @@ static bool bwd_rows_ok(int64_t tokens, int h, int d) {
     return fail(1, "backward: %lld (token, head) rows exceed the 32-bit thread index", (long long)(tokens * h));
 }
 
-static bool bwd_common(BwdParams& p, float softmax_scale, float softcap, int wl, int wr,
-                       int seqlen_k_norm) {
-    p.alibi_causal = set_windows(wl, wr, seqlen_k_norm);
+// What both backward entries check alike, after check_common and before their own lengths
+static bool bwd_check(const void* dout, const void* lse, const void* dq, const void* dk,
+                      const void* dv, float softcap, float p_dropout) {
+    if (!(dout && lse && dq && dk && dv)) return fail(1, "dout/softmax_lse/dq/dk/dv must be non-null");
+    if (softcap > 0.f && p_dropout > 0.f) return fail(1, "Softcapping does not support dropout for now");
+    return true;
+}
+
+// The backward of both entries.  `tokens`: the query rows of the whole batch; `packed`: rows of
+// all sequences back to back (no batch strides, LSE and accumulator [h, tokens], cu_seqlens
+// give the offsets) instead of dense [b, seqlen, ..]; seqlen_q / seqlen_k: the (maximum)
+// sequence lengths.
+struct BwdTensors { void *dout, *q, *k, *v, *out, *lse, *dq, *dk, *dv, *alibi, *softmax_d; };
+static void bwd_run(const BwdTensors& t, int64_t tokens, bool packed, const void* cu_seqlens_q,
+                    const void* cu_seqlens_k, int alibi_bstride, int seqlen_q, int seqlen_k, int b,
+                    int h, int hk, int d, float p_dropout, float softmax_scale, int wl, int wr,
+                    float softcap, bool deterministic, bool is_fp16, hipStream_t stream,
+                    void* workspace, size_t workspace_bytes, const char* what) {
+    if (!slab_ok("q/out/dout/dq", seqlen_q, (int64_t)h * d, 2) ||
+        !slab_ok("k/v/dk/dv", seqlen_k, (int64_t)hk * d, 2) ||
+        !slab_ok("dq_accum", seqlen_q, hd_bucket(d), 4) ||
+        !bwd_rows_ok(tokens, h, d)) return;
+    int slices = bwd_slices(tokens, b, h, hk, d, seqlen_k, deterministic);
+    char* ws = (char*)workspace;
+    if (ws) {
+        const int fit = bwd_slices_fit(tokens, h, d, workspace_bytes);
+        REQUIRE(fit >= 1, "workspace too small (%zu < %zu bytes)", workspace_bytes, bwd_ws_bytes(tokens, h, d, 1));
+        slices = std::min(slices, fit);
+    }
+    const size_t need = bwd_ws_bytes(tokens, h, d, slices);
+    if (!ws) ws = (char*)pool_get(stream, need);
+    REQUIRE(ws, "could not allocate %zu bytes of backward scratch", need);
+    const int hd = hd_bucket(d);
+    const int64_t rows = packed ? tokens : seqlen_q;      // rows under one head of the LSE / accumulator
+    BwdParams p{};
+    p.q = t.q; p.k = t.k; p.v = t.v; p.o = t.out; p.dout = t.dout; p.lse = (const float*)t.lse;
+    p.dq = t.dq; p.dk = t.dk; p.dv = t.dv;
+    p.dq_accum = (float*)ws;
+    const size_t acc = bwd_acc_bytes(tokens, h, d);
+    p.dsum = t.softmax_d ? (float*)t.softmax_d : (float*)(ws + slices * acc);
+    p.lse_fix = (float*)(ws + slices * acc + bwd_dsum_bytes(tokens, h));
+    p.dq_slices = deterministic ? slices : 0;   // slices a workgroup walks into
+    p.acc_slice = (int64_t)(acc / sizeof(float));
+    p.q_row = p.o_row = p.do_row = p.dq_row = (int64_t)h * d;
+    p.k_row = p.v_row = p.dk_row = p.dv_row = (int64_t)hk * d;
+    p.q_head = p.o_head = p.do_head = p.dq_head = p.k_head = p.v_head = p.dk_head = p.dv_head = d;
+    p.q_batch = p.o_batch = p.do_batch = p.dq_batch = packed ? 0 : (int64_t)seqlen_q * h * d;
+    p.k_batch = p.v_batch = p.dk_batch = p.dv_batch = packed ? 0 : (int64_t)seqlen_k * hk * d;
+    p.lse_head = rows; p.lse_batch = packed ? 0 : (int64_t)h * rows;
+    p.acc_row = hd; p.acc_head = rows * hd; p.acc_batch = packed ? 0 : (int64_t)h * rows * hd;
+    p.cu_seqlens_q = (const int*)cu_seqlens_q;
+    p.cu_seqlens_k = (const int*)cu_seqlens_k;
+    p.alibi = (const float*)t.alibi;
+    p.alibi_bstride = alibi_bstride;
+    p.b = b; p.h = h; p.hk = hk; p.group = h / hk; p.d = d;
+    p.seqlen_q = seqlen_q; p.seqlen_k = seqlen_k;
+    p.alibi_causal = set_windows(wl, wr, seqlen_k);
     p.wl = wl; p.wr = wr;
-    float scale_softmax = softmax_scale;
+    set_scales(p, softmax_scale, softcap);
     p.softcap_on = softcap > 0.f;
-    if (p.softcap_on) { p.softcap_pre = softmax_scale / softcap; scale_softmax = softcap; }
     p.scale = softmax_scale;
-    p.scale_log2 = scale_softmax * 1.4426950408889634f;
-    p.alibi_mul = 1.f / scale_softmax;
     p.device = current_device();
     p.order = options().bwd_order.load();
     p.desc = options().bwd_desc.load();
-    return true;
+    if (!set_dropout(p, p_dropout, softcap)) return;
+    if (!bwd_lse_convention(p, stream)) return;
+    hip_ok(dispatch_bwd(p, !is_fp16, stream), what);
 }
 
 void fmha_bwd(void* dout, void* q, void* k, void* v, void* out, void* softmax_lse, void* dq,
@@ -946,55 +957,14 @@ void fmha_bwd(void* dout, void* q, void* k, void* v, void* out, void* softmax_ls
     try {
         clear_error();
         DevRngScope rng_scope;
-        if (!check_common(q, k, v, out, batch_size, num_heads, num_heads_k, head_size)) return;
-        REQUIRE(head_size <= 256, "the backward supports head dimension at most 256 (got %d)", head_size);
-        REQUIRE(dout && softmax_lse && dq && dk && dv, "dout/softmax_lse/dq/dk/dv must be non-null");
-        REQUIRE(!(softcap > 0.f && p_dropout > 0.f), "Softcapping does not support dropout for now");
+        if (!check_common(q, k, v, out, batch_size, num_heads, num_heads_k, head_size) ||
+            !bwd_check(dout, softmax_lse, dq, dk, dv, softcap, p_dropout)) return;
         REQUIRE(seqlen_q > 0 && seqlen_k > 0, "seqlen_q/seqlen_k must be positive");
-        const int h = num_heads, hk = num_heads_k, d = head_size;
-        if (!slab_ok("q/out/dout/dq", seqlen_q, (int64_t)h * d, 2) ||
-            !slab_ok("k/v/dk/dv", seqlen_k, (int64_t)hk * d, 2) ||
-            !slab_ok("dq_accum", seqlen_q, hd_bucket(d), 4) ||
-            !bwd_rows_ok((int64_t)batch_size * seqlen_q, h, d)) return;
-        const int64_t tok = (int64_t)batch_size * seqlen_q;
-        int slices = bwd_slices(tok, batch_size, h, hk, d, seqlen_k, deterministic);
-        char* ws = (char*)workspace;
-        if (ws) {
-            const int fit = bwd_slices_fit(tok, h, d, workspace_bytes);
-            REQUIRE(fit >= 1, "workspace too small (%zu < %zu bytes)", workspace_bytes, bwd_ws_bytes(tok, h, d, 1));
-            slices = std::min(slices, fit);
-        }
-        const size_t need = bwd_ws_bytes(tok, h, d, slices);
-        if (!ws) ws = (char*)pool_get(stream, need);
-        REQUIRE(ws, "could not allocate %zu bytes of backward scratch", need);
-        const int hd = hd_bucket(d);
-        BwdParams p{};
-        p.q = q; p.k = k; p.v = v; p.o = out; p.dout = dout; p.lse = (const float*)softmax_lse;
-        p.dq = dq; p.dk = dk; p.dv = dv;
-        p.dq_accum = (float*)ws;
-        const size_t acc = bwd_acc_bytes((int64_t)batch_size * seqlen_q, h, d);
-        p.dsum = softmax_d ? (float*)softmax_d : (float*)(ws + slices * acc);
-        p.lse_fix = (float*)(ws + slices * acc + bwd_dsum_bytes((int64_t)batch_size * seqlen_q, h));
-        p.dq_slices = deterministic ? slices : 0;   // slices a workgroup walks into
-        p.acc_slice = (int64_t)(acc / sizeof(float));
-        p.q_row = (int64_t)h * d; p.q_head = d; p.q_batch = (int64_t)seqlen_q * h * d;
-        p.o_row = p.q_row; p.o_head = d; p.o_batch = p.q_batch;
-        p.do_row = p.q_row; p.do_head = d; p.do_batch = p.q_batch;
-        p.dq_row = p.q_row; p.dq_head = d; p.dq_batch = p.q_batch;
-        p.k_row = (int64_t)hk * d; p.k_head = d; p.k_batch = (int64_t)seqlen_k * hk * d;
-        p.v_row = p.k_row; p.v_head = d; p.v_batch = p.k_batch;
-        p.dk_row = p.k_row; p.dk_head = d; p.dk_batch = p.k_batch;
-        p.dv_row = p.k_row; p.dv_head = d; p.dv_batch = p.k_batch;
-        p.lse_batch = (int64_t)h * seqlen_q; p.lse_head = seqlen_q;
-        p.acc_row = hd; p.acc_head = (int64_t)seqlen_q * hd; p.acc_batch = (int64_t)h * seqlen_q * hd;
-        p.alibi = (const float*)alibi_slopes;
-        p.alibi_bstride = batch_size > 1 ? num_heads : 0;
-        p.b = batch_size; p.h = h; p.hk = hk; p.group = h / hk; p.d = d;
-        p.seqlen_q = seqlen_q; p.seqlen_k = seqlen_k;
-        bwd_common(p, softmax_scale, softcap, window_size_left, window_size_right, seqlen_k);
-        if (!set_dropout(p, p_dropout, softcap)) return;
-        if (!bwd_lse_convention(p, stream)) return;
-        hip_ok(dispatch_bwd(p, !is_fp16, stream), "backward launch");
+        bwd_run({dout, q, k, v, out, softmax_lse, dq, dk, dv, alibi_slopes, softmax_d},
+                (int64_t)batch_size * seqlen_q, false, nullptr, nullptr, batch_size > 1 ? num_heads : 0,
+                seqlen_q, seqlen_k, batch_size, num_heads, num_heads_k, head_size, p_dropout,
+                softmax_scale, window_size_left, window_size_right, softcap, deterministic, is_fp16,
+                stream, workspace, workspace_bytes, "backward launch");
     } catch (...) {
         fail(9, "internal error in fmha_bwd");
     }
@@ -1012,58 +982,16 @@ void fmha_varlen_bwd(void* dout, void* q, void* k, void* v, void* out, void* sof
     try {
         clear_error();
         DevRngScope rng_scope;
-        if (!check_common(q, k, v, out, batch_size, num_heads, num_heads_k, head_size)) return;
-        REQUIRE(head_size <= 256, "the backward supports head dimension at most 256 (got %d)", head_size);
-        REQUIRE(dout && softmax_lse && dq && dk && dv, "dout/softmax_lse/dq/dk/dv must be non-null");
-        REQUIRE(!(softcap > 0.f && p_dropout > 0.f), "Softcapping does not support dropout for now");
+        if (!check_common(q, k, v, out, batch_size, num_heads, num_heads_k, head_size) ||
+            !bwd_check(dout, softmax_lse, dq, dk, dv, softcap, p_dropout)) return;
         REQUIRE(cu_seqlens_q && cu_seqlens_k, "cu_seqlens_q/cu_seqlens_k must be non-null");
         REQUIRE(total_q > 0 && total_k > 0 && max_seqlen_q > 0 && max_seqlen_k > 0,
                 "total/max sequence lengths must be positive");
-        const int h = num_heads, hk = num_heads_k, d = head_size;
-        if (!slab_ok("q/out/dout/dq", max_seqlen_q, (int64_t)h * d, 2) ||
-            !slab_ok("k/v/dk/dv", max_seqlen_k, (int64_t)hk * d, 2) ||
-            !slab_ok("dq_accum", max_seqlen_q, hd_bucket(d), 4) ||
-            !bwd_rows_ok(total_q, h, d)) return;
-        int slices = bwd_slices(total_q, batch_size, h, hk, d, max_seqlen_k, deterministic);
-        char* ws = (char*)workspace;
-        if (ws) {
-            const int fit = bwd_slices_fit(total_q, h, d, workspace_bytes);
-            REQUIRE(fit >= 1, "workspace too small (%zu < %zu bytes)", workspace_bytes, bwd_ws_bytes(total_q, h, d, 1));
-            slices = std::min(slices, fit);
-        }
-        const size_t need = bwd_ws_bytes(total_q, h, d, slices);
-        if (!ws) ws = (char*)pool_get(stream, need);
-        REQUIRE(ws, "could not allocate %zu bytes of backward scratch", need);
-        const int hd = hd_bucket(d);
-        BwdParams p{};
-        p.q = q; p.k = k; p.v = v; p.o = out; p.dout = dout; p.lse = (const float*)softmax_lse;
-        p.dq = dq; p.dk = dk; p.dv = dv;
-        p.dq_accum = (float*)ws;
-        const size_t acc = bwd_acc_bytes(total_q, h, d);
-        p.dsum = softmax_d ? (float*)softmax_d : (float*)(ws + slices * acc);
-        p.lse_fix = (float*)(ws + slices * acc + bwd_dsum_bytes(total_q, h));
-        p.dq_slices = deterministic ? slices : 0;   // slices a workgroup walks into
-        p.acc_slice = (int64_t)(acc / sizeof(float));
-        p.q_row = (int64_t)h * d; p.q_head = d; p.q_batch = 0;
-        p.o_row = p.q_row; p.o_head = d; p.o_batch = 0;
-        p.do_row = p.q_row; p.do_head = d; p.do_batch = 0;
-        p.dq_row = p.q_row; p.dq_head = d; p.dq_batch = 0;
-        p.k_row = (int64_t)hk * d; p.k_head = d; p.k_batch = 0;
-        p.v_row = p.k_row; p.v_head = d; p.v_batch = 0;
-        p.dk_row = p.k_row; p.dk_head = d; p.dk_batch = 0;
-        p.dv_row = p.k_row; p.dv_head = d; p.dv_batch = 0;
-        p.lse_batch = 0; p.lse_head = total_q;                 // LSE [h, total_q]
-        p.acc_row = hd; p.acc_head = (int64_t)total_q * hd; p.acc_batch = 0;
-        p.cu_seqlens_q = (const int*)cu_seqlens_q;
-        p.cu_seqlens_k = (const int*)cu_seqlens_k;
-        p.alibi = (const float*)alibi_slopes;
-        p.alibi_bstride = alibi_batch_stride;
-        p.b = batch_size; p.h = h; p.hk = hk; p.group = h / hk; p.d = d;
-        p.seqlen_q = max_seqlen_q; p.seqlen_k = max_seqlen_k;
-        bwd_common(p, softmax_scale, softcap, window_size_left, window_size_right, max_seqlen_k);
-        if (!set_dropout(p, p_dropout, softcap)) return;
-        if (!bwd_lse_convention(p, stream)) return;
-        hip_ok(dispatch_bwd(p, !is_fp16, stream), "varlen backward launch");
+        bwd_run({dout, q, k, v, out, softmax_lse, dq, dk, dv, alibi_slopes, softmax_d}, total_q, true,
+                cu_seqlens_q, cu_seqlens_k, alibi_batch_stride, max_seqlen_q, max_seqlen_k, batch_size,
+                num_heads, num_heads_k, head_size, p_dropout, softmax_scale, window_size_left,
+                window_size_right, softcap, deterministic, is_fp16, stream, workspace, workspace_bytes,
+                "varlen backward launch");
     } catch (...) {
         fail(9, "internal error in fmha_varlen_bwd");
     }

@@ -100,35 +100,14 @@ static hipError_t launch_fwd_nw(const FwdParams& p, hipStream_t st) {
     const bool mask = p.wl >= 0 || p.wr >= 0;
     // FEAT: per-score transforms (ALiBi, softcap) and the paged / fp8 staging paths
     const bool feat = p.alibi || p.softcap_pre > 0.f || p.block_table || p.kv_fp8 || p.drop;
-    const int rows = p.seqlen_q * p.group;
-    const int n_mb = (rows + NW * 32 - 1) / (NW * 32);
-    dim3 grid(p.b * p.hk, n_mb, p.num_splits > 1 ? p.num_splits : 1);
-    FwdParams pp = p;
-    pp.n_mblocks = n_mb;
-    pp.persistent = 0;
-    if (p.persist_per_cu > 0) {
-        const int items = p.b * p.hk * n_mb;
-        const int slots = p.num_cus * p.persist_per_cu;
-        if (items > slots) {
-            pp.persistent = p.work_ctr ? 3 : (p.order == 1 && slots % 8 == 0) ? 2 : 1;
-            pp.xcd_queues = p.work_ctr && p.xcdq && slots % 8 == 0 && p.b * p.hk >= 8;
-            grid = dim3(slots, 1, grid.z);
-        }
-    }
+    const FwdPlan s = plan_fwd(p, NW * 32, p.num_cus * p.persist_per_cu, p.num_splits, kQueueXcd);
     const size_t smem = (size_t)(fwd_nbuf(HD) * 2 * kBlockN * HD * 2);
     void (*kern)(const FwdParams) =
         mask ? (feat ? fmha_fwd_kernel<HD, T, NW, true, true> : fmha_fwd_kernel<HD, T, NW, true, false>)
              : (feat ? fmha_fwd_kernel<HD, T, NW, false, true> : fmha_fwd_kernel<HD, T, NW, false, false>);
-    static std::atomic<unsigned long long> attr_done{0};
-    once_per_device(attr_done, p.device, [&] {
-        (void)hipFuncSetAttribute((const void*)fmha_fwd_kernel<HD, T, NW, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        (void)hipFuncSetAttribute((const void*)fmha_fwd_kernel<HD, T, NW, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        (void)hipFuncSetAttribute((const void*)fmha_fwd_kernel<HD, T, NW, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        (void)hipFuncSetAttribute((const void*)fmha_fwd_kernel<HD, T, NW, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    });
-    note_launch(NW == 8 ? "fmha_fwd_kernel<8 waves>" : "fmha_fwd_kernel<4 waves>", pp.persistent, pp.xcd_queues, grid.x, grid.y, grid.z, NW * 64);
-    hipLaunchKernelGGL(kern, grid, dim3(NW * 64), smem, st, pp);
-    hipError_t e = hipGetLastError();
+    allow_lds<fmha_fwd_kernel<HD, T, NW, true, true>, fmha_fwd_kernel<HD, T, NW, true, false>,
+              fmha_fwd_kernel<HD, T, NW, false, true>, fmha_fwd_kernel<HD, T, NW, false, false>>(p.device, (int)smem);
+    hipError_t e = launch_planned(NW == 8 ? "fmha_fwd_kernel<8 waves>" : "fmha_fwd_kernel<4 waves>", kern, s, NW * 64, smem, st);
     if (e != hipSuccess || p.num_splits <= 1) return e;
     return launch_combine(p, HD, st, fmha_combine_kernel<HD, T>,
                           (HD == 64 || HD == 128 || HD == 256) ? fmha_combine_row_kernel<HD, T> : nullptr);
@@ -155,36 +134,17 @@ static bool fwd4_eligible(const FwdParams& p) {
 
 // 8-wave ping-pong forward (fmha_fwdpp_kernel.h): the same items, schedules and eligibility
 static hipError_t launch_fwdpp(const FwdParams& p, hipStream_t st) {
-    const int n_mb = (p.seqlen_q * p.group + kFwdppRows - 1) / kFwdppRows;
-    FwdParams pp = p;
-    pp.n_mblocks = n_mb;
-    pp.persistent = 0;
-    dim3 grid(p.b * p.hk, n_mb, 1);
-    const int items = p.b * p.hk * n_mb;
-    const int slots = p.num_cus;
-    if (p.persist_per_cu > 0 && items > slots) {
-        pp.persistent = p.work_ctr ? 3 : (p.order == 1 && slots % 8 == 0) ? 2 : 1;
-        pp.xcd_queues = p.work_ctr && p.xcdq && slots % 8 == 0 && p.b * p.hk >= 8;
-        grid = dim3(slots, 1, 1);
-    }
+    const FwdPlan s = plan_fwd(p, kFwdppRows, p.num_cus, 1, kQueueXcd);
     constexpr bool BF = std::is_same<elem_t, __bf16>::value;
     // fwd_w4 = 3: the body on the 16x16x32 MFMA shape (tools/gen_fwdpp16.py); 4 (auto, the
     // default): 16x16x32 where no row has a right window (causal / local rows: 32x32x16), the
     // faster of the two per mask on the same box
     const bool m16 = !p.block_table &&
                      (p.fwd4 == 3 || (p.fwd4 == 4 && p.wr < 0 && !p.alibi && !(p.softcap_pre > 0.f)));
-    static std::atomic<unsigned long long> attr_done{0};
-    once_per_device(attr_done, p.device, [&] {
-        (void)hipFuncSetAttribute((const void*)fmha_fwdpp_kernel<BF, false>, hipFuncAttributeMaxDynamicSharedMemorySize, kFwdppSmem);
-        (void)hipFuncSetAttribute((const void*)fmha_fwdpp_kernel<BF, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kFwdppSmem);
-        (void)hipFuncSetAttribute((const void*)fmha_fwdpp_kernel<BF, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kFwdppSmem);
-    });
-    note_launch(m16 ? "fmha_fwdpp16_kernel" : p.block_table ? "fmha_fwdpp_paged_kernel" : "fmha_fwdpp_kernel",
-                pp.persistent, pp.xcd_queues, grid.x, grid.y, grid.z, 512);
-    if (m16) hipLaunchKernelGGL((fmha_fwdpp_kernel<BF, true>), grid, dim3(512), kFwdppSmem, st, pp);
-    else if (p.block_table) hipLaunchKernelGGL((fmha_fwdpp_kernel<BF, false, true>), grid, dim3(512), kFwdppSmem, st, pp);
-    else hipLaunchKernelGGL((fmha_fwdpp_kernel<BF, false>), grid, dim3(512), kFwdppSmem, st, pp);
-    return hipGetLastError();
+    allow_lds<fmha_fwdpp_kernel<BF, false>, fmha_fwdpp_kernel<BF, true>, fmha_fwdpp_kernel<BF, false, true>>(p.device, kFwdppSmem);
+    if (m16) return launch_planned("fmha_fwdpp16_kernel", fmha_fwdpp_kernel<BF, true>, s, 512, kFwdppSmem, st);
+    if (p.block_table) return launch_planned("fmha_fwdpp_paged_kernel", fmha_fwdpp_kernel<BF, false, true>, s, 512, kFwdppSmem, st);
+    return launch_planned("fmha_fwdpp_kernel", fmha_fwdpp_kernel<BF, false>, s, 512, kFwdppSmem, st);
 }
 
 static hipError_t launch_fwd4(const FwdParams& p, hipStream_t st) {
@@ -192,24 +152,10 @@ static hipError_t launch_fwd4(const FwdParams& p, hipStream_t st) {
 #if !XFA_VARIANTS
     return hipErrorNotSupported;   // (fmha_set_option refuses fwd_w4 = 1 in this build)
 #else
-    const int n_mb = (p.seqlen_q * p.group + kFwd4Rows - 1) / kFwd4Rows;
-    FwdParams pp = p;
-    pp.n_mblocks = n_mb;
-    pp.persistent = 0;
-    dim3 grid(p.b * p.hk, n_mb, 1);
-    const int items = p.b * p.hk * n_mb;
-    const int slots = p.num_cus;
-    if (p.persist_per_cu > 0 && items > slots) {
-        pp.persistent = p.work_ctr ? 3 : (p.order == 1 && slots % 8 == 0) ? 2 : 1;
-        pp.xcd_queues = p.work_ctr && p.xcdq && slots % 8 == 0 && p.b * p.hk >= 8;
-        grid = dim3(slots, 1, 1);
-    }
     constexpr bool BF = std::is_same<elem_t, __bf16>::value;
-    static std::atomic<unsigned long long> attr_done{0};
-    once_per_device(attr_done, p.device, [&] { (void)hipFuncSetAttribute((const void*)fmha_fwd4_kernel<BF>, hipFuncAttributeMaxDynamicSharedMemorySize, kFwd4Smem); });
-    note_launch("fmha_fwd4_kernel", pp.persistent, pp.xcd_queues, grid.x, grid.y, grid.z, 256);
-    hipLaunchKernelGGL((fmha_fwd4_kernel<BF>), grid, dim3(256), kFwd4Smem, st, pp);
-    return hipGetLastError();
+    allow_lds<fmha_fwd4_kernel<BF>>(p.device, kFwd4Smem);
+    return launch_planned("fmha_fwd4_kernel", fmha_fwd4_kernel<BF>, plan_fwd(p, kFwd4Rows, p.num_cus, 1, kQueueXcd),
+                          256, kFwd4Smem, st);
 #endif
 }
 #endif

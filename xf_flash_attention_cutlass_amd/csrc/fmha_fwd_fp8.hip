@@ -16,82 +16,36 @@ namespace xfa {
 // runs the one without, whose code the packed path does not touch)
 template <bool F16, bool VARLEN>
 static hipError_t launch_fp8_w4(const FwdParams& p, hipStream_t st) {
-    const int n_mb = (p.seqlen_q * p.group + kFwd8wRows - 1) / kFwd8wRows;
-    FwdParams pp = p;
-    pp.n_mblocks = n_mb;
-    pp.persistent = 0;
-    dim3 grid(p.b * p.hk, n_mb, 1);
-    const int items = p.b * p.hk * n_mb;
-    if (p.persist_per_cu > 0 && items > p.num_cus) {
-        pp.persistent = p.work_ctr ? 3 : (p.order == 1 && p.num_cus % 8 == 0) ? 2 : 1;
-        pp.xcd_queues = p.work_ctr && p.xcdq && p.num_cus % 8 == 0 && p.b * p.hk >= 8;
-        grid = dim3(p.num_cus, 1, 1);
-    }
-    static std::atomic<unsigned long long> attr_done{0};
-    once_per_device(attr_done, p.device, [&] { (void)hipFuncSetAttribute((const void*)fmha_fwd8w_kernel<F16, VARLEN>, hipFuncAttributeMaxDynamicSharedMemorySize, kFwd8wSmem); });
-    note_launch("fmha_fwd8w_kernel", pp.persistent, pp.xcd_queues, grid.x, grid.y, grid.z, 256);
-    hipLaunchKernelGGL((fmha_fwd8w_kernel<F16, VARLEN>), grid, dim3(256), kFwd8wSmem, st, pp);
-    return hipGetLastError();
+    allow_lds<fmha_fwd8w_kernel<F16, VARLEN>>(p.device, kFwd8wSmem);
+    return launch_planned("fmha_fwd8w_kernel", fmha_fwd8w_kernel<F16, VARLEN>,
+                          plan_fwd(p, kFwd8wRows, p.num_cus, 1, kQueueXcd), 256, kFwd8wSmem, st);
 }
 
 #if XFA_VARIANTS
 // 8-wave ping-pong fp8 forward (fmha_fwd8pp_kernel.h): the same items, schedules, eligibility
 template <bool F16>
 static hipError_t launch_fp8_pp(const FwdParams& p, hipStream_t st) {
-    const int n_mb = (p.seqlen_q * p.group + kFwd8ppRows - 1) / kFwd8ppRows;
-    FwdParams pp = p;
-    pp.n_mblocks = n_mb;
-    pp.persistent = 0;
-    dim3 grid(p.b * p.hk, n_mb, 1);
-    const int items = p.b * p.hk * n_mb;
-    if (p.persist_per_cu > 0 && items > p.num_cus) {
-        pp.persistent = p.work_ctr ? 3 : (p.order == 1 && p.num_cus % 8 == 0) ? 2 : 1;
-        pp.xcd_queues = p.work_ctr && p.xcdq && p.num_cus % 8 == 0 && p.b * p.hk >= 8;
-        grid = dim3(p.num_cus, 1, 1);
-    }
-    static std::atomic<unsigned long long> attr_done{0};
-    once_per_device(attr_done, p.device, [&] { (void)hipFuncSetAttribute((const void*)fmha_fwd8pp_kernel<F16>, hipFuncAttributeMaxDynamicSharedMemorySize, kFwd8ppSmem); });
-    note_launch("fmha_fwd8pp_kernel", pp.persistent, pp.xcd_queues, grid.x, grid.y, grid.z, 512);
-    hipLaunchKernelGGL((fmha_fwd8pp_kernel<F16>), grid, dim3(512), kFwd8ppSmem, st, pp);
-    return hipGetLastError();
+    allow_lds<fmha_fwd8pp_kernel<F16>>(p.device, kFwd8ppSmem);
+    return launch_planned("fmha_fwd8pp_kernel", fmha_fwd8pp_kernel<F16>,
+                          plan_fwd(p, kFwd8ppRows, p.num_cus, 1, kQueueXcd), 512, kFwd8ppSmem, st);
 }
 #endif
 
+// 8-wave fp8 forward.  Its schedules differ from the other launchers': a dense launch never
+// takes the dynamic queue (static schedules only, whatever fwd_dyn says), and a packed one with
+// the item counter follows the ragged rule (plan_fwd, kQueueRagged: more items than CUs =>
+// mode 3 on min(items, slots) workgroups, never per-XCD queues).
 template <typename T, bool VARLEN>
 static hipError_t launch_fp8_t(const FwdParams& p, hipStream_t st) {
     constexpr int NW = 8;
     const bool mask = p.wl >= 0 || p.wr >= 0;
-    const int rows = p.seqlen_q * p.group;
-    const int n_mb = (rows + NW * 32 - 1) / (NW * 32);
-    dim3 grid(p.b * p.hk, n_mb, 1);
-    FwdParams pp = p;
-    pp.n_mblocks = n_mb;
-    pp.persistent = 0;
-    if (p.persist_per_cu > 0) {
-        const int items = p.b * p.hk * n_mb;
-        const int slots = p.num_cus * p.persist_per_cu;
-        if (VARLEN && p.work_ctr) {
-            // varlen: ragged items from one dynamic queue (as the bf16 varlen launches), once
-            // there are more items than CUs
-            if (items > p.num_cus) {
-                pp.persistent = 3;
-                grid = dim3(std::min(items, slots), 1, 1);
-            }
-        } else if (items > slots) {
-            pp.persistent = (p.order == 1 && slots % 8 == 0) ? 2 : 1;
-            grid = dim3(slots, 1, 1);
-        }
-    }
+    const FwdPlan s = plan_fwd(p, NW * 32, p.num_cus * p.persist_per_cu, 1,
+                               VARLEN && p.work_ctr ? kQueueRagged : kQueueStatic);
     const size_t smem = 8 * (size_t)kFp8Tile;     // K and V, four buffers each
-    void (*kern)(const FwdParams) = mask ? fmha_fwd_fp8_kernel<T, NW, true, VARLEN> : fmha_fwd_fp8_kernel<T, NW, false, VARLEN>;
-    static std::atomic<unsigned long long> attr_done{0};
-    once_per_device(attr_done, p.device, [&] {
-        (void)hipFuncSetAttribute((const void*)fmha_fwd_fp8_kernel<T, NW, true, VARLEN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        (void)hipFuncSetAttribute((const void*)fmha_fwd_fp8_kernel<T, NW, false, VARLEN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    });
-    note_launch("fmha_fwd_fp8_kernel<8 waves>", pp.persistent, 0, grid.x, grid.y, grid.z, NW * 64);
-    hipLaunchKernelGGL(kern, grid, dim3(NW * 64), smem, st, pp);
-    return hipGetLastError();
+    allow_lds<fmha_fwd_fp8_kernel<T, NW, true, VARLEN>, fmha_fwd_fp8_kernel<T, NW, false, VARLEN>>(p.device, (int)smem);
+    return launch_planned("fmha_fwd_fp8_kernel<8 waves>",
+                          mask ? fmha_fwd_fp8_kernel<T, NW, true, VARLEN> : fmha_fwd_fp8_kernel<T, NW, false, VARLEN>,
+                          s, NW * 64, smem, st);
 }
 
 hipError_t launch_fwd_fp8(const FwdParams& p, bool out_fp16, hipStream_t st) {

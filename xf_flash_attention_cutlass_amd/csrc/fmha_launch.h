@@ -18,47 +18,67 @@
 namespace xfa {
 
 // Tuning knobs, settable through fmha_set_option() (schedule choices with equal results; the
-// parity suite runs under any of them via XFA_TEST_OPTIONS).  Atomic: a launch on another
-// thread reads each knob once, as a whole value.
+// parity suite runs under any of them via XFA_TEST_OPTIONS).  The one list of them: Options,
+// fmha_set_option and fmha_get_option all expand it.  X(name, default, lo, hi); two knobs take
+// only the ends of their range (fwd_waves 4 | 8, dec_mr 16 | 32: fmha_set_option).
+#define XFA_KNOBS(X)                                                                              \
+    /* D = 128 forward where eligible: 4 auto (3 where no row has a right window, else 2); 3 the  \
+       ping-pong on the 16x16x32 MFMA (r6: non-causal C2 +1.5-2.8 %, causal -1.3-3.4 % against 2, \
+       same box); 2 the 8-wave ping-pong kernel (fmha_fwdpp_kernel.h; round 5, same box: C2       \
+       causal +2-3 %, C4 +3 %, non-causal equal), 1 the 4-wave kernel (fmha_fwd4_kernel.h, the    \
+       variants build only), 0 neither (8-wave fmha_fwd_kernel) */                                \
+    X(fwd_w4, 4, 0, 4)                                                                            \
+    /* 4-wave fp8 forward (fmha_fwd8w_kernel.h) where eligible (C2 shape, same box: 1610 vs 1576  \
+       TFLOP/s causal, 1852 vs 1799 non-causal); 2 the ping-pong one (the variants build only) */ \
+    X(fp8_w4, 1, 0, 2)                                                                            \
+    /* waves per forward workgroup (4 or 8); 32 query rows per wave */                            \
+    X(fwd_waves, 8, 4, 8)                                                                         \
+    /* static s_setprio 1 for the younger half of the workgroup */                                \
+    X(fwd_prio, 0, 0, 1)                                                                          \
+    /* persistent grid (workgroups per CU; 0 = one workgroup per item) */                         \
+    X(fwd_persistent, 1, 0, 8)                                                                    \
+    /* deferred rescale: running max may lag by this many log2 units */                           \
+    X(fwd_slack, 8, 0, 16)                                                                        \
+    /* persistent item order: 0 boustrophedon, 1 XCD-grouped pairs */                             \
+    X(fwd_order, 1, 0, 1)                                                                         \
+    /* dynamic item queue: 0 never, 1 varlen only, 2 every persistent launch */                   \
+    X(fwd_dyn, 1, 0, 2)                                                                           \
+    /* dynamic queue kind: 1 one unit-major queue per XCD, 0 one global heaviest-row-block-first  \
+       queue */                                                                                   \
+    X(fwd_xcdq, 1, 0, 1)                                                                          \
+    /* software-pipelined loop over the unmasked key tiles */                                     \
+    X(fwd_pipe, 1, 0, 2)                                                                          \
+    /* split-KV decode kernel when seqlen_q * H/Hk <= 32 */                                       \
+    X(fwd_decode, 1, 0, 1)                                                                        \
+    /* decode split target: workgroups per CU over all (b, kv head) */                            \
+    X(dec_wg_per_cu, 2, 1, 16)                                                                    \
+    /* decode MFMA rows: 16 when the query rows fit 16 (C5: 105 vs 110 us with dec_hmaj = 1),     \
+       else 32 */                                                                                 \
+    X(dec_mr, 16, 16, 32)                                                                         \
+    /* split combine: one workgroup per row when rows are few */                                  \
+    X(comb_row, 1, 0, 1)                                                                          \
+    /* decode: the last split of each (b, kv head) merges the partials (no separate combine       \
+       launch; C5: 126.8 vs 105.5 us - the coherent partial stores and the 64-wave merge tail     \
+       cost more than the 5 us combine launch they replace) */                                    \
+    X(dec_fold, 0, 0, 1)                                                                          \
+    /* decode over per-sequence cache lengths (2 <= b <= 64): split slots shared in proportion to \
+       the key tiles (ragged caches) */                                                           \
+    X(dec_bal, 1, 0, 1)                                                                           \
+    /* backward grid: 1 = the key blocks of one (b, kv head) consecutive on one XCD (they then    \
+       sweep the same Q / dO tiles together; C3: 3.03 vs 2.88 ms - their dQ atomics then collide) */ \
+    X(bwd_order, 0, 0, 1)                                                                         \
+    /* backward query-tile sweep: 1 = last tile first (C3 on the round-3 session-2 kernel: 2.496  \
+       vs 2.513 ms, non-causal 4.410 vs 4.423; dK/dV equal up to fp32 summation order) */         \
+    X(bwd_desc, 1, 0, 1)                                                                          \
+    /* decode workgroup: 0 = 1 kv head x 4 splits, 1 = 4 kv heads x one split, 2 = 8 kv heads x   \
+       one split (C5 fp8: 116 / 110 / 112 us) */                                                  \
+    X(dec_hmaj, 1, 0, 2)
+
+// Atomic: a launch on another thread reads each knob once, as a whole value.
 struct Options {
-    std::atomic<int> fwd_w4{4};          // D = 128 forward where eligible: 4 auto (3 where no row
-                                         // has a right window, else 2); 3 the ping-pong on the
-                                         // 16x16x32 MFMA (r6: non-causal C2 +1.5-2.8 %, causal
-                                         // -1.3-3.4 % against 2, same box); 2 the 8-wave ping-pong
-                                         // kernel (fmha_fwdpp_kernel.h; round 5, same box: C2 causal
-                                         // +2-3 %, C4 +3 %, non-causal equal), 1 the 4-wave kernel
-                                         // (fmha_fwd4_kernel.h), 0 neither (8-wave fmha_fwd_kernel)
-    std::atomic<int> fp8_w4{1};          // 4-wave fp8 forward (fmha_fwd8w_kernel.h) where eligible
-                                         // (C2 shape, same box: 1610 vs 1576 TFLOP/s causal, 1852 vs
-                                         // 1799 non-causal)
-    std::atomic<int> fwd_waves{8};       // waves per forward workgroup (4 or 8); 32 query rows per wave
-    std::atomic<int> fwd_prio{0};        // static s_setprio 1 for the younger half of the workgroup
-    std::atomic<int> fwd_persistent{1};  // persistent grid (workgroups per CU; 0 = one workgroup per item)
-    std::atomic<int> fwd_slack{8};       // deferred rescale: running max may lag by this many log2 units
-    std::atomic<int> fwd_order{1};       // persistent item order: 0 boustrophedon, 1 XCD-grouped pairs
-    std::atomic<int> fwd_dyn{1};         // dynamic item queue: 0 never, 1 varlen only, 2 every persistent launch
-    std::atomic<int> fwd_xcdq{1};        // dynamic queue kind: 1 one unit-major queue per XCD, 0 one global
-                                         // heaviest-row-block-first queue
-    std::atomic<int> fwd_pipe{1};        // software-pipelined loop over the unmasked key tiles
-    std::atomic<int> fwd_decode{1};      // split-KV decode kernel when seqlen_q * H/Hk <= 32
-    std::atomic<int> dec_wg_per_cu{2};   // decode split target: workgroups per CU over all (b, kv head)
-    std::atomic<int> dec_mr{16};         // decode MFMA rows: 16 when the query rows fit 16 (C5: 105 vs
-                                         // 110 us with dec_hmaj = 1), else 32
-    std::atomic<int> comb_row{1};        // split combine: one workgroup per row when rows are few
-    std::atomic<int> dec_fold{0};        // decode: the last split of each (b, kv head) merges the partials
-    std::atomic<int> dec_bal{1};         // decode over per-sequence cache lengths (2 <= b <= 64): split
-                                         // slots shared in proportion to the key tiles (ragged caches)
-                                         // (no separate combine launch; C5: 126.8 vs 105.5 us - the
-                                         // coherent partial stores and the 64-wave merge tail cost
-                                         // more than the 5 us combine launch they replace)
-    std::atomic<int> bwd_order{0};       // backward grid: 1 = the key blocks of one (b, kv head) consecutive
-                                         // on one XCD (they then sweep the same Q / dO tiles together;
-                                         // C3: 3.03 vs 2.88 ms - their dQ atomics then collide)
-    std::atomic<int> bwd_desc{1};        // backward query-tile sweep: 1 = last tile first (C3 on the
-                                         // round-3 session-2 kernel: 2.496 vs 2.513 ms, non-causal
-                                         // 4.410 vs 4.423; dK/dV equal up to fp32 summation order)
-    std::atomic<int> dec_hmaj{1};        // decode workgroup: 0 = 1 kv head x 4 splits, 1 = 4 kv heads x one
-                                         // split, 2 = 8 kv heads x one split (C5 fp8: 116 / 110 / 112 us)
+#define XFA_KNOB_FIELD(name, def, lo, hi) std::atomic<int> name{def};
+    XFA_KNOBS(XFA_KNOB_FIELD)
+#undef XFA_KNOB_FIELD
 };
 Options& options();
 
@@ -66,6 +86,56 @@ Options& options();
 // the persistent mode (0 = one workgroup per item, 1 boustrophedon, 2 XCD-grouped pairs,
 // 3 dynamic queue), the per-XCD queues flag and the grid.  Thread-local, set by the launchers.
 void note_launch(const char* kernel, int persistent, int xcdq, unsigned gx, unsigned gy, unsigned gz, int block);
+
+// The schedule of one forward launch, shared by every forward launcher: the params as the
+// kernel gets them (n_mblocks, persistent, xcd_queues filled in) and the grid.  An item is one
+// row block of `rows_per_item` query rows (seqlen_q * group of them) of one (b, kv head);
+// `slots` workgroups stay resident once there are more items than slots (and fwd_persistent
+// > 0), else one workgroup runs one item.
+//   kQueueStatic: boustrophedon (1) or XCD-grouped pairs (2, fwd_order = 1 and slots % 8 == 0);
+//   kQueueXcd:    the same, or with p.work_ctr the dynamic item queue (3), one queue per XCD
+//                 where fwd_xcdq asks and the slots and (b, kv head) units fill 8 XCDs;
+//   kQueueRagged: the 8-wave fp8 kernel's packed launches (it has no per-XCD queues): one
+//                 dynamic queue as soon as there are more items than CUs, walked by
+//                 min(items, slots) workgroups.
+enum FwdQueue { kQueueStatic, kQueueXcd, kQueueRagged };
+struct FwdPlan { FwdParams pp; dim3 grid; };
+inline FwdPlan plan_fwd(const FwdParams& p, int rows_per_item, int slots, int splits, FwdQueue queue) {
+    FwdPlan s{p, dim3()};
+    const int n_mb = (p.seqlen_q * p.group + rows_per_item - 1) / rows_per_item;
+    const int items = p.b * p.hk * n_mb;
+    const unsigned gz = splits > 1 ? splits : 1;
+    s.pp.n_mblocks = n_mb;
+    s.pp.persistent = 0;
+    s.pp.xcd_queues = 0;
+    s.grid = dim3(p.b * p.hk, n_mb, gz);
+    if (p.persist_per_cu <= 0) return s;
+    if (queue == kQueueRagged) {
+        if (items > p.num_cus) { s.pp.persistent = 3; s.grid = dim3(items < slots ? items : slots, 1, gz); }
+    } else if (items > slots) {
+        const bool dyn = queue == kQueueXcd && p.work_ctr;
+        s.pp.persistent = dyn ? 3 : (p.order == 1 && slots % 8 == 0) ? 2 : 1;
+        s.pp.xcd_queues = dyn && p.xcdq && slots % 8 == 0 && p.b * p.hk >= 8;
+        s.grid = dim3(slots, 1, gz);
+    }
+    return s;
+}
+
+// Raises the dynamic-LDS limit of the kernels of one launcher, once per device.
+template <auto... Kernels>
+inline void allow_lds(int device, int bytes) {
+    static std::atomic<unsigned long long> done{0};
+    once_per_device(done, device, [&] {
+        ((void)hipFuncSetAttribute((const void*)Kernels, hipFuncAttributeMaxDynamicSharedMemorySize, bytes), ...);
+    });
+}
+// The tail of every planned launch: the record for fmha_last_kernel(), the launch, its status.
+inline hipError_t launch_planned(const char* name, void (*kern)(const FwdParams), const FwdPlan& s,
+                                 int block, size_t lds, hipStream_t st) {
+    note_launch(name, s.pp.persistent, s.pp.xcd_queues, s.grid.x, s.grid.y, s.grid.z, block);
+    hipLaunchKernelGGL(kern, s.grid, dim3(block), lds, st, s.pp);
+    return hipGetLastError();
+}
 
 // Forward for head dim bucket HD (64 or 128) and dtype; launches the combine when
 // p.num_splits > 1.  Returns the launch status.
