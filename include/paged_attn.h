@@ -191,6 +191,50 @@ void fmha_varlen_fwd_fp8(void* q, void* k, void* v, void* o, void* softmax_lse,
                          float softmax_scale, int window_size_left, int window_size_right,
                          bool out_fp16, hipStream_t stream);
 
+/* fmha_fwd_fp8 / fmha_varlen_fwd_fp8 with the descales read on the device (2.6): the three
+ * floats become device pointers q_descale, k_descale, v_descale (fp32) and two ELEMENT strides
+ * that index each of them by (batch, kv head): the descale of batch b (packed input: sequence
+ * b), kv head g is ptr[b * descale_batch_stride + g * descale_head_stride]; q's applies to the
+ * whole group of query heads of kv head g.  (0, 0) is a one-element per-tensor scale,
+ * (heads_k, 1) FA3's [batch, heads_k] tensors.  No host sync, so a scale computed on the device
+ * (fmha_quantize_fp8) can be used inside a captured graph.  Caller contract: the values cannot be
+ * checked on the host, so "descale > 0" is the caller's to keep - a non-positive or non-finite
+ * descale spoils the output of that (batch, kv head) only, never addressing.  Everything else as
+ * the by-value entries, which give bit-identical results for equal scales. */
+void fmha_fwd_fp8_ex(void* q, void* k, void* v, void* o, void* softmax_lse, const float* q_descale,
+                     const float* k_descale, const float* v_descale, int32_t descale_batch_stride,
+                     int32_t descale_head_stride, int32_t seqlen_q, int32_t seqlen_k,
+                     int32_t batch_size, int32_t num_heads, int32_t num_heads_k, int32_t head_size,
+                     float softmax_scale, int window_size_left, int window_size_right, bool out_fp16,
+                     hipStream_t stream);
+
+void fmha_varlen_fwd_fp8_ex(void* q, void* k, void* v, void* o, void* softmax_lse,
+                            void* cu_seqlens_q, void* cu_seqlens_k, void* seqused_k,
+                            const float* q_descale, const float* k_descale, const float* v_descale,
+                            int32_t descale_batch_stride, int32_t descale_head_stride,
+                            int32_t max_seqlen_q, int32_t max_seqlen_k, int32_t total_q,
+                            int32_t batch_size, int32_t num_heads, int32_t num_heads_k, int32_t head_size,
+                            float softmax_scale, int window_size_left, int window_size_right,
+                            bool out_fp16, hipStream_t stream);
+
+/* bf16 / fp16 -> OCP fp8 e4m3fn with the descales the fp8 entries take (2.6).  x: [batch, seqlen,
+ * heads, head_size] by ELEMENT strides {batch, row, head} (last dimension contiguous, as
+ * fmha_fwd_strided), or with cu_seqlens (int32 [batch + 1]) packed [total, heads, head_size]:
+ * then seqlen is the longest sequence and the batch stride is ignored.  x8: contiguous bytes of
+ * the same logical shape.  granularity 0: one scale, descale[1]; 1: one per (batch or sequence,
+ * group of `group` consecutive heads), descale [batch, num_heads / group] contiguous - group =
+ * heads / heads_k for q (a forward item covers one kv head and all its query heads), 1 for k, v.
+ *   amax = max |float(x)| over the scale's set;  descale = amax / 448.0f (1.0f when amax == 0 or
+ *   the set is empty);  byte = e4m3fn round-to-nearest-even of clamp(float(x) * (1.0f / descale),
+ *   -448, 448).
+ * Two passes over x (an order-independent maximum, then the conversion), no allocation per call
+ * and no host sync: capturable in a graph.  head_size a multiple of 8 and <= 256; x 16-byte and
+ * x8 8-byte aligned; strides multiples of 8. */
+void fmha_quantize_fp8(const void* x, void* x8, float* descale, const void* cu_seqlens,
+                       int32_t batch_size, int32_t seqlen, int32_t num_heads, int32_t group,
+                       int32_t head_size, const int64_t* strides, int32_t granularity, bool is_fp16,
+                       hipStream_t stream);
+
 /* Varlen forward with the fields the reference's varlen C entry drops (paged_attn.cpp:423-433):
  * LSE out (fp32 [num_heads, total_q], unpadded as export.cpp:827; total_q = cu_seqlens_q[batch]
  * must be passed by the caller, it is only used to address the LSE), ALiBi, softcap,
@@ -248,6 +292,21 @@ void fmha_kvcache_append(void* q, void* q_out, void* kcache, void* vcache, const
                          bool q_rotary_per_token, int32_t batch_size, int32_t seqlen_q,
                          int32_t num_heads, int32_t num_heads_k, int32_t head_size,
                          bool is_fp16, hipStream_t stream);
+
+/* fmha_kvcache_append into an fp8 (OCP e4m3fn) cache (2.6): kcache / vcache are bytes
+ * [num_blocks, page, hk, d], knew / vnew / q / q_out stay in q's dtype; k_scale / v_scale are the
+ * cache's descales (positive), as fmha_page_kvcache_fwd_ex takes them with kv_dtype = 1.  K: the
+ * rotary in fp32 as above, x (1 / k_scale), clamped to +-448 and rounded once to e4m3; V:
+ * x (1 / v_scale), clamped, rounded.  Everything else (seqlens_out, dropped rows, q_out) as
+ * fmha_kvcache_append. */
+void fmha_kvcache_append_fp8(void* q, void* q_out, void* kcache, void* vcache, const void* knew,
+                             const void* vnew, int32_t seqlen_new, const void* block_table,
+                             int32_t block_table_stride, int32_t page_block_size,
+                             const void* cache_seqlens, void* seqlens_out, const void* rotary_cos,
+                             const void* rotary_sin, int32_t rotary_dim, bool is_rotary_interleaved,
+                             bool q_rotary_per_token, int32_t batch_size, int32_t seqlen_q,
+                             int32_t num_heads, int32_t num_heads_k, int32_t head_size,
+                             bool is_fp16, hipStream_t stream, float k_scale, float v_scale);
 
 /* Dense backward: the C form of mha_bwd (export.cpp:948-1176, live twin flash_api_hip.cpp:
  * 815-1043), which the reference never built.  Inputs dout/q/k/v/out as the fwd layout,

@@ -43,6 +43,7 @@ from .interface import (  # noqa: E402
     flash_attn_varlen_func,
     flash_attn_varlen_kvpacked_func,
     flash_attn_with_kvcache,
+    quantize_fp8,
 )
 
 __all__ = [
@@ -54,4 +55,5 @@ __all__ = [
     "flash_attn_varlen_fp8_func",
     "flash_attn_varlen_kvpacked_func",
     "flash_attn_with_kvcache",
+    "quantize_fp8",
 ]

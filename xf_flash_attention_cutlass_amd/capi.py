@@ -32,6 +32,12 @@ _SIGS = {
                      C.c_int, C.c_int, b_, vp],
     "fmha_varlen_fwd_fp8": [vp, vp, vp, vp, vp, vp, vp, vp, f32, f32, f32, i32, i32, i32, i32,
                             i32, i32, i32, f32, C.c_int, C.c_int, b_, vp],
+    "fmha_fwd_fp8_ex": [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, f32,
+                        C.c_int, C.c_int, b_, vp],
+    "fmha_varlen_fwd_fp8_ex": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32,
+                               i32, i32, i32, i32, f32, C.c_int, C.c_int, b_, vp],
+    "fmha_quantize_fp8": [vp, vp, vp, vp, i32, i32, i32, i32, i32, C.POINTER(C.c_int64), i32, b_,
+                          vp],
     "fmha_varlen_fwd_ex_v2": [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, i32, i32, i32, i32,
                            i32, i32, i32, i32, f32, C.c_int, C.c_int, f32, b_, vp, f32, vp],
     "fmha_page_kvcache_fwd_ex_v2": [vp, vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32,
@@ -46,6 +52,8 @@ _SIGS = {
     "fmha_varlen_bwd_workspace_size_v2": [i32, i32, i32, i32, i32, i32, b_],
     "fmha_kvcache_append": [vp, vp, vp, vp, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, i32, b_,
                             b_, i32, i32, i32, i32, i32, b_, vp],
+    "fmha_kvcache_append_fp8": [vp, vp, vp, vp, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, i32, b_,
+                                b_, i32, i32, i32, i32, i32, b_, vp, f32, f32],
     "fmha_last_error": [],
     "fmha_last_status": [],
     "fmha_last_num_splits": [],

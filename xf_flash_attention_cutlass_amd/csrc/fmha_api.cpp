@@ -431,9 +431,27 @@ void run_fwd(FwdParams& p, bool bf16, hipStream_t st, int num_splits_req) {
 
 // The fp8 forward's launch (one pass, D = 128): the schedule knobs with fp8_w4 as the kernel
 // choice and none of fwd_waves / fwd_prio / fwd_pipe, which its kernels do not read
-void run_fwd_fp8(FwdParams& p, float q_scale, float k_scale, float v_scale, int dyn_min,
+// The fp8 forward's descales as an entry gives them: by value (the plain entries; the pointers
+// null), or device tensors indexed by (batch, kv head) with element strides (the _ex entries)
+struct Fp8Descales {
+    float q = 1.f, k = 1.f, v = 1.f;
+    const float* q_ptr = nullptr; const float* k_ptr = nullptr; const float* v_ptr = nullptr;
+    int batch_stride = 0, head_stride = 0;
+};
+bool check_descales(const Fp8Descales& ds, bool device) {
+    if (!device) return (ds.q > 0.f && ds.k > 0.f && ds.v > 0.f) || fail(1, "fp8 descales must be positive");
+    if (!ds.q_ptr || !ds.k_ptr || !ds.v_ptr)
+        return fail(1, "q_descale, k_descale and v_descale must be non-null device pointers");
+    if (ds.batch_stride < 0 || ds.head_stride < 0)
+        return fail(1, "descale strides must be non-negative (got %d, %d)", ds.batch_stride, ds.head_stride);
+    return true;
+}
+
+void run_fwd_fp8(FwdParams& p, const Fp8Descales& ds, int dyn_min,
                  bool out_fp16, hipStream_t st, const char* what) {
-    p.q_scale = q_scale; p.k_scale = k_scale; p.v_scale = v_scale;
+    p.q_scale = ds.q; p.k_scale = ds.k; p.v_scale = ds.v;
+    p.q_descale = ds.q_ptr; p.k_descale = ds.k_ptr; p.v_descale = ds.v_ptr;
+    p.ds_batch = ds.batch_stride; p.ds_head = ds.head_stride;
     load_schedule(p, options().fp8_w4);
     p.num_splits = 1;
     if (!take_item_queue(p, st, dyn_min, 1)) return;
@@ -461,7 +479,7 @@ const char* fmha_last_error(void) { return g_err.c_str(); }
 int fmha_last_status(void) { return g_status; }
 int fmha_last_num_splits(void) { return g_last_splits; }
 const char* fmha_last_kernel(void) { return g_last_kernel; }
-const char* fmha_version(void) { return XFA_VARIANTS ? "xf-fmha-gfx950 2.5 (variants)" : "xf-fmha-gfx950 2.5"; }
+const char* fmha_version(void) { return XFA_VARIANTS ? "xf-fmha-gfx950 2.6 (variants)" : "xf-fmha-gfx950 2.6"; }
 
 void fmha_set_rng_state(uint64_t seed, uint64_t offset) {
     g_seed = seed;
@@ -585,17 +603,21 @@ void fmha_fwd_strided(void* q, void* k, void* v, void* o, void* alibi_slopes, vo
     }
 }
 
-void fmha_fwd_fp8(void* q, void* k, void* v, void* o, void* softmax_lse, float q_scale,
-                  float k_scale, float v_scale, int32_t seqlen_q, int32_t seqlen_k,
-                  int32_t batch_size, int32_t num_heads, int32_t num_heads_k, int32_t head_size,
-                  float softmax_scale, int window_size_left, int window_size_right, bool out_fp16,
-                  hipStream_t stream) {
+}  // extern "C"
+
+namespace {
+
+void fwd_fp8_entry(const char* entry, void* q, void* k, void* v, void* o, void* softmax_lse,
+                   const Fp8Descales& ds, bool device_descales, int32_t seqlen_q, int32_t seqlen_k,
+                   int32_t batch_size, int32_t num_heads, int32_t num_heads_k, int32_t head_size,
+                   float softmax_scale, int window_size_left, int window_size_right, bool out_fp16,
+                   hipStream_t stream) {
     try {
         begin_fwd();
         if (!check_common(q, k, v, o, batch_size, num_heads, num_heads_k, head_size)) return;
         REQUIRE(head_size == 128, "the fp8 forward supports head_size 128 (got %d)", head_size);
         REQUIRE(seqlen_q > 0 && seqlen_k > 0, "seqlen_q/seqlen_k must be positive (%d, %d)", seqlen_q, seqlen_k);
-        REQUIRE(q_scale > 0.f && k_scale > 0.f && v_scale > 0.f, "fp8 descales must be positive");
+        if (!check_descales(ds, device_descales)) return;
         if (!slab_ok("q", seqlen_q, (int64_t)num_heads * head_size, 1) ||
             !slab_ok("k/v", seqlen_k, (int64_t)num_heads_k * head_size, 1) ||
             !slab_ok("o", seqlen_q, (int64_t)num_heads * head_size, 2)) return;
@@ -604,25 +626,25 @@ void fmha_fwd_fp8(void* q, void* k, void* v, void* o, void* softmax_lse, float q
                    seqlen_q, seqlen_k, window_size_left, window_size_right, softmax_scale, 0.f, nullptr, 0);
         dense_strides(p, seqlen_q, seqlen_k, num_heads, num_heads_k, head_size);
         // fwd_dyn = 2: the dynamic per-XCD item queues for the dense fp8 launch too
-        run_fwd_fp8(p, q_scale, k_scale, v_scale, 2, out_fp16, stream, "fp8 forward launch");
+        run_fwd_fp8(p, ds, 2, out_fp16, stream, "fp8 forward launch");
     } catch (...) {
-        fail(9, "internal error in fmha_fwd_fp8");
+        fail(9, "internal error in %s", entry);
     }
 }
 
-void fmha_varlen_fwd_fp8(void* q, void* k, void* v, void* o, void* softmax_lse,
-                         void* cu_seqlens_q, void* cu_seqlens_k, void* seqused_k,
-                         float q_scale, float k_scale, float v_scale,
-                         int32_t max_seqlen_q, int32_t max_seqlen_k, int32_t total_q,
-                         int32_t batch_size, int32_t num_heads, int32_t num_heads_k, int32_t head_size,
-                         float softmax_scale, int window_size_left, int window_size_right,
-                         bool out_fp16, hipStream_t stream) {
+void varlen_fwd_fp8_entry(const char* entry, void* q, void* k, void* v, void* o, void* softmax_lse,
+                          void* cu_seqlens_q, void* cu_seqlens_k, void* seqused_k,
+                          const Fp8Descales& ds, bool device_descales,
+                          int32_t max_seqlen_q, int32_t max_seqlen_k, int32_t total_q,
+                          int32_t batch_size, int32_t num_heads, int32_t num_heads_k, int32_t head_size,
+                          float softmax_scale, int window_size_left, int window_size_right,
+                          bool out_fp16, hipStream_t stream) {
     try {
         begin_fwd();
         if (!check_common(q, k, v, o, batch_size, num_heads, num_heads_k, head_size)) return;
         REQUIRE(cu_seqlens_q && cu_seqlens_k, "cu_seqlens_q and cu_seqlens_k must be given");
         REQUIRE(head_size == 128, "the fp8 forward supports head_size 128 (got %d)", head_size);
-        REQUIRE(q_scale > 0.f && k_scale > 0.f && v_scale > 0.f, "fp8 descales must be positive");
+        if (!check_descales(ds, device_descales)) return;
         REQUIRE(max_seqlen_q > 0, "max_seqlen_q must be positive (got %d)", max_seqlen_q);
         REQUIRE(max_seqlen_k > 0, "max_seqlen_k must be positive (got %d): nothing to attend to", max_seqlen_k);
         REQUIRE(!softmax_lse || total_q > 0, "total_q must be given to address the LSE");
@@ -640,9 +662,117 @@ void fmha_varlen_fwd_fp8(void* q, void* k, void* v, void* o, void* softmax_lse,
         p.seqused_k = (const int*)seqused_k;
         // ragged items balance from the dynamic item queue (fwd_dyn >= 1, as the bf16 varlen
         // launches); fwd_dyn = 0 keeps the static persistent schedules
-        run_fwd_fp8(p, q_scale, k_scale, v_scale, 1, out_fp16, stream, "fp8 varlen forward launch");
+        run_fwd_fp8(p, ds, 1, out_fp16, stream, "fp8 varlen forward launch");
     } catch (...) {
-        fail(9, "internal error in fmha_varlen_fwd_fp8");
+        fail(9, "internal error in %s", entry);
+    }
+}
+
+Fp8Descales descales_by_value(float q, float k, float v) {
+    Fp8Descales ds;
+    ds.q = q; ds.k = k; ds.v = v;
+    return ds;
+}
+Fp8Descales descales_on_device(const float* q, const float* k, const float* v, int batch_stride, int head_stride) {
+    Fp8Descales ds;
+    ds.q_ptr = q; ds.k_ptr = k; ds.v_ptr = v;
+    ds.batch_stride = batch_stride; ds.head_stride = head_stride;
+    return ds;
+}
+
+}  // namespace
+
+extern "C" {
+
+void fmha_fwd_fp8(void* q, void* k, void* v, void* o, void* softmax_lse, float q_scale,
+                  float k_scale, float v_scale, int32_t seqlen_q, int32_t seqlen_k,
+                  int32_t batch_size, int32_t num_heads, int32_t num_heads_k, int32_t head_size,
+                  float softmax_scale, int window_size_left, int window_size_right, bool out_fp16,
+                  hipStream_t stream) {
+    fwd_fp8_entry("fmha_fwd_fp8", q, k, v, o, softmax_lse, descales_by_value(q_scale, k_scale, v_scale),
+                  false, seqlen_q, seqlen_k, batch_size, num_heads, num_heads_k, head_size,
+                  softmax_scale, window_size_left, window_size_right, out_fp16, stream);
+}
+
+void fmha_fwd_fp8_ex(void* q, void* k, void* v, void* o, void* softmax_lse, const float* q_descale,
+                     const float* k_descale, const float* v_descale, int32_t descale_batch_stride,
+                     int32_t descale_head_stride, int32_t seqlen_q, int32_t seqlen_k,
+                     int32_t batch_size, int32_t num_heads, int32_t num_heads_k, int32_t head_size,
+                     float softmax_scale, int window_size_left, int window_size_right, bool out_fp16,
+                     hipStream_t stream) {
+    fwd_fp8_entry("fmha_fwd_fp8_ex", q, k, v, o, softmax_lse,
+                  descales_on_device(q_descale, k_descale, v_descale, descale_batch_stride, descale_head_stride),
+                  true, seqlen_q, seqlen_k, batch_size, num_heads, num_heads_k, head_size,
+                  softmax_scale, window_size_left, window_size_right, out_fp16, stream);
+}
+
+void fmha_varlen_fwd_fp8(void* q, void* k, void* v, void* o, void* softmax_lse,
+                         void* cu_seqlens_q, void* cu_seqlens_k, void* seqused_k,
+                         float q_scale, float k_scale, float v_scale,
+                         int32_t max_seqlen_q, int32_t max_seqlen_k, int32_t total_q,
+                         int32_t batch_size, int32_t num_heads, int32_t num_heads_k, int32_t head_size,
+                         float softmax_scale, int window_size_left, int window_size_right,
+                         bool out_fp16, hipStream_t stream) {
+    varlen_fwd_fp8_entry("fmha_varlen_fwd_fp8", q, k, v, o, softmax_lse, cu_seqlens_q, cu_seqlens_k,
+                         seqused_k, descales_by_value(q_scale, k_scale, v_scale), false, max_seqlen_q,
+                         max_seqlen_k, total_q, batch_size, num_heads, num_heads_k, head_size,
+                         softmax_scale, window_size_left, window_size_right, out_fp16, stream);
+}
+
+void fmha_varlen_fwd_fp8_ex(void* q, void* k, void* v, void* o, void* softmax_lse,
+                            void* cu_seqlens_q, void* cu_seqlens_k, void* seqused_k,
+                            const float* q_descale, const float* k_descale, const float* v_descale,
+                            int32_t descale_batch_stride, int32_t descale_head_stride,
+                            int32_t max_seqlen_q, int32_t max_seqlen_k, int32_t total_q,
+                            int32_t batch_size, int32_t num_heads, int32_t num_heads_k, int32_t head_size,
+                            float softmax_scale, int window_size_left, int window_size_right,
+                            bool out_fp16, hipStream_t stream) {
+    varlen_fwd_fp8_entry("fmha_varlen_fwd_fp8_ex", q, k, v, o, softmax_lse, cu_seqlens_q, cu_seqlens_k,
+                         seqused_k,
+                         descales_on_device(q_descale, k_descale, v_descale, descale_batch_stride, descale_head_stride),
+                         true, max_seqlen_q, max_seqlen_k, total_q, batch_size, num_heads, num_heads_k,
+                         head_size, softmax_scale, window_size_left, window_size_right, out_fp16, stream);
+}
+
+void fmha_quantize_fp8(const void* x, void* x8, float* descale, const void* cu_seqlens,
+                       int32_t batch_size, int32_t seqlen, int32_t num_heads, int32_t group,
+                       int32_t head_size, const int64_t* strides, int32_t granularity, bool is_fp16,
+                       hipStream_t stream) {
+    try {
+        begin_fwd();
+        REQUIRE(x && x8 && descale && strides, "x, x8, descale and strides must be non-null pointers");
+        REQUIRE(batch_size > 0 && batch_size <= 65535, "batch size must be in [1, 65535] (got %d)", batch_size);
+        REQUIRE(seqlen > 0, "seqlen must be positive (got %d)", seqlen);
+        REQUIRE(num_heads > 0, "num_heads must be positive (got %d)", num_heads);
+        REQUIRE(head_size > 0 && head_size % 8 == 0 && head_size <= 256,
+                "head_size must be a multiple of 8 and at most 256 (got %d)", head_size);
+        REQUIRE(group > 0 && num_heads % group == 0,
+                "group must divide the number of heads (heads=%d, group=%d)", num_heads, group);
+        REQUIRE(granularity == 0 || granularity == 1,
+                "granularity must be 0 (per tensor) or 1 (per batch and head group), got %d", granularity);
+        REQUIRE(!(((uintptr_t)x) & 15) && !(((uintptr_t)x8) & 7),
+                "x must be 16-byte and x8 8-byte aligned device pointers");
+        const int ext[3] = {cu_seqlens ? 1 : batch_size, seqlen, num_heads};
+        for (int i = 0; i < 3; ++i)
+            REQUIRE(strides[i] >= 0 && (ext[i] == 1 || strides[i] % 8 == 0),
+                    "strides must be non-negative multiples of 8 elements (16 bytes): stride %d is %lld",
+                    i, (long long)strides[i]);
+        {   // the slab rule of the other entries (one sequence's rows of x)
+            const int64_t bytes = ((int64_t)(seqlen - 1) * strides[1] + (int64_t)(num_heads - 1) * strides[2] + head_size) * 2;
+            REQUIRE(bytes < kMaxSlabBytes, "x: one sequence spans %lld bytes; this build supports < %lld bytes",
+                    (long long)bytes, (long long)kMaxSlabBytes);
+        }
+        const int nscale = granularity ? batch_size * (num_heads / group) : 1;
+        QuantParams p{};
+        p.x = x; p.x8 = x8; p.descale = descale; p.cu = (const int*)cu_seqlens;
+        p.b = batch_size; p.s = seqlen; p.h = num_heads; p.group = group; p.d = head_size;
+        p.gran = granularity;
+        p.x_batch = strides[0]; p.x_row = strides[1]; p.x_head = strides[2];
+        p.amax = (unsigned*)pool_get(stream, (size_t)nscale * sizeof(unsigned));
+        if (!p.amax) { fail(3, "could not allocate the amax accumulator"); return; }
+        hip_ok(launch_quantize_fp8(p, is_fp16, stream), "fp8 quantise launch");
+    } catch (...) {
+        fail(9, "internal error in fmha_quantize_fp8");
     }
 }
 
@@ -743,16 +873,26 @@ void fmha_page_kvcache_fwd_ex(void* q, void* kcache, void* vcache, void* o, void
     }
 }
 
-void fmha_kvcache_append(void* q, void* q_out, void* kcache, void* vcache, const void* knew,
-                         const void* vnew, int32_t seqlen_new, const void* block_table,
-                         int32_t block_table_stride, int32_t page_block_size,
-                         const void* cache_seqlens, void* seqlens_out, const void* rotary_cos,
-                         const void* rotary_sin, int32_t rotary_dim, bool is_rotary_interleaved,
-                         bool q_rotary_per_token, int32_t batch_size, int32_t seqlen_q,
-                         int32_t num_heads, int32_t num_heads_k, int32_t head_size,
-                         bool is_fp16, hipStream_t stream) {
+}  // extern "C"
+
+namespace {
+
+// fmha_kvcache_append (fp8 = false: the caches in q's dtype) and fmha_kvcache_append_fp8 (e4m3fn
+// caches with their descales)
+void kvcache_append_entry(const char* entry, bool fp8, float k_scale, float v_scale,
+                          void* q, void* q_out, void* kcache, void* vcache, const void* knew,
+                          const void* vnew, int32_t seqlen_new, const void* block_table,
+                          int32_t block_table_stride, int32_t page_block_size,
+                          const void* cache_seqlens, void* seqlens_out, const void* rotary_cos,
+                          const void* rotary_sin, int32_t rotary_dim, bool is_rotary_interleaved,
+                          bool q_rotary_per_token, int32_t batch_size, int32_t seqlen_q,
+                          int32_t num_heads, int32_t num_heads_k, int32_t head_size,
+                          bool is_fp16, hipStream_t stream) {
     try {
         clear_error();
+        // (k_scale > 0 is false for a NaN too)
+        REQUIRE(!fp8 || (k_scale > 0.f && v_scale > 0.f && std::isfinite(k_scale) && std::isfinite(v_scale)),
+                "fp8 cache descales must be positive");
         REQUIRE(kcache && vcache && block_table && cache_seqlens,
                 "kcache, vcache, block_table and cache_seqlens must be given");
         REQUIRE(seqlen_new >= 0, "seqlen_new must be >= 0");
@@ -785,10 +925,47 @@ void fmha_kvcache_append(void* q, void* q_out, void* kcache, void* vcache, const
         p.kn_batch = (int64_t)seqlen_new * p.kn_row;
         p.head_stride = head_size; p.row_stride = (int64_t)num_heads_k * head_size;
         p.page_stride = (int64_t)page_block_size * p.row_stride;
+        p.cache_fp8 = fp8;
+        p.k_inv = fp8 ? 1.f / k_scale : 1.f;
+        p.v_inv = fp8 ? 1.f / v_scale : 1.f;
         hip_ok(launch_append(p, is_fp16, stream), "append launch");
     } catch (...) {
-        fail(9, "internal error in fmha_kvcache_append");
+        fail(9, "internal error in %s", entry);
     }
+}
+
+}  // namespace
+
+extern "C" {
+
+void fmha_kvcache_append(void* q, void* q_out, void* kcache, void* vcache, const void* knew,
+                         const void* vnew, int32_t seqlen_new, const void* block_table,
+                         int32_t block_table_stride, int32_t page_block_size,
+                         const void* cache_seqlens, void* seqlens_out, const void* rotary_cos,
+                         const void* rotary_sin, int32_t rotary_dim, bool is_rotary_interleaved,
+                         bool q_rotary_per_token, int32_t batch_size, int32_t seqlen_q,
+                         int32_t num_heads, int32_t num_heads_k, int32_t head_size,
+                         bool is_fp16, hipStream_t stream) {
+    kvcache_append_entry("fmha_kvcache_append", false, 1.f, 1.f, q, q_out, kcache, vcache, knew, vnew,
+                         seqlen_new, block_table, block_table_stride, page_block_size, cache_seqlens,
+                         seqlens_out, rotary_cos, rotary_sin, rotary_dim, is_rotary_interleaved,
+                         q_rotary_per_token, batch_size, seqlen_q, num_heads, num_heads_k, head_size,
+                         is_fp16, stream);
+}
+
+void fmha_kvcache_append_fp8(void* q, void* q_out, void* kcache, void* vcache, const void* knew,
+                             const void* vnew, int32_t seqlen_new, const void* block_table,
+                             int32_t block_table_stride, int32_t page_block_size,
+                             const void* cache_seqlens, void* seqlens_out, const void* rotary_cos,
+                             const void* rotary_sin, int32_t rotary_dim, bool is_rotary_interleaved,
+                             bool q_rotary_per_token, int32_t batch_size, int32_t seqlen_q,
+                             int32_t num_heads, int32_t num_heads_k, int32_t head_size,
+                             bool is_fp16, hipStream_t stream, float k_scale, float v_scale) {
+    kvcache_append_entry("fmha_kvcache_append_fp8", true, k_scale, v_scale, q, q_out, kcache, vcache,
+                         knew, vnew, seqlen_new, block_table, block_table_stride, page_block_size,
+                         cache_seqlens, seqlens_out, rotary_cos, rotary_sin, rotary_dim,
+                         is_rotary_interleaved, q_rotary_per_token, batch_size, seqlen_q, num_heads,
+                         num_heads_k, head_size, is_fp16, stream);
 }
 
 void fmha_page_kvcache_fwd(void* q_ptr, void* kcache_ptr, void* vcache_ptr, void* /*k_ptr*/,

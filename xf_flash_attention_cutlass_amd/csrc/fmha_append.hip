@@ -17,6 +17,10 @@
 //   interleaved (GPT-J):        x1 = x[2i], x2 = x[2i + 1]      -> same, with c = cos[pos][i]
 // computed in fp32 and rounded once.  One thread owns 8 output elements (16 bytes); in the
 // non-interleaved case a thread of the first half also writes the partner chunk.
+//
+// An fp8 cache (fmha_kvcache_append_fp8; cache element type uint8_t = OCP e4m3fn bytes): the
+// fp32 value (K after its rotary, V as read) is multiplied by 1 / k_scale or 1 / v_scale,
+// clamped to +-448 and rounded once to e4m3 (no 16-bit step in between), 8 bytes per store.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -42,10 +46,30 @@ __device__ __forceinline__ void store8(T* p, const float (&x)[8]) {
     *reinterpret_cast<T8*>(p) = v;
 }
 
-// rotate-and-store one row (8 elements per thread; chunk c of the row)
+// 8 fp32 values x inv -> 8 e4m3fn bytes (v_cvt_pk_fp8_f32: round to nearest even), one store
+__device__ __forceinline__ void store8(uint8_t* p, const float (&x)[8], const float inv) {
+    float f[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const float v = x[i] * inv;
+        f[i] = v < -448.f ? -448.f : (v > 448.f ? 448.f : v);
+    }
+    int lo = 0, hi = 0;
+    lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], lo, false);
+    lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], lo, true);
+    hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], hi, false);
+    hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], hi, true);
+    *reinterpret_cast<u32x2*>(p) = u32x2{(unsigned)lo, (unsigned)hi};
+}
+// (a cache in q's dtype: no scale)
 template <typename T>
-__device__ __forceinline__ void rotate_row(const AppendParams& p, const T* src, T* dst, int c,
-                                           int pos) {
+__device__ __forceinline__ void store8(T* p, const float (&x)[8], const float) { store8(p, x); }
+
+// rotate-and-store one row (8 elements per thread; chunk c of the row); C: the destination's
+// element type (T, or uint8_t for an fp8 cache, then scaled by inv)
+template <typename T, typename C>
+__device__ __forceinline__ void rotate_row(const AppendParams& p, const T* src, C* dst, int c,
+                                           int pos, const float inv) {
     const int e0 = 8 * c;
     if (e0 >= p.d) return;
     const T* cs = reinterpret_cast<const T*>(p.cos) + (int64_t)pos * (p.rdim / 2);
@@ -53,7 +77,7 @@ __device__ __forceinline__ void rotate_row(const AppendParams& p, const T* src, 
     float x[8];
     load8(src + e0, x);
     if (e0 >= p.rdim) {                 // past the rotary part: copy
-        store8(dst + e0, x);
+        store8(dst + e0, x, inv);
         return;
     }
     if (p.interleaved) {
@@ -64,7 +88,7 @@ __device__ __forceinline__ void rotate_row(const AppendParams& p, const T* src, 
             x[2 * i] = x1 * c0 - x2 * s0;
             x[2 * i + 1] = x1 * s0 + x2 * c0;
         }
-        store8(dst + e0, x);
+        store8(dst + e0, x, inv);
         return;
     }
     const int half = p.rdim / 2;
@@ -78,13 +102,14 @@ __device__ __forceinline__ void rotate_row(const AppendParams& p, const T* src, 
         x[i] = x1 * c0 - x2 * s0;
         y[i] = x1 * s0 + x2 * c0;
     }
-    store8(dst + e0, x);
-    store8(dst + e0 + half, y);
+    store8(dst + e0, x, inv);
+    store8(dst + e0 + half, y, inv);
 }
 
 // rows [0, n_kv) are new K/V rows (b, j, hk); rows [n_kv, n_kv + n_q) are q rows (b, s, h)
-template <typename T>
+template <typename T, typename C>
 __global__ void __launch_bounds__(256) fmha_append_kernel(const AppendParams p) {
+    constexpr bool kFp8 = !std::is_same<T, C>::value;
     const int cpr = p.d / 8;                           // 16-byte chunks per row
     const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int64_t row = t / cpr;
@@ -107,13 +132,25 @@ __global__ void __launch_bounds__(256) fmha_append_kernel(const AppendParams p) 
         const int64_t src = (int64_t)bi * p.kn_batch + (int64_t)j * p.kn_row + (int64_t)hki * p.kn_head;
         const T* kn = reinterpret_cast<const T*>(p.knew) + src;
         const T* vn = reinterpret_cast<const T*>(p.vnew) + src;
-        T* kc = reinterpret_cast<T*>(p.kcache) + slot;
-        T* vc = reinterpret_cast<T*>(p.vcache) + slot;
+        C* kc = reinterpret_cast<C*>(p.kcache) + slot;
+        C* vc = reinterpret_cast<C*>(p.vcache) + slot;
         if (8 * c < p.d) {
             typedef __attribute__((ext_vector_type(8))) T T8;
-            *reinterpret_cast<T8*>(vc + 8 * c) = *reinterpret_cast<const T8*>(vn + 8 * c);
-            if (p.rdim > 0) rotate_row<T>(p, kn, kc, c, pos);
-            else *reinterpret_cast<T8*>(kc + 8 * c) = *reinterpret_cast<const T8*>(kn + 8 * c);
+            if constexpr (kFp8) {
+                float x[8];
+                load8(vn + 8 * c, x);
+                store8(vc + 8 * c, x, p.v_inv);
+                if (p.rdim > 0) {
+                    rotate_row<T, C>(p, kn, kc, c, pos, p.k_inv);
+                } else {
+                    load8(kn + 8 * c, x);
+                    store8(kc + 8 * c, x, p.k_inv);
+                }
+            } else {
+                *reinterpret_cast<T8*>(vc + 8 * c) = *reinterpret_cast<const T8*>(vn + 8 * c);
+                if (p.rdim > 0) rotate_row<T, C>(p, kn, kc, c, pos, 1.f);
+                else *reinterpret_cast<T8*>(kc + 8 * c) = *reinterpret_cast<const T8*>(kn + 8 * c);
+            }
         }
     } else if (row < n_kv + n_q) {
         const int64_t r = row - n_kv;
@@ -123,7 +160,7 @@ __global__ void __launch_bounds__(256) fmha_append_kernel(const AppendParams p) 
         const int bi = (int)(bs / p.sq);
         const int pos = p.cache_seqlens[bi] + (p.q_per_token ? s : 0);
         const int64_t off = (int64_t)bi * p.q_batch + (int64_t)s * p.q_row + (int64_t)hi * p.q_head;
-        rotate_row<T>(p, reinterpret_cast<const T*>(p.q) + off, reinterpret_cast<T*>(p.q_out) + off, c, pos);
+        rotate_row<T, T>(p, reinterpret_cast<const T*>(p.q) + off, reinterpret_cast<T*>(p.q_out) + off, c, pos, 1.f);
     }
 }
 
@@ -132,8 +169,13 @@ hipError_t launch_append(const AppendParams& p, bool fp16, hipStream_t st) {
     const int64_t rows = (int64_t)p.b * p.snew * p.hk + (p.rdim > 0 ? (int64_t)p.b * p.sq * p.h : 0);
     const int64_t threads = rows * cpr > p.b ? rows * cpr : p.b;
     const unsigned blocks = (unsigned)((threads + 255) / 256);
-    if (fp16) hipLaunchKernelGGL(fmha_append_kernel<_Float16>, dim3(blocks), dim3(256), 0, st, p);
-    else hipLaunchKernelGGL(fmha_append_kernel<__bf16>, dim3(blocks), dim3(256), 0, st, p);
+    if (p.cache_fp8) {
+        if (fp16) hipLaunchKernelGGL((fmha_append_kernel<_Float16, uint8_t>), dim3(blocks), dim3(256), 0, st, p);
+        else hipLaunchKernelGGL((fmha_append_kernel<__bf16, uint8_t>), dim3(blocks), dim3(256), 0, st, p);
+    } else {
+        if (fp16) hipLaunchKernelGGL((fmha_append_kernel<_Float16, _Float16>), dim3(blocks), dim3(256), 0, st, p);
+        else hipLaunchKernelGGL((fmha_append_kernel<__bf16, __bf16>), dim3(blocks), dim3(256), 0, st, p);
+    }
     return hipGetLastError();
 }
 

@@ -160,7 +160,29 @@ struct FwdParams {
     const int64_t* seed_ptr;
     const int64_t* offset_ptr;
     int64_t* rng_out;
+    // fp8 Q/K/V forward, device descales (the _ex entries): element (batch, kv head) of each is
+    // ptr[batch * ds_batch + kv head * ds_head]; (0, 0) a one-element per-tensor scale.  Null
+    // (the by-value entries): q_scale / k_scale / v_scale above.
+    const float* q_descale;
+    const float* k_descale;
+    const float* v_descale;
+    int ds_batch, ds_head;
 };
+
+// The fp8 forward's descales of item (batch, kv head), workgroup-uniform.  DSC = true (the
+// instantiation the _ex entries launch): read from the device tensors with scalar loads; false:
+// the by-value ones of the params, so the by-value kernels compile to the code they had before
+// the device descales existed (a shared prologue with a branch measured + 1 % on the C2 shape).
+struct Fp8Scales { float q, k, v; };
+template <bool DSC>
+__device__ __forceinline__ Fp8Scales fp8_scales(const FwdParams& p, const int bidx, const int hk_i) {
+    if constexpr (DSC) {
+        const int i = __builtin_amdgcn_readfirstlane(bidx * p.ds_batch + hk_i * p.ds_head);
+        return Fp8Scales{p.q_descale[i], p.k_descale[i], p.v_descale[i]};
+    } else {
+        return Fp8Scales{p.q_scale, p.k_scale, p.v_scale};
+    }
+}
 
 // Sequence `bidx` of a packed (varlen / seqused_k) launch: first row and length on the q and the
 // k side, as workgroup-uniform scalars (the fp8 kernels build buffer descriptors from them).

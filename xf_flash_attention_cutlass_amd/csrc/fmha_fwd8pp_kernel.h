@@ -22,7 +22,7 @@ constexpr int kFwd8ppVReg = kFwd8ppRing * kFwd8wTile;      // the V ring follows
 constexpr int kFwd8ppSmem = 2 * kFwd8ppRing * kFwd8wTile;  // (kFwd8ppRing: the generated body's)
 
 // One (batch x kv head, 256-row query block) item.
-template <bool F16>
+template <bool F16, bool DSC>
 __device__ __forceinline__ void fwd8pp_item(const FwdParams& p, char* smem, const int bh, const int m_block) {
     constexpr int HD = 128;
     int tid = threadIdx.x;
@@ -34,6 +34,8 @@ __device__ __forceinline__ void fwd8pp_item(const FwdParams& p, char* smem, cons
 
     const int bidx = bh / p.hk;
     const int hk_i = bh - bidx * p.hk;
+    // this item's descales first: device descales are loaded under the rest of the prologue
+    const Fp8Scales ds = fp8_scales<DSC>(p, bidx, hk_i);
     const int sq = p.seqlen_q, sk = p.seqlen_k;
     const int G = p.group;
     const int rows_total = sq * G;
@@ -118,22 +120,22 @@ __device__ __forceinline__ void fwd8pp_item(const FwdParams& p, char* smem, cons
     const int kstep = __builtin_amdgcn_readfirstlane(kBlockN * k_row);
     const int kdst = __builtin_amdgcn_readfirstlane(sbase + wave * 1024);
     const int grp = __builtin_amdgcn_readfirstlane(wave >> 2);
-    const float c = p.scale_log2 * p.q_scale * p.k_scale;
+    const float c = p.scale_log2 * ds.q * ds.k;
     const float thr = __builtin_amdgcn_exp2f(fminf(p.max_slack, 8.f));   // P <= 256 < 448
     const int kvb = __builtin_amdgcn_readfirstlane((int)kvbytes);
     if constexpr (F16)
         fwd8pp_item_f16(kblo, kbhi, vblo, vbhi, kvb, qsrd, osrd, lsrd, kstep, kdst, ntl, t_w, e_w, grp,
-                        c, thr, p.v_scale, ka[0], ka[1], ka[2], ka[3], va[0], va[1], va[2], va[3], dk, dv,
+                        c, thr, ds.v, ka[0], ka[1], ka[2], ka[3], va[0], va[1], va[2], va[3], dk, dv,
                         lim, qoff, ooff, loff);
     else
         fwd8pp_item_bf16(kblo, kbhi, vblo, vbhi, kvb, qsrd, osrd, lsrd, kstep, kdst, ntl, t_w, e_w, grp,
-                         c, thr, p.v_scale, ka[0], ka[1], ka[2], ka[3], va[0], va[1], va[2], va[3], dk, dv,
+                         c, thr, ds.v, ka[0], ka[1], ka[2], ka[3], va[0], va[1], va[2], va[3], dk, dv,
                          lim, qoff, ooff, loff);
 }
 
 // Persistent grid (one workgroup per CU): XCD-grouped (n-1-i, i) row-block pairs, or (fwd_dyn
 // = 2) the per-XCD dynamic item queues, as fmha_fwd8w_kernel.
-template <bool F16>
+template <bool F16, bool DSC>
 __global__ void __launch_bounds__(512, 1) fmha_fwd8pp_kernel(const FwdParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __shared__ int s_claim[2];
@@ -175,7 +177,7 @@ __global__ void __launch_bounds__(512, 1) fmha_fwd8pp_kernel(const FwdParams p) 
             bh = blockIdx.x;
             m_block = gridDim.y - 1 - blockIdx.y;
         }
-        fwd8pp_item<F16>(p, smem, bh, m_block);
+        fwd8pp_item<F16, DSC>(p, smem, bh, m_block);
     }
     if (p.persistent == 3 && threadIdx.x == 0) {
         const int total = (int)(gridDim.x * gridDim.y * gridDim.z);

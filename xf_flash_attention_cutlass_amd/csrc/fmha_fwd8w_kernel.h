@@ -53,7 +53,7 @@ __device__ __forceinline__ int v8w_swz(int row) { return (((row >> 1) & 1) | (((
 __device__ __forceinline__ int v8w_off(int row, int chunk) { return row * 128 + 16 * (chunk ^ v8w_swz(row)); }
 
 // One (batch x kv head, 256-row query block) item.
-template <bool F16, bool VARLEN>
+template <bool F16, bool VARLEN, bool DSC>
 __device__ __forceinline__ void fwd8w_item(const FwdParams& p, char* smem, const int bh, const int m_block XFA_F8_ACC_PARAM) {
     constexpr int HD = 128;
     int tid = threadIdx.x;
@@ -65,6 +65,8 @@ __device__ __forceinline__ void fwd8w_item(const FwdParams& p, char* smem, const
 
     const int bidx = bh / p.hk;
     const int hk_i = bh - bidx * p.hk;
+    // this item's descales first: device descales are loaded under the rest of the prologue
+    const Fp8Scales ds = fp8_scales<DSC>(p, bidx, hk_i);
     // varlen / seqused_k: this sequence's rows of the packed tensors (dense: q_off = k_off = 0)
     const SeqRange sr = seq_range<VARLEN>(p, bidx);
     const int q_off = sr.q_off, sq = sr.sq, k_off = sr.k_off, sk = sr.sk;
@@ -164,21 +166,21 @@ __device__ __forceinline__ void fwd8w_item(const FwdParams& p, char* smem, const
     }
     const int kstep = __builtin_amdgcn_readfirstlane(kBlockN * k_row);
     const int kdst = __builtin_amdgcn_readfirstlane(sbase + wave * 2048);
-    const float c = p.scale_log2 * p.q_scale * p.k_scale;
+    const float c = p.scale_log2 * ds.q * ds.k;
     const float thr = __builtin_amdgcn_exp2f(fminf(p.max_slack, 8.f));   // P <= 256 < 448
     if constexpr (F16)
         fwd8_item_f16(kblo, kbhi, vblo, vbhi, (int)kvbytes, qsrd, osrd, lsrd, kstep, kdst, ntl, t_w, e_w,
-                      c, thr, p.v_scale, ka[0], ka[1], ka[2], ka[3], va[0], va[1], va[2], va[3], dk[0], dk[1],
+                      c, thr, ds.v, ka[0], ka[1], ka[2], ka[3], va[0], va[1], va[2], va[3], dk[0], dk[1],
                       dv[0], dv[1], lim[0], lim[1], qoff[0], qoff[1], ooff[0], ooff[1], loff[0], loff[1] XFA_F8_ACC_ARG);
     else
         fwd8_item_bf16(kblo, kbhi, vblo, vbhi, (int)kvbytes, qsrd, osrd, lsrd, kstep, kdst, ntl, t_w, e_w,
-                       c, thr, p.v_scale, ka[0], ka[1], ka[2], ka[3], va[0], va[1], va[2], va[3], dk[0], dk[1],
+                       c, thr, ds.v, ka[0], ka[1], ka[2], ka[3], va[0], va[1], va[2], va[3], dk[0], dk[1],
                        dv[0], dv[1], lim[0], lim[1], qoff[0], qoff[1], ooff[0], ooff[1], loff[0], loff[1] XFA_F8_ACC_ARG);
 }
 
 // Persistent grid (one workgroup per CU): XCD-grouped (n-1-i, i) row-block pairs, or (fwd_dyn
 // = 2) the per-XCD dynamic item queues, as the bf16 kernels.
-template <bool F16, bool VARLEN>
+template <bool F16, bool VARLEN, bool DSC>
 __global__ void __launch_bounds__(256, 1) fmha_fwd8w_kernel(const FwdParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __shared__ int s_claim[2];
@@ -223,7 +225,7 @@ __global__ void __launch_bounds__(256, 1) fmha_fwd8w_kernel(const FwdParams p) {
             bh = blockIdx.x;
             m_block = gridDim.y - 1 - blockIdx.y;
         }
-        fwd8w_item<F16, VARLEN>(p, smem, bh, m_block XFA_F8_ACC_ARG);
+        fwd8w_item<F16, VARLEN, DSC>(p, smem, bh, m_block XFA_F8_ACC_ARG);
     }
 #ifdef XFA_FWD8_STAMPS
     if ((threadIdx.x & 63) < 8) atomicAdd(&g_fwd8_stamps[(threadIdx.x >> 6) * 8 + (threadIdx.x & 63)], (unsigned long long)acc);

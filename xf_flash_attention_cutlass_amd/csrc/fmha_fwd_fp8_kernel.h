@@ -47,7 +47,7 @@ __device__ __forceinline__ int v8_off(int row, int chunk) {      // V tile image
 
 constexpr int kFp8Tile = 64 * 128;        // bytes of one K (or V) tile: 64 keys x D = 128
 
-template <typename T, int NW, bool MASK, bool VARLEN>
+template <typename T, int NW, bool MASK, bool VARLEN, bool DSC>
 __device__ __forceinline__ void fwd8_item(const FwdParams& p, char* smem, const int bh,
                                           const int m_block) {
     constexpr int HD = 128;
@@ -67,6 +67,8 @@ __device__ __forceinline__ void fwd8_item(const FwdParams& p, char* smem, const 
 
     const int bidx = bh / p.hk;
     const int hk_i = bh - bidx * p.hk;
+    // this item's descales first: device descales are loaded under the rest of the prologue
+    const Fp8Scales ds = fp8_scales<DSC>(p, bidx, hk_i);
     // varlen / seqused_k: this sequence's rows of the packed tensors (dense: q_off = k_off = 0)
     const SeqRange sr = seq_range<VARLEN>(p, bidx);
     const int q_off = sr.q_off, sq = sr.sq, k_off = sr.k_off, sk = sr.sk;
@@ -96,7 +98,7 @@ __device__ __forceinline__ void fwd8_item(const FwdParams& p, char* smem, const 
     const int w_ll_min = lim_l(wp_lo), w_ll_max = lim_l(wp_hi);
     const int my_lr = lim_r(pos), my_ll = lim_l(pos);
     // scores arrive in q8.k8 units: fold both descales into the exp2 scale
-    const float c = p.scale_log2 * p.q_scale * p.k_scale;
+    const float c = p.scale_log2 * ds.q * ds.k;
 
     // ---- Q fragments: lane holds Q[row][64 s + 32 hh .. +31] (fp8 bytes) for s = 0, 1
     i32x8 qf[2];
@@ -541,7 +543,7 @@ __device__ __forceinline__ void fwd8_item(const FwdParams& p, char* smem, const 
     // ---- epilogue: O = v_scale * acc / l, LSE in natural units of the dequantised scores
     const float l_full = wave_sum_halves(l_run);
     const bool empty = (l_full == 0.f) || (l_full != l_full);
-    const float inv = empty ? 1.f : p.v_scale / l_full;
+    const float inv = empty ? 1.f : ds.v / l_full;
     if (!row_ok) return;
     T* orow = reinterpret_cast<T*>(p.o) + (int64_t)bidx * p.o_batch + (int64_t)(q_off + pos) * p.o_row +
               (int64_t)head * p.o_head;
@@ -551,7 +553,7 @@ __device__ __forceinline__ void fwd8_item(const FwdParams& p, char* smem, const 
             empty ? INFINITY : (m_sc + __log2f(l_full)) * kLn2;
 }
 
-template <typename T, int NW, bool MASK, bool VARLEN>
+template <typename T, int NW, bool MASK, bool VARLEN, bool DSC>
 __global__ void __launch_bounds__(NW * 64, 2) fmha_fwd_fp8_kernel(const FwdParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __shared__ int s_claim[2];
@@ -586,7 +588,7 @@ __global__ void __launch_bounds__(NW * 64, 2) fmha_fwd_fp8_kernel(const FwdParam
             bh = blockIdx.x;
             m_block = gridDim.y - 1 - blockIdx.y;
         }
-        fwd8_item<T, NW, MASK, VARLEN>(p, smem, bh, m_block);
+        fwd8_item<T, NW, MASK, VARLEN, DSC>(p, smem, bh, m_block);
     }
     if (VARLEN && p.persistent == 3 && threadIdx.x == 0) {
         // the grid's last workgroup resets the queue counters for the next launch on the stream

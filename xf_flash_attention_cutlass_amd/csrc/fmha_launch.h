@@ -172,8 +172,22 @@ struct AppendParams {
     int64_t q_batch, q_row, q_head;          // elements (q and q_out share the layout)
     int64_t kn_batch, kn_row, kn_head;       // elements (knew / vnew share the layout)
     int64_t page_stride, row_stride, head_stride;   // cache strides (elements)
+    int cache_fp8;                           // 1: the caches hold OCP fp8 e4m3fn bytes, written as
+    float k_inv, v_inv;                      //    e4m3(clamp(value x k_inv / v_inv, +-448))
 };
 hipError_t launch_append(const AppendParams& p, bool fp16, hipStream_t st);
+
+// bf16 / fp16 -> fp8 e4m3fn quantisation with its descales (fmha_quant.hip)
+struct QuantParams {
+    const void* x;                    // [b, s, h, d] by element strides, or packed [total, h, d]
+    void* x8;                         // contiguous e4m3fn bytes of the same logical shape
+    float* descale;                   // [1] (gran 0) or [b, h / group]
+    unsigned* amax;                   // scratch of the same count: max |x| as float bits
+    const int* cu;                    // packed: cu_seqlens [b + 1] (then s = the longest sequence)
+    int b, s, h, group, d, gran;
+    int64_t x_batch, x_row, x_head;   // elements
+};
+hipError_t launch_quantize_fp8(const QuantParams& p, bool fp16, hipStream_t st);
 
 // Causal ALiBi LSE convention (fmha_append.hip): the kernels bias a causal score by
 // -slope |pos + diag - key| (its largest value 0 sits on the diagonal, which the in-loop

@@ -712,11 +712,37 @@ mha_fwd_kvcache_fp8(at::Tensor& q, const at::Tensor& kcache, const at::Tensor& v
 
 // fp8 e4m3fn Q/K/V forward (extension): q [b, sq, h, 128], k/v [b, sk, hk, 128] as
 // float8_e4m3fn (or uint8 bytes) with per-tensor descales; returns {out (out_dtype), lse}.
+// Device descales of the _ex ops: fp32 CUDA tensors of one element or of shape [batch, heads_k]
+// (FA3's layout), brought to one stride pair for the three of them - (0, 0) when all have one
+// element, else [batch, heads_k] contiguous (a one-element tensor expanded on the device: no
+// host read)
+struct DeviceDescales { at::Tensor q, k, v; int batch_stride, head_stride; };
+DeviceDescales device_descales(const at::Tensor& qd, const at::Tensor& kd, const at::Tensor& vd,
+                               const at::Tensor& like, int batch_size, int num_heads_k) {
+    const at::Tensor* in[3] = {&qd, &kd, &vd};
+    bool per_head = false;
+    for (const at::Tensor* t : in) {
+        TORCH_CHECK(t->is_cuda() && t->device() == like.device(), "descales must be CUDA tensors on q's device");
+        TORCH_CHECK(t->scalar_type() == torch::kFloat32, "descales must have dtype float32");
+        const bool one = t->numel() == 1;
+        TORCH_CHECK(one || t->sizes() == torch::IntArrayRef({batch_size, num_heads_k}),
+                    "a descale must have one element or shape (batch_size, num_heads_k)");
+        per_head = per_head || !one;
+    }
+    at::Tensor out[3];
+    for (int i = 0; i < 3; ++i)
+        out[i] = !per_head ? in[i]->reshape({1})
+                           : (in[i]->numel() == 1 && in[i]->dim() != 2 ? in[i]->reshape({1, 1}) : *in[i])
+                                 .expand({batch_size, num_heads_k}).contiguous();
+    return {out[0], out[1], out[2], per_head ? num_heads_k : 0, per_head ? 1 : 0};
+}
+
+// `launch(out, lse, window_left, window_right)` calls the C entry (by-value or device descales)
+template <typename F>
 std::vector<at::Tensor>
-mha_fwd_fp8(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
-            c10::optional<at::Tensor>& out_, const float q_scale, const float k_scale,
-            const float v_scale, const float softmax_scale, bool is_causal, int window_size_left,
-            int window_size_right, const bool out_fp16) {
+fwd_fp8_impl(const char* op, const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+             c10::optional<at::Tensor>& out_, bool is_causal, int window_size_left,
+             int window_size_right, const bool out_fp16, F&& launch) {
     TORCH_CHECK(q.element_size() == 1 && k.element_size() == 1 && v.element_size() == 1,
                 "fp8 forward: q, k and v must be float8_e4m3fn (or uint8 bytes)");
     CHECK_DEVICE(q); CHECK_DEVICE(k); CHECK_DEVICE(v);
@@ -744,23 +770,52 @@ mha_fwd_fp8(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
         out = torch::empty({batch_size, seqlen_q, num_heads, d}, q.options().dtype(odt));
     }
     auto lse = torch::empty({batch_size, num_heads, seqlen_q}, q.options().dtype(at::kFloat));
-    fmha_fwd_fp8(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), lse.data_ptr(), q_scale,
-                 k_scale, v_scale, seqlen_q, seqlen_k, batch_size, num_heads, num_heads_k, d,
-                 softmax_scale, window_size_left, window_size_right, out_fp16, cur_stream());
-    raise_if_failed("fwd_fp8");
+    launch(out, lse, window_size_left, window_size_right);
+    raise_if_failed(op);
     return {out, lse};
+}
+
+std::vector<at::Tensor>
+mha_fwd_fp8(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+            c10::optional<at::Tensor>& out_, const float q_scale, const float k_scale,
+            const float v_scale, const float softmax_scale, bool is_causal, int window_size_left,
+            int window_size_right, const bool out_fp16) {
+    return fwd_fp8_impl("fwd_fp8", q, k, v, out_, is_causal, window_size_left, window_size_right, out_fp16,
+                        [&](at::Tensor& out, at::Tensor& lse, int wl, int wr) {
+        fmha_fwd_fp8(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), lse.data_ptr(), q_scale,
+                     k_scale, v_scale, q.size(1), k.size(1), q.size(0), q.size(2), k.size(2), q.size(3),
+                     softmax_scale, wl, wr, out_fp16, cur_stream());
+    });
+}
+
+// ... with the descales as device tensors (one element or [batch, heads_k]): no host read
+std::vector<at::Tensor>
+mha_fwd_fp8_ex(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+               c10::optional<at::Tensor>& out_, const at::Tensor& q_descale,
+               const at::Tensor& k_descale, const at::Tensor& v_descale, const float softmax_scale,
+               bool is_causal, int window_size_left, int window_size_right, const bool out_fp16) {
+    TORCH_CHECK(q.dim() == 4 && k.dim() == 4, "q, k, v must be [b, s, h, d]");
+    const DeviceDescales ds = device_descales(q_descale, k_descale, v_descale, q, q.size(0), k.size(2));
+    return fwd_fp8_impl("fwd_fp8_ex", q, k, v, out_, is_causal, window_size_left, window_size_right, out_fp16,
+                        [&](at::Tensor& out, at::Tensor& lse, int wl, int wr) {
+        fmha_fwd_fp8_ex(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), lse.data_ptr(),
+                        ds.q.data_ptr<float>(), ds.k.data_ptr<float>(), ds.v.data_ptr<float>(),
+                        ds.batch_stride, ds.head_stride, q.size(1), k.size(1), q.size(0), q.size(2),
+                        k.size(2), q.size(3), softmax_scale, wl, wr, out_fp16, cur_stream());
+    });
 }
 
 // fp8 e4m3fn forward over packed sequences (extension): q [total_q, h, 128], k/v
 // [total_k, hk, 128], cu_seqlens int32 [b + 1], optional seqused_k int32 [b]; returns
 // {out [total_q, h, 128] (out dtype), lse [h, total_q]}.
+// `launch(out, lse, seqused pointer, window_left, window_right)` calls the C entry
+template <typename F>
 std::vector<at::Tensor>
-mha_varlen_fwd_fp8(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
-                   c10::optional<at::Tensor>& out_, const at::Tensor& cu_seqlens_q,
-                   const at::Tensor& cu_seqlens_k, c10::optional<at::Tensor>& seqused_k,
-                   int max_seqlen_q, const int max_seqlen_k, const float q_scale,
-                   const float k_scale, const float v_scale, const float softmax_scale,
-                   bool is_causal, int window_size_left, int window_size_right, const bool out_fp16) {
+varlen_fwd_fp8_impl(const char* op, const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+                    c10::optional<at::Tensor>& out_, const at::Tensor& cu_seqlens_q,
+                    const at::Tensor& cu_seqlens_k, c10::optional<at::Tensor>& seqused_k,
+                    int max_seqlen_q, const int max_seqlen_k, bool is_causal, int window_size_left,
+                    int window_size_right, const bool out_fp16, F&& launch) {
     TORCH_CHECK(q.element_size() == 1 && k.element_size() == 1 && v.element_size() == 1,
                 "fp8 varlen forward: q, k and v must be float8_e4m3fn (or uint8 bytes)");
     CHECK_DEVICE(q); CHECK_DEVICE(k); CHECK_DEVICE(v);
@@ -808,13 +863,159 @@ mha_varlen_fwd_fp8(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v
     }
     auto lse = torch::empty({num_heads, total_q}, q.options().dtype(at::kFloat));
     if (total_q == 0) return {out, lse};
-    fmha_varlen_fwd_fp8(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), lse.data_ptr(),
-                        cu_seqlens_q.data_ptr(), cu_seqlens_k.data_ptr(),
-                        seqused.defined() ? seqused.data_ptr() : nullptr, q_scale, k_scale, v_scale,
-                        max_seqlen_q, max_seqlen_k, total_q, batch_size, num_heads, num_heads_k, d,
-                        softmax_scale, window_size_left, window_size_right, out_fp16, cur_stream());
-    raise_if_failed("varlen_fwd_fp8");
+    launch(out, lse, seqused.defined() ? seqused.data_ptr() : nullptr, window_size_left, window_size_right);
+    raise_if_failed(op);
     return {out, lse};
+}
+
+std::vector<at::Tensor>
+mha_varlen_fwd_fp8(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+                   c10::optional<at::Tensor>& out_, const at::Tensor& cu_seqlens_q,
+                   const at::Tensor& cu_seqlens_k, c10::optional<at::Tensor>& seqused_k,
+                   int max_seqlen_q, const int max_seqlen_k, const float q_scale,
+                   const float k_scale, const float v_scale, const float softmax_scale,
+                   bool is_causal, int window_size_left, int window_size_right, const bool out_fp16) {
+    return varlen_fwd_fp8_impl("varlen_fwd_fp8", q, k, v, out_, cu_seqlens_q, cu_seqlens_k, seqused_k,
+                               max_seqlen_q, max_seqlen_k, is_causal, window_size_left,
+                               window_size_right, out_fp16,
+                               [&](at::Tensor& out, at::Tensor& lse, void* seqused, int wl, int wr) {
+        fmha_varlen_fwd_fp8(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), lse.data_ptr(),
+                            cu_seqlens_q.data_ptr(), cu_seqlens_k.data_ptr(), seqused, q_scale, k_scale,
+                            v_scale, max_seqlen_q, max_seqlen_k, q.size(0), cu_seqlens_q.numel() - 1,
+                            q.size(1), k.size(1), q.size(2), softmax_scale, wl, wr, out_fp16, cur_stream());
+    });
+}
+
+// ... with the descales as device tensors (one element or [sequences, heads_k]): no host read
+std::vector<at::Tensor>
+mha_varlen_fwd_fp8_ex(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+                      c10::optional<at::Tensor>& out_, const at::Tensor& cu_seqlens_q,
+                      const at::Tensor& cu_seqlens_k, c10::optional<at::Tensor>& seqused_k,
+                      int max_seqlen_q, const int max_seqlen_k, const at::Tensor& q_descale,
+                      const at::Tensor& k_descale, const at::Tensor& v_descale, const float softmax_scale,
+                      bool is_causal, int window_size_left, int window_size_right, const bool out_fp16) {
+    TORCH_CHECK(q.dim() == 3 && k.dim() == 3, "q, k, v must be [total, h, d]");
+    const DeviceDescales ds = device_descales(q_descale, k_descale, v_descale, q,
+                                              (int)cu_seqlens_q.numel() - 1, k.size(1));
+    return varlen_fwd_fp8_impl("varlen_fwd_fp8_ex", q, k, v, out_, cu_seqlens_q, cu_seqlens_k, seqused_k,
+                               max_seqlen_q, max_seqlen_k, is_causal, window_size_left,
+                               window_size_right, out_fp16,
+                               [&](at::Tensor& out, at::Tensor& lse, void* seqused, int wl, int wr) {
+        fmha_varlen_fwd_fp8_ex(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), lse.data_ptr(),
+                               cu_seqlens_q.data_ptr(), cu_seqlens_k.data_ptr(), seqused,
+                               ds.q.data_ptr<float>(), ds.k.data_ptr<float>(), ds.v.data_ptr<float>(),
+                               ds.batch_stride, ds.head_stride, max_seqlen_q, max_seqlen_k, q.size(0),
+                               cu_seqlens_q.numel() - 1, q.size(1), k.size(1), q.size(2), softmax_scale,
+                               wl, wr, out_fp16, cur_stream());
+    });
+}
+
+// bf16 / fp16 -> fp8 e4m3fn with its descale(s) (fmha_quantize_fp8): x [b, s, h, d] (any strides
+// with a contiguous last dimension) or, with cu_seqlens, packed [total, h, d] (max_seqlen <= 0:
+// total bounds a sequence's rows, so no length is read on the host); granularity 0 one scale,
+// 1 one per (batch or sequence, group of `group` heads).  Returns {x8 (float8_e4m3fn,
+// contiguous), descale fp32 [1] or [b, h / group]}.
+std::vector<at::Tensor>
+mha_quantize_fp8(const at::Tensor& x, int granularity, int group,
+                 c10::optional<at::Tensor>& cu_seqlens_, int max_seqlen) {
+    auto dt = x.dtype();
+    TORCH_CHECK(dt == torch::kFloat16 || dt == torch::kBFloat16, "quantize_fp8: x must be fp16 or bf16");
+    CHECK_DEVICE(x);
+    TORCH_CHECK(granularity == 0 || granularity == 1, "granularity must be 0 (tensor) or 1 (head)");
+    const bool packed = cu_seqlens_.has_value();
+    TORCH_CHECK(x.dim() == (packed ? 3 : 4), "x must be [b, s, h, d], or [total, h, d] with cu_seqlens");
+    at::Tensor xs = x.stride(-1) == 1 && aligned16(x) ? x : dense(x);
+    const c10::DeviceGuard device_guard(x.device());
+    at::Tensor cu;
+    int batch_size, seqlen, num_heads, d;
+    int64_t st[3];
+    if (packed) {
+        cu = cu_seqlens_.value();
+        TORCH_CHECK(cu.dtype() == torch::kInt32, "cu_seqlens must have dtype int32");
+        TORCH_CHECK(cu.is_cuda() && cu.device() == x.device(), "cu_seqlens must be on x's device");
+        CHECK_CONTIGUOUS(cu);
+        TORCH_CHECK(cu.dim() == 1 && cu.numel() >= 2, "cu_seqlens must be [batch + 1]");
+        batch_size = cu.numel() - 1;
+        seqlen = max_seqlen > 0 ? max_seqlen : (int)xs.size(0);
+        num_heads = xs.size(1); d = xs.size(2);
+        st[0] = 0; st[1] = xs.stride(0); st[2] = xs.stride(1);
+    } else {
+        batch_size = xs.size(0); seqlen = xs.size(1); num_heads = xs.size(2); d = xs.size(3);
+        st[0] = xs.stride(0); st[1] = xs.stride(1); st[2] = xs.stride(2);
+    }
+    TORCH_CHECK(group > 0 && num_heads % group == 0, "group must divide the number of heads");
+    auto x8 = torch::empty(xs.sizes(), x.options().dtype(at::kFloat8_e4m3fn));
+    auto descale = granularity ? torch::empty({batch_size, num_heads / group}, x.options().dtype(at::kFloat))
+                               : torch::empty({1}, x.options().dtype(at::kFloat));
+    if (xs.numel() == 0) { descale.fill_(1.f); return {x8, descale}; }
+    fmha_quantize_fp8(xs.data_ptr(), x8.data_ptr(), descale.data_ptr<float>(),
+                      cu.defined() ? cu.data_ptr() : nullptr, batch_size, seqlen, num_heads, group, d,
+                      st, granularity, dt == torch::kFloat16, cur_stream());
+    raise_if_failed("quantize_fp8");
+    return {x8, descale};
+}
+
+// Append new K/V rows (+ rotary on k and q) into an fp8 e4m3fn paged cache
+// (fmha_kvcache_append_fp8): the write step of fwd_kvcache for an fp8 cache.  Returns
+// {seqlens_out, q_out (rotary; else q itself)}.
+std::vector<at::Tensor>
+mha_kvcache_append_fp8(const at::Tensor& q, at::Tensor& kcache, at::Tensor& vcache,
+                       const at::Tensor& kn, const at::Tensor& vn, const at::Tensor& seqlens_k,
+                       const at::Tensor& block_table, c10::optional<at::Tensor>& rotary_cos_,
+                       c10::optional<at::Tensor>& rotary_sin_, const float k_scale,
+                       const float v_scale, bool is_rotary_interleaved, bool q_rotary_per_token) {
+    auto dt = q.dtype();
+    TORCH_CHECK(dt == torch::kFloat16 || dt == torch::kBFloat16, "q must be fp16 or bf16");
+    TORCH_CHECK(kn.dtype() == dt && vn.dtype() == dt, "new key / value must have the same dtype as query");
+    TORCH_CHECK(kcache.element_size() == 1 && vcache.element_size() == 1, "fp8 K/V cache expected");
+    CHECK_DEVICE(q); CHECK_DEVICE(kcache); CHECK_DEVICE(vcache); CHECK_DEVICE(kn); CHECK_DEVICE(vn);
+    CHECK_DEVICE(block_table); CHECK_DEVICE(seqlens_k);
+    CHECK_CONTIGUOUS(kcache); CHECK_CONTIGUOUS(vcache); CHECK_CONTIGUOUS(seqlens_k);
+    TORCH_CHECK(block_table.dtype() == torch::kInt32 && seqlens_k.dtype() == torch::kInt32,
+                "block_table / seqlens_k must be int32");
+    TORCH_CHECK(q.dim() == 4 && kn.dim() == 4 && kcache.dim() == 4 && block_table.dim() == 2,
+                "q, k, v, caches must be 4-D and block_table 2-D");
+    const int batch_size = q.size(0), seqlen_q = q.size(1), num_heads = q.size(2), d = q.size(3);
+    const int page = kcache.size(1), num_heads_k = kcache.size(2), seqlen_new = kn.size(1);
+    TORCH_CHECK(kcache.size(3) == d && d % 8 == 0 && d <= 256, "head_size must be a multiple of 8 and <= 256");
+    TORCH_CHECK(num_heads % num_heads_k == 0, "Number of heads in key/value must divide number of heads in query");
+    TORCH_CHECK(vcache.sizes() == kcache.sizes(), "k_cache and v_cache must have the same shape");
+    CHECK_SHAPE(kn, batch_size, seqlen_new, num_heads_k, d);
+    CHECK_SHAPE(vn, batch_size, seqlen_new, num_heads_k, d);
+    CHECK_SHAPE(block_table, batch_size, block_table.size(1));
+    CHECK_SHAPE(seqlens_k, batch_size);
+    TORCH_CHECK(k_scale > 0.f && v_scale > 0.f, "fp8 cache descales must be positive");
+    const c10::DeviceGuard device_guard(q.device());
+    auto qc = dense(q);
+    auto knc = dense(kn), vnc = dense(vn);
+    auto bt = block_table.contiguous();
+    int rotary_dim = 0;
+    at::Tensor cos, sin, q_rot;
+    if (rotary_cos_.has_value()) {
+        TORCH_CHECK(rotary_sin_.has_value(), "If rotary cos is provided, rotary sin must also be provided");
+        cos = rotary_cos_.value();
+        sin = rotary_sin_.value();
+        CHECK_DEVICE(cos); CHECK_DEVICE(sin); CHECK_CONTIGUOUS(cos); CHECK_CONTIGUOUS(sin);
+        TORCH_CHECK(cos.dim() == 2, "rotary_cos must be [seqlen_ro, rotary_dim / 2]");
+        rotary_dim = cos.size(1) * 2;
+        TORCH_CHECK(rotary_dim <= d, "rotary_dim must be <= headdim");
+        TORCH_CHECK(rotary_dim % 16 == 0, "Only rotary dimensions divisible by 16 are currently supported");
+        TORCH_CHECK(cos.size(0) >= (int64_t)bt.size(1) * page, "cos/sin seqlen must be at least the seqlen of KV cache");
+        CHECK_SHAPE(sin, cos.size(0), rotary_dim / 2);
+        TORCH_CHECK(cos.scalar_type() == q.scalar_type() && sin.scalar_type() == q.scalar_type(),
+                    "rotary_cos/sin must have the same dtype as query");
+        q_rot = torch::empty_like(qc);
+    }
+    auto seqlens_new = torch::empty_like(seqlens_k);
+    fmha_kvcache_append_fp8(qc.data_ptr(), q_rot.defined() ? q_rot.data_ptr() : nullptr,
+                            kcache.data_ptr(), vcache.data_ptr(), knc.data_ptr(), vnc.data_ptr(),
+                            seqlen_new, bt.data_ptr(), (int)bt.stride(0), page, seqlens_k.data_ptr(),
+                            seqlens_new.data_ptr(), cos.defined() ? cos.data_ptr() : nullptr,
+                            sin.defined() ? sin.data_ptr() : nullptr, rotary_dim, is_rotary_interleaved,
+                            q_rotary_per_token, batch_size, seqlen_q, num_heads, num_heads_k, d,
+                            dt == torch::kFloat16, cur_stream(), k_scale, v_scale);
+    raise_if_failed("kvcache_append_fp8");
+    return {seqlens_new, q_rot.defined() ? q_rot : qc};
 }
 
 PYBIND11_MODULE(paged_attn, m) {
@@ -835,5 +1036,11 @@ PYBIND11_MODULE(paged_attn, m) {
     m.def("fwd_kvcache_fp8", &mha_fwd_kvcache_fp8, "Paged decode over an fp8 e4m3fn K/V cache");
     m.def("fwd_fp8", &mha_fwd_fp8, "Forward pass over fp8 e4m3fn q/k/v (fp8 MFMA)");
     m.def("varlen_fwd_fp8", &mha_varlen_fwd_fp8, "Forward pass over packed fp8 e4m3fn q/k/v (variable length)");
+    m.def("quantize_fp8", &mha_quantize_fp8, "bf16 / fp16 -> fp8 e4m3fn with its descale(s)", py::arg("x"),
+          py::arg("granularity"), py::arg("group"), py::arg("cu_seqlens") = py::none(),
+          py::arg("max_seqlen") = 0);
+    m.def("fwd_fp8_ex", &mha_fwd_fp8_ex, "fp8 forward with device descales (one element or [b, hk])");
+    m.def("varlen_fwd_fp8_ex", &mha_varlen_fwd_fp8_ex, "Packed fp8 forward with device descales");
+    m.def("kvcache_append_fp8", &mha_kvcache_append_fp8, "Append new K/V (+ rotary) into an fp8 e4m3fn paged cache");
     m.def("version",[]() { return std::string(fmha_version()); });
 }

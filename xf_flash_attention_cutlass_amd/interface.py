@@ -67,21 +67,85 @@ def flash_attn_func(q, k, v, dropout_p=0.0, causal=False, window_size=(-1, -1), 
     return out if not return_attn_probs else (out, lse, s_dmask)
 
 
+_GRANULARITY = {"tensor": 0, "head": 1}
+
+
+def quantize_fp8(x, granularity="tensor", group=1, cu_seqlens=None, *, max_seqlen=None):
+    """bf16 / fp16 x [b, s, h, d] (any strides, last dimension contiguous) or, with cu_seqlens
+    (int32 [b + 1]), packed [total, h, d] -> (x8, descale): x8 float8_e4m3fn of x's shape,
+    descale fp32 with x ~ x8 * descale.  One HIP call of two passes over x, no host sync.
+
+    granularity "tensor": one scale, descale [1]; "head": one per (batch or sequence, group of
+    `group` consecutive heads), descale [b, h // group] - group = h // hk for q (the fp8 forward
+    takes q's descale per kv head), 1 for k and v.  descale = amax / 448 (1.0 for an all-zero or
+    empty set).  max_seqlen (packed): the longest sequence if known; the default bounds it by
+    `total`, so no length is read on the host."""
+    if granularity not in _GRANULARITY:
+        raise ValueError(f"granularity must be 'tensor' or 'head' (got {granularity!r})")
+    x8, descale = paged_attn.quantize_fp8(x, _GRANULARITY[granularity], int(group), cu_seqlens,
+                                          0 if max_seqlen is None else int(max_seqlen))
+    return x8, descale
+
+
+def _device_descales(*ds):
+    """True when any descale is a CUDA tensor: then all three go to the _ex entries as device
+    tensors (one element or [batch, heads_k]) and nothing is read on the host."""
+    return any(isinstance(x, torch.Tensor) and x.is_cuda for x in ds)
+
+
+def _as_device_descale(x, device):
+    if x is None:
+        return torch.ones(1, dtype=torch.float32, device=device)
+    if isinstance(x, torch.Tensor):
+        return x.to(device=device, dtype=torch.float32)
+    return torch.full((1,), float(x), dtype=torch.float32, device=device)
+
+
+def _quantize_qkv(q, k, v, quantize, descales, cu_q=None, cu_k=None, max_q=None, max_k=None):
+    """quantize= of the fp8 functions: bf16 / fp16 q, k, v -> fp8 with device descales (q's per kv
+    head under "head")."""
+    if quantize not in _GRANULARITY:
+        raise ValueError(f"quantize must be None, 'tensor' or 'head' (got {quantize!r})")
+    if any(x is not None for x in descales):
+        raise ValueError("quantize= computes the descales: do not pass q/k/v_descale with it")
+    if q.dtype not in (torch.bfloat16, torch.float16) or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise TypeError("quantize= needs bf16 or fp16 q, k and v of one dtype")
+    group = q.shape[-2] // k.shape[-2]
+    q8, qd = quantize_fp8(q, quantize, group, cu_q, max_seqlen=max_q)
+    k8, kd = quantize_fp8(k, quantize, 1, cu_k, max_seqlen=max_k)
+    v8, vd = quantize_fp8(v, quantize, 1, cu_k, max_seqlen=max_k)
+    return q8, k8, v8, qd, kd, vd
+
+
 def flash_attn_fp8_func(q, k, v, q_descale=None, k_descale=None, v_descale=None,
                         softmax_scale=None, causal=False, window_size=(-1, -1),
-                        out_dtype=torch.bfloat16, return_lse=False):
-    """fp8 e4m3fn q [b, sq, h, 128], k/v [b, sk, hk, 128] with per-tensor descales (floats or
-    one-element tensors; None = 1.0): both GEMMs on the gfx950 fp8 MFMA.  Forward only."""
+                        out_dtype=torch.bfloat16, return_lse=False, *, quantize=None):
+    """fp8 e4m3fn q [b, sq, h, 128], k/v [b, sk, hk, 128] with descales (value = stored x
+    descale; None = 1.0): both GEMMs on the gfx950 fp8 MFMA.  Forward only.
+
+    Descales: Python floats or CPU tensors (one element) are passed by value; CUDA tensors of one
+    element or of shape [b, hk] (FA3's layout; q's per kv head) are read by the kernel, with no
+    host sync.  quantize="tensor" | "head": q, k, v are bf16 / fp16 and are quantised first
+    (`quantize_fp8`, three calls), all on the device."""
     if q.requires_grad or k.requires_grad or v.requires_grad:
         raise NotImplementedError("the fp8 forward has no backward")
     if out_dtype not in (torch.bfloat16, torch.float16):
         raise ValueError("out_dtype must be bfloat16 or float16")
     if softmax_scale is None:
         softmax_scale = q.shape[-1] ** (-0.5)
+    if quantize is not None:
+        q, k, v, q_descale, k_descale, v_descale = _quantize_qkv(
+            q, k, v, quantize, (q_descale, k_descale, v_descale))
 
     def _f(x):
         return 1.0 if x is None else float(x)
     q, k, v = (_maybe_contiguous(x) for x in (q, k, v))
+    if _device_descales(q_descale, k_descale, v_descale):
+        qd, kd, vd = (_as_device_descale(x, q.device) for x in (q_descale, k_descale, v_descale))
+        out, lse = paged_attn.fwd_fp8_ex(q, k, v, None, qd, kd, vd, softmax_scale, causal,
+                                         int(window_size[0]), int(window_size[1]),
+                                         out_dtype == torch.float16)
+        return (out, lse) if return_lse else out
     out, lse = paged_attn.fwd_fp8(q, k, v, None, _f(q_descale), _f(k_descale), _f(v_descale),
                                   softmax_scale, causal, int(window_size[0]), int(window_size[1]),
                                   out_dtype == torch.float16)
@@ -129,11 +193,14 @@ class _FlashAttnVarlenFunc(torch.autograd.Function):
 def flash_attn_varlen_fp8_func(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k,
                                q_descale=None, k_descale=None, v_descale=None,
                                softmax_scale=None, causal=False, window_size=(-1, -1),
-                               out_dtype=torch.bfloat16, return_lse=False, seqused_k=None):
+                               out_dtype=torch.bfloat16, return_lse=False, seqused_k=None, *,
+                               quantize=None):
     """Packed fp8 e4m3fn q [total_q, h, 128], k/v [total_k, hk, 128], cu_seqlens int32 [b + 1],
-    per-tensor descales (floats or one-element tensors; None = 1.0), optional seqused_k int32
-    [b]: the fp8-MFMA forward over variable-length sequences.  Forward only; the LSE is
-    [h, total_q]."""
+    descales (None = 1.0), optional seqused_k int32 [b]: the fp8-MFMA forward over
+    variable-length sequences.  Forward only; the LSE is [h, total_q].
+
+    Descales and quantize= as `flash_attn_fp8_func`; a [b, hk] descale is indexed by (sequence,
+    kv head)."""
     if q.requires_grad or k.requires_grad or v.requires_grad:
         raise NotImplementedError("the fp8 forward has no backward")
     if out_dtype not in (torch.bfloat16, torch.float16):
@@ -141,9 +208,21 @@ def flash_attn_varlen_fp8_func(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q
     if softmax_scale is None:
         softmax_scale = q.shape[-1] ** (-0.5)
 
+    if quantize is not None:
+        q, k, v, q_descale, k_descale, v_descale = _quantize_qkv(
+            q, k, v, quantize, (q_descale, k_descale, v_descale), cu_seqlens_q, cu_seqlens_k,
+            max_seqlen_q, max_seqlen_k)
+
     def _f(x):
         return 1.0 if x is None else float(x)
     q, k, v = (_maybe_contiguous(x) for x in (q, k, v))
+    if _device_descales(q_descale, k_descale, v_descale):
+        qd, kd, vd = (_as_device_descale(x, q.device) for x in (q_descale, k_descale, v_descale))
+        out, lse = paged_attn.varlen_fwd_fp8_ex(q, k, v, None, cu_seqlens_q, cu_seqlens_k, seqused_k,
+                                                int(max_seqlen_q), int(max_seqlen_k), qd, kd, vd,
+                                                softmax_scale, causal, int(window_size[0]),
+                                                int(window_size[1]), out_dtype == torch.float16)
+        return (out, lse) if return_lse else out
     out, lse = paged_attn.varlen_fwd_fp8(q, k, v, None, cu_seqlens_q, cu_seqlens_k, seqused_k,
                                          int(max_seqlen_q), int(max_seqlen_k), _f(q_descale),
                                          _f(k_descale), _f(v_descale), softmax_scale, causal,
@@ -209,7 +288,11 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
     embedding on k and q, interleaved = GPT-J pairs), then attended over.
 
     Extension: a `torch.float8_e4m3fn` paged cache is read natively (dequantised in-kernel as
-    fp8 * k_scale / v_scale); it requires `block_table` and `cache_seqlens`."""
+    fp8 * k_scale / v_scale); it requires `block_table` and `cache_seqlens`.  With k/v (bf16 /
+    fp16, q's dtype) the new rows are quantised into it first: K after its rotary in fp32, times
+    1 / k_scale, clamped to +-448 and rounded once to e4m3; V times 1 / v_scale likewise
+    (k_scale, v_scale positive floats); rotary_cos/sin and rotary_interleaved as for a bf16 cache.
+    ALiBi and softcap are not supported with an fp8 cache."""
     assert k_cache.stride(-1) == 1, "k_cache must have contiguous last dimension"
     assert v_cache.stride(-1) == 1, "v_cache must have contiguous last dimension"
     if cache_leftpad is not None and (block_table is not None or k_cache.dtype == torch.float8_e4m3fn):
@@ -219,13 +302,24 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
     if softmax_scale is None:
         softmax_scale = q.shape[-1] ** (-0.5)
     if k_cache.dtype == torch.float8_e4m3fn:
-        if block_table is None or cache_seqlens is None or k is not None or alibi_slopes is not None \
-                or softcap > 0:
+        if block_table is None or cache_seqlens is None or alibi_slopes is not None or softcap > 0:
             raise NotImplementedError("fp8 K/V cache: paged decode with block_table and "
-                                      "cache_seqlens only")
+                                      "cache_seqlens only (no ALiBi, no softcap)")
+        if (k is None) != (v is None):
+            raise ValueError("If key is supplied, value must also be passed in")
+        if k is None and (rotary_cos is not None or rotary_sin is not None):
+            raise ValueError("If rotary cos/sin are provided, new key / value to be appended to "
+                             "KV cache must also be provided")
         if isinstance(cache_seqlens, int):
             cache_seqlens = torch.full((q.shape[0],), cache_seqlens, dtype=torch.int32,
                                        device=q.device)
+        if k is not None:
+            # append (+ rotary on k and q) into the fp8 cache, then attend over the grown lengths
+            per_token = bool(causal) or int(window_size[0]) >= 0 or int(window_size[1]) >= 0
+            cache_seqlens, q = paged_attn.kvcache_append_fp8(
+                q, k_cache.view(torch.uint8), v_cache.view(torch.uint8), k, v,
+                _maybe_contiguous(cache_seqlens), block_table, rotary_cos, rotary_sin,
+                float(k_scale), float(v_scale), rotary_interleaved, per_token)
         out, lse = paged_attn.fwd_kvcache_fp8(q, k_cache.view(torch.uint8),
                                               v_cache.view(torch.uint8), cache_seqlens,
                                               block_table, float(k_scale), float(v_scale),
