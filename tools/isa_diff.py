@@ -22,8 +22,8 @@ def units(tree):
     tus = [(f"fmha_{kind}_hd{hd}_{dt}", f"fmha_{kind}.hip",
             [f"-DXFA_HD={hd}", f"-DXFA_DTN={dt}", f"-DXFA_DT_BF16={int(dt == 'bf16')}"])
            for hd, dt in b.VARIANTS for kind in ("fwd", "bwd")]
-    tus += [("fmha_append", "fmha_append.hip", []), ("fmha_fwd_fp8", "fmha_fwd_fp8.hip", []),
-            ("fmha_api", "fmha_api.cpp", [])]
+    tus += [("fmha_append", "fmha_append.hip", []), ("fmha_quant", "fmha_quant.hip", []),
+            ("fmha_fwd_fp8", "fmha_fwd_fp8.hip", []), ("fmha_api", "fmha_api.cpp", [])]
     tus += [(n + "+variants", src, d + ["-DXFA_VARIANTS=1"]) for n, src, d in tus if n + ".o" in b.VARIANT_TUS]
     return b, tus
 

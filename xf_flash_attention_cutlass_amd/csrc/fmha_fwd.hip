@@ -100,7 +100,7 @@ static hipError_t launch_fwd_nw(const FwdParams& p, hipStream_t st) {
     const bool mask = p.wl >= 0 || p.wr >= 0;
     // FEAT: per-score transforms (ALiBi, softcap) and the paged / fp8 staging paths
     const bool feat = p.alibi || p.softcap_pre > 0.f || p.block_table || p.kv_fp8 || p.drop;
-    const FwdPlan s = plan_fwd(p, NW * 32, p.num_cus * p.persist_per_cu, p.num_splits, kQueueXcd);
+    const FwdPlan s = plan_fwd(p, NW * 32, p.num_cus * p.persist_per_cu, p.num_splits, kFwdQueue);
     const size_t smem = (size_t)(fwd_nbuf(HD) * 2 * kBlockN * HD * 2);
     void (*kern)(const FwdParams) =
         mask ? (feat ? fmha_fwd_kernel<HD, T, NW, true, true> : fmha_fwd_kernel<HD, T, NW, true, false>)
@@ -134,7 +134,7 @@ static bool fwd4_eligible(const FwdParams& p) {
 
 // 8-wave ping-pong forward (fmha_fwdpp_kernel.h): the same items, schedules and eligibility
 static hipError_t launch_fwdpp(const FwdParams& p, hipStream_t st) {
-    const FwdPlan s = plan_fwd(p, kFwdppRows, p.num_cus, 1, kQueueXcd);
+    const FwdPlan s = plan_fwd(p, kFwdppRows, p.num_cus, 1, kFwdppQueue);
     constexpr bool BF = std::is_same<elem_t, __bf16>::value;
     // fwd_w4 = 3: the body on the 16x16x32 MFMA shape (tools/gen_fwdpp16.py); 4 (auto, the
     // default): 16x16x32 where no row has a right window (causal / local rows: 32x32x16), the
@@ -154,7 +154,7 @@ static hipError_t launch_fwd4(const FwdParams& p, hipStream_t st) {
 #else
     constexpr bool BF = std::is_same<elem_t, __bf16>::value;
     allow_lds<fmha_fwd4_kernel<BF>>(p.device, kFwd4Smem);
-    return launch_planned("fmha_fwd4_kernel", fmha_fwd4_kernel<BF>, plan_fwd(p, kFwd4Rows, p.num_cus, 1, kQueueXcd),
+    return launch_planned("fmha_fwd4_kernel", fmha_fwd4_kernel<BF>, plan_fwd(p, kFwd4Rows, p.num_cus, 1, kFwd4Queue),
                           256, kFwd4Smem, st);
 #endif
 }

@@ -1,5 +1,5 @@
 // fmha_fwd_fp8.hip — launches of the fp8 (e4m3fn) Q/K/V forward (fmha_fwd_fp8_kernel.h), D = 128,
-// bf16 or fp16 output; persistent XCD-paired grid as the bf16 forward.
+// bf16 or fp16 output; the item schedules are planned by plan_fwd and walked by fwd_walk.
 #include <algorithm>
 
 #include "fmha_fwd_fp8_kernel.h"
@@ -20,7 +20,7 @@ template <bool F16, bool VARLEN, bool DSC>
 static hipError_t launch_fp8_w4(const FwdParams& p, hipStream_t st) {
     allow_lds<fmha_fwd8w_kernel<F16, VARLEN, DSC>>(p.device, kFwd8wSmem);
     return launch_planned("fmha_fwd8w_kernel", fmha_fwd8w_kernel<F16, VARLEN, DSC>,
-                          plan_fwd(p, kFwd8wRows, p.num_cus, 1, kQueueXcd), 256, kFwd8wSmem, st);
+                          plan_fwd(p, kFwd8wRows, p.num_cus, 1, kFwd8wQueue), 256, kFwd8wSmem, st);
 }
 
 #if XFA_VARIANTS
@@ -29,7 +29,7 @@ template <bool F16, bool DSC>
 static hipError_t launch_fp8_pp(const FwdParams& p, hipStream_t st) {
     allow_lds<fmha_fwd8pp_kernel<F16, DSC>>(p.device, kFwd8ppSmem);
     return launch_planned("fmha_fwd8pp_kernel", fmha_fwd8pp_kernel<F16, DSC>,
-                          plan_fwd(p, kFwd8ppRows, p.num_cus, 1, kQueueXcd), 512, kFwd8ppSmem, st);
+                          plan_fwd(p, kFwd8ppRows, p.num_cus, 1, kFwd8ppQueue), 512, kFwd8ppSmem, st);
 }
 #endif
 
@@ -42,7 +42,7 @@ static hipError_t launch_fp8_t(const FwdParams& p, hipStream_t st) {
     constexpr int NW = 8;
     const bool mask = p.wl >= 0 || p.wr >= 0;
     const FwdPlan s = plan_fwd(p, NW * 32, p.num_cus * p.persist_per_cu, 1,
-                               VARLEN && p.work_ctr ? kQueueRagged : kQueueStatic);
+                               p.work_ctr ? kFwdFp8Queue<VARLEN> : kQueueStatic);
     const size_t smem = 8 * (size_t)kFp8Tile;     // K and V, four buffers each
     allow_lds<fmha_fwd_fp8_kernel<T, NW, true, VARLEN, DSC>, fmha_fwd_fp8_kernel<T, NW, false, VARLEN, DSC>>(p.device, (int)smem);
     return launch_planned("fmha_fwd_fp8_kernel<8 waves>",

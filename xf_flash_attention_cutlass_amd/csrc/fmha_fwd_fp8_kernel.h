@@ -8,8 +8,8 @@
 // descales, FA3-style), with P rounded to e4m3 for the PV product as the reference rounds P to
 // the input dtype (flash_fwd_kernel_hip.h `convert_type`).
 //
-// Structure (one workgroup = NW waves x 32 query rows, persistent XCD-paired items, as
-// fmha_fwd_kernel.h):
+// Structure (one workgroup = NW waves x 32 query rows; the item schedules are
+// fmha_fwd_sched.h's):
 //  * S^T = K Q^T: the 32x32x64 A operand is 32 bytes of one key row per lane (d = 64 s + 32 h
 //    .. +31 for lane half h), B the same bytes of one query row (held in registers per item).
 //    A and B use the same (lane half, byte) -> k map (verified with one-hot operands,
@@ -24,9 +24,12 @@
 //  * K / V tiles (64 keys x 128 B) arrive by LDS-DMA into a double buffer; the images XOR the
 //    16-byte chunk by the row so both the 32-byte row reads of K and the transposed reads of V
 //    are bank-conflict-free (K: chunk ^ ((row >> 1) & 7); V: chunk ^ (((row >> 1) & 3) << 1)).
+// This file's own: the compiler-scheduled item body (fwd8_item).  The loop over a workgroup's
+// items is fmha_fwd_sched.h's fwd_walk.
 #pragma once
 
 #include "fmha_common.h"
+#include "fmha_fwd_sched.h"
 
 namespace xfa {
 
@@ -553,51 +556,15 @@ __device__ __forceinline__ void fwd8_item(const FwdParams& p, char* smem, const 
             empty ? INFINITY : (m_sc + __log2f(l_full)) * kLn2;
 }
 
+// The schedules of a dense launch are static; a packed one may also take one dynamic queue, last
+// row blocks first (for plan_fwd and fwd_walk).
+template <bool VARLEN>
+constexpr FwdQueue kFwdFp8Queue = VARLEN ? kQueueRagged : kQueueStatic;
+
 template <typename T, int NW, bool MASK, bool VARLEN, bool DSC>
 __global__ void __launch_bounds__(NW * 64, 2) fmha_fwd_fp8_kernel(const FwdParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    __shared__ int s_claim[2];
-    const int nbh = p.b * p.hk;
-    const int g = gridDim.x;
-    for (int k = 0;; ++k) {
-        int bh, m_block;
-        if (VARLEN && p.persistent == 3) {   // varlen: one dynamic item queue, last row blocks first
-            if (threadIdx.x == 0) s_claim[k & 1] = atomicAdd(p.work_ctr + 2, 1);
-            __syncthreads();
-            const int q = __builtin_amdgcn_readfirstlane(s_claim[k & 1]);
-            if (q >= nbh * p.n_mblocks) break;
-            bh = q % nbh;
-            m_block = p.n_mblocks - 1 - q / nbh;
-        } else if (p.persistent == 2) {  // XCD-grouped (n-1-i, i) row-block pairs (fmha_fwd_kernel.h)
-            const int nm = p.n_mblocks, npair = (nm + 1) >> 1;
-            const int bid = (int)blockIdx.x;
-            const int v = (bid & 7) * (g >> 3) + (bid >> 3);
-            const int q = (k >> 1) * g + v;
-            if (q >= nbh * npair) break;
-            bh = q / npair;
-            const int i = q - bh * npair;
-            m_block = (k & 1) ? i : nm - 1 - i;
-            if ((k & 1) && i == nm - 1 - i) continue;
-        } else if (p.persistent) {
-            const int lin = k * g + ((k & 1) ? g - 1 - (int)blockIdx.x : (int)blockIdx.x);
-            if (lin >= nbh * p.n_mblocks) break;
-            bh = lin % nbh;
-            m_block = p.n_mblocks - 1 - lin / nbh;
-        } else {
-            if (k > 0) break;
-            bh = blockIdx.x;
-            m_block = gridDim.y - 1 - blockIdx.y;
-        }
-        fwd8_item<T, NW, MASK, VARLEN, DSC>(p, smem, bh, m_block);
-    }
-    if (VARLEN && p.persistent == 3 && threadIdx.x == 0) {
-        // the grid's last workgroup resets the queue counters for the next launch on the stream
-        const int total = (int)(gridDim.x * gridDim.y * gridDim.z);
-        if (atomicAdd(p.work_ctr + 1, 1) == total - 1) {
-            for (int i = 2; i < 10; ++i) atomicExch(p.work_ctr + i, 0);
-            atomicExch(p.work_ctr + 1, 0);
-        }
-    }
+    fwd_walk<kFwdFp8Queue<VARLEN>>(p, [&](int bh, int m_block) { fwd8_item<T, NW, MASK, VARLEN, DSC>(p, smem, bh, m_block); });
 }
 
 }  // namespace xfa

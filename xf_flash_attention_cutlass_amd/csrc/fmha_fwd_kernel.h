@@ -20,9 +20,12 @@
 //    ds_read_b64_tr_b16 — both conflict-free on the same image;
 //  * masking runs only on the tiles that cross a window edge; tiles a wave cannot see are
 //    skipped by that wave (wave-uniform branch); the heaviest causal row blocks launch first.
+// This file's own: the item body (fwd_item), the dropout key write-back and the split-KV
+// combines.  The item schedules and the loop over a workgroup's items are fmha_fwd_sched.h's.
 #pragma once
 
 #include "fmha_common.h"
+#include "fmha_fwd_sched.h"
 
 #include <type_traits>
 
@@ -745,64 +748,12 @@ __device__ __forceinline__ void fwd_item(const FwdParams& p, char* smem, const i
     }
 }
 
-// Grid: either one workgroup per item (grid = (b*hk, m_blocks, splits), heaviest causal row
-// blocks dispatched first), or persistent (p.persistent: grid = (resident workgroups, 1,
-// splits)), each workgroup walking items in a heaviest-first boustrophedon order so the
-// causal work per workgroup balances, and one item's O-store tail overlaps the next item's
-// prologue loads instead of a workgroup boundary.
+// Grid: one workgroup per item or persistent, as plan_fwd chose; fwd_walk (fmha_fwd_sched.h)
+// runs this workgroup's items.
+constexpr FwdQueue kFwdQueue = kQueueXcd;   // for plan_fwd and fwd_walk
 template <int HD, typename T, int NW, bool MASK, bool FEAT>
 __global__ void __launch_bounds__(NW * 64, fwd_waves_per_simd(HD)) fmha_fwd_kernel(const FwdParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    __shared__ int s_claim[2];
-    const int nbh = p.b * p.hk;
-    const int g = gridDim.x;
-    for (int k = 0;; ++k) {        // one call site: the item body is inlined once
-        int bh, m_block;
-        if (p.persistent == 2) {
-            // XCD-grouped pairs: pair i of (b, kv head) = row blocks (n-1-i, i), equal causal
-            // work; consecutive pairs of one (b, kv head) run at the same time on the CUs of
-            // one XCD (workgroup bid sits on XCD bid % 8), so they share that XCD's L2 for K/V
-            const int nm = p.n_mblocks, npair = (nm + 1) >> 1;
-            const int bid = (int)blockIdx.x;
-            const int v = (bid & 7) * (g >> 3) + (bid >> 3);
-            const int q = (k >> 1) * g + v;
-            if (q >= nbh * npair) break;
-            bh = q / npair;
-            const int i = q - bh * npair;
-            m_block = (k & 1) ? i : nm - 1 - i;
-            if ((k & 1) && i == nm - 1 - i) continue;   // odd count: the middle block is alone
-        } else if (p.persistent == 3) {
-            // dynamic queue: claim the next item (heaviest row block first, then (b, kv head))
-            // from a device counter, so ragged varlen items balance as workgroups finish; the
-            // claim slot alternates so a fast wave's next claim cannot overwrite it unread
-            // p.xcd_queues (default): one queue per XCD over the units bh = x (mod 8), unit-major,
-            // so a unit's row blocks run together on one XCD and share its L2 for K/V (workgroup
-            // b sits on XCD b % 8; slots % 8 == 0 and nbh >= 8 are checked on the host)
-            const int x = p.xcd_queues ? (int)(blockIdx.x & 7) : 0;
-            const int nq = p.xcd_queues ? (nbh - x + 7) >> 3 : nbh;
-            if (threadIdx.x == 0) s_claim[k & 1] = atomicAdd(p.work_ctr + 2 + x, 1);
-            __syncthreads();
-            const int q = s_claim[k & 1];
-            if (q >= nq * p.n_mblocks) break;
-            if (p.xcd_queues) {     // unit-major: an XCD's workgroups share a unit's K/V in L2
-                bh = x + 8 * (q / p.n_mblocks);
-                m_block = p.n_mblocks - 1 - q % p.n_mblocks;
-            } else {                // heaviest row block first over all units
-                bh = q % nq;
-                m_block = p.n_mblocks - 1 - q / nq;
-            }
-        } else if (p.persistent) {
-            const int lin = k * g + ((k & 1) ? g - 1 - (int)blockIdx.x : (int)blockIdx.x);
-            if (lin >= nbh * p.n_mblocks) break;
-            bh = lin % nbh;
-            m_block = p.n_mblocks - 1 - lin / nbh;
-        } else {
-            if (k > 0) break;
-            bh = blockIdx.x;
-            m_block = gridDim.y - 1 - blockIdx.y;
-        }
-        fwd_item<HD, T, NW, MASK, FEAT>(p, smem, bh, m_block, blockIdx.z);
-    }
     // the key this launch used, for the backward (the reference writes params.rng_state the
     // same way, flash_fwd_kernel_hip.h); one lane of one workgroup
     if (FEAT && p.drop && p.rng_out && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 &&
@@ -812,15 +763,7 @@ __global__ void __launch_bounds__(NW * 64, fwd_waves_per_simd(HD)) fmha_fwd_kern
         p.rng_out[0] = (int64_t)dseed;
         p.rng_out[1] = (int64_t)doff;
     }
-    // dynamic queue: every workgroup has made its last (failed) claim when it gets here; the
-    // last one to finish resets the counters for the next launch on this stream
-    if (p.persistent == 3 && threadIdx.x == 0) {
-        const int total = (int)(gridDim.x * gridDim.y * gridDim.z);
-        if (atomicAdd(p.work_ctr + 1, 1) == total - 1) {
-            for (int i = 2; i < 10; ++i) atomicExch(p.work_ctr + i, 0);
-            atomicExch(p.work_ctr + 1, 0);
-        }
-    }
+    fwd_walk<kFwdQueue>(p, [&](int bh, int m_block) { fwd_item<HD, T, NW, MASK, FEAT>(p, smem, bh, m_block, blockIdx.z); });
 }
 
 // Split-KV combine: lse = log sum_s exp(lse_s); O = sum_s exp(lse_s - lse) O_s

@@ -13,11 +13,13 @@
 //    VALU / DMA (tools/gen_fwdpp.py generates the item body, fmha_fwdpp_body.h);
 //  * no row max in the loop (P against tile 0's max, a rare redo past 2^fwd_slack), as the
 //    4-wave kernel.
-// This file computes the item geometry (SRDs, per-lane offsets, the wave's last / first-masked
-// tiles) and runs the persistent item schedules of fmha_fwd4_kernel.h.
+// This file's own: the left-window extras of the 32x32x16 body (T0, l_w, f_w), the LDS images
+// and DMA offsets, the 16x16x32 body's operands, the paged descriptors and the score-feature
+// scalars.  The item geometry is fmha_fwd_geom.h's, the item schedules fmha_fwd_sched.h's.
 #pragma once
 
-#include "fmha_common.h"
+#include "fmha_fwd_geom.h"
+#include "fmha_fwd_sched.h"
 #ifdef XFA_FWDPP_BODY
 #include XFA_FWDPP_BODY         // an A/B variant of the generated body (tools/fwdpp_variants.sh)
 #else
@@ -32,6 +34,7 @@
 namespace xfa {
 
 constexpr int kFwdppRows = 256;            // query rows per workgroup (8 waves x 32)
+constexpr FwdQueue kFwdppQueue = kQueueXcd; // for plan_fwd and fwd_walk
 
 #ifdef XFA_FWDPP_STAMPS
 // Diagnostic build only (tools/fwdpp_variants.sh "name=--stamps", tools/pp_stamps.py): each wave
@@ -47,16 +50,6 @@ static __device__ unsigned g_fwdpp_stamps[8 * 8];
 constexpr int kFwdppTile = 128 * 64 * 2;   // bytes of one K (or V) tile at D = 128
 constexpr int kFwdppVReg = kFwdppRing * kFwdppTile;      // the V ring follows the K ring
 constexpr int kFwdppSmem = 2 * kFwdppRing * kFwdppTile;  // (kFwdppRing: the generated body's)
-
-__device__ __forceinline__ i32x4 fwdpp_srd(const void* base, uint32_t bytes) {
-    const uint64_t a = (uint64_t)base;
-    i32x4 r;
-    r[0] = __builtin_amdgcn_readfirstlane((int)(uint32_t)a);
-    r[1] = __builtin_amdgcn_readfirstlane((int)(uint32_t)(a >> 32) & 0xFFFF);
-    r[2] = __builtin_amdgcn_readfirstlane((int)bytes);
-    r[3] = 0x00020000;
-    return r;
-}
 
 // The 16x16x32 body's image: kv_off with the chunk XORed by ppx16(row bits 2-3) = 0, 2, 3, 1
 // instead of the bits themselves.  Its K row reads (16 lanes of a ds_read_b128 bank group cover
@@ -79,82 +72,56 @@ __device__ __forceinline__ void fwdpp_item(const FwdParams& p, char* smem, const
 
     const int bidx = bh / p.hk;
     const int hk_i = bh - bidx * p.hk;
-    int q_off = 0, sq = p.seqlen_q, k_off = 0, sk = p.seqlen_k;
-    if (p.cu_seqlens_q) { q_off = p.cu_seqlens_q[bidx]; sq = p.cu_seqlens_q[bidx + 1] - q_off; }
-    if (p.cu_seqlens_k) { k_off = p.cu_seqlens_k[bidx]; sk = p.cu_seqlens_k[bidx + 1] - k_off; }
-    if (p.seqused_k) sk = p.seqused_k[bidx];
+    // varlen / seqused_k: this sequence's rows of the packed tensors
+    const SeqRange sr = seq_range<true>(p, bidx);
+    const int q_off = sr.q_off, sq = sr.sq, k_off = sr.k_off, sk = sr.sk;
     const int G = p.group;
     const int rows_total = sq * G;
     const int row0 = m_block * kFwdppRows;
     if (row0 >= rows_total) return;    // workgroup-uniform
     const int diag = sk - sq;
-    auto lim_r = [&](int pos) { return p.wr >= 0 ? min(sk, pos + diag + p.wr + 1) : sk; };
-
+    const KeyLimit lim_r{sk, diag, p.wr};
     // left window (wl >= 0, the 32x32 body only): keys [lim_l(pos), lim_r(pos))
     auto lim_l = [&](int pos) { return p.wl >= 0 ? max(0, pos + diag - p.wl) : 0; };
 
     // key tiles of the workgroup: [T0, T0 + ntl) — T0 > 0 when the item's first row's window
     // starts past key 0; the body counts tiles from T0 (K / V bases, limits shifted by 64 T0)
-    const int pos_hi = (min(row0 + kFwdppRows, rows_total) - 1) / G;
-    const int n_hi = sk > 0 ? lim_r(pos_hi) : 0;
-    const int ntl_abs = n_hi > 0 ? (n_hi + kBlockN - 1) / kBlockN : 0;
+    const int ntl_abs = key_tiles(lim_r, (min(row0 + kFwdppRows, rows_total) - 1) / G);
     const int T0 = (M16 || ntl_abs <= 0) ? 0 : min(lim_l(row0 / G) / kBlockN, ntl_abs - 1);
     const int ntl = ntl_abs - T0;
 
     // this wave: rows wrow0 .. wrow0 + 31; last tile t_w; tiles >= e_w need the right edge mask,
-    // tiles < l_w the left one
+    // tiles < l_w the left one; before tile f_w no row of the wave sees a key
     const int wrow0 = row0 + 32 * wave;
-    int t_w = -1, e_w = 1 << 30, l_w = 0, f_w = 0;
-    if (wrow0 < rows_total && ntl > 0) {
-        const int wp_lo = wrow0 / G, wp_hi = (min(wrow0 + 32, rows_total) - 1) / G;
-        const int lr_hi = lim_r(wp_hi), lr_lo = lim_r(wp_lo);
-        t_w = lr_hi > 0 ? min(ntl_abs, (lr_hi + kBlockN - 1) / kBlockN) - 1 - T0 : -1;
-        t_w = max(t_w, -1);
-        e_w = (lr_lo > 0 ? lr_lo / kBlockN : 0) - T0;
-        l_w = (lim_l(wp_hi) + kBlockN - 1) / kBlockN - T0;
-        f_w = lim_l(wp_lo) / kBlockN - T0;     // tiles before it: no row of the wave sees a key
+    int t_w, e_w, l_w = 0, f_w = 0;
+    if (wave_tiles<32>(lim_r, wrow0, rows_total, G, ntl_abs, t_w, e_w)) {
+        t_w = max(t_w - T0, -1);
+        e_w -= T0;
+        l_w = (lim_l((min(wrow0 + 32, rows_total) - 1) / G) + kBlockN - 1) / kBlockN - T0;
+        f_w = lim_l(wrow0 / G) / kBlockN - T0;
     }
     t_w = __builtin_amdgcn_readfirstlane(t_w);
     e_w = __builtin_amdgcn_readfirstlane(e_w);
     l_w = __builtin_amdgcn_readfirstlane(l_w);
     f_w = __builtin_amdgcn_readfirstlane(f_w);
 
-    // this lane's row
-    const int row = wrow0 + lr;
-    const bool ok = row < rows_total;
-    const int pos = ok ? row / G : 0;
-    const int head = hk_i * G + (ok ? row - pos * G : 0);
-    const int qoff = ok ? (pos * (int)p.q_row + head * (int)p.q_head) * 2 + 16 * hh : kOOB;
-    const int ooff = ok ? (pos * (int)p.o_row + head * (int)p.o_head) * 2 + 16 * hh : kOOB;
-    const int loff = (ok && hh == 0) ? (int)(head * p.lse_head + pos) * 4 : kOOB;
-    // key limits of tile 0 (absolute tile T0) for this lane's keys (offset 4*hh folded in);
-    // other rows: none
-    const int lim = (ok ? lim_r(pos) : sk) - 4 * hh - kBlockN * T0;
+    // this lane's row; its key limits count from tile 0 of the body (absolute tile T0)
+    const LaneRow lrow = lane_row<2>(p, lim_r, wrow0 + lr, rows_total, hk_i, 16 * hh, 16 * hh, hh);
+    const bool ok = lrow.ok;
+    const int pos = lrow.pos, head = lrow.head, qoff = lrow.qoff, ooff = lrow.ooff, loff = lrow.loff;
+    const int lim = lrow.lim - kBlockN * T0;
     const int liml = (ok ? lim_l(pos) : 0) - 4 * hh - kBlockN * T0;
     const int wid = max(lim - liml, 0);
 
     if (ntl <= 0) {
-        // no visible key for any row: O = 0, LSE = +inf (the reference's empty-row output)
-        typedef __attribute__((ext_vector_type(4))) unsigned u4;
-        char* oseq = reinterpret_cast<char*>(p.o) + ((int64_t)bidx * p.o_batch + (int64_t)q_off * p.o_row) * 2;
-        if (ooff != kOOB) {
-#pragma unroll
-            for (int c = 0; c < 8; ++c) *reinterpret_cast<u4*>(oseq + ooff + 32 * c) = u4{0, 0, 0, 0};
-            if (p.lse && hh == 0) p.lse[(int64_t)bidx * p.lse_batch + q_off + loff / 4] = INFINITY;
-        }
+        store_empty_row(p, bidx, q_off, lrow, hh);
         return;
     }
 
     // SRDs: Q / O / LSE of this sequence; K / V of this sequence and kv head, their range ending
     // at the workgroup's last key tile (the ring's DMA past it reads zeros and moves no bytes)
-    const char* qseq = reinterpret_cast<const char*>(p.q) + ((int64_t)bidx * p.q_batch + (int64_t)q_off * p.q_row) * 2;
-    char* oseq = reinterpret_cast<char*>(p.o) + ((int64_t)bidx * p.o_batch + (int64_t)q_off * p.o_row) * 2;
-    const uint32_t qbytes = (uint32_t)(((int64_t)(sq - 1) * p.q_row + (int64_t)(p.h - 1) * p.q_head + HD) * 2);
-    const uint32_t obytes = (uint32_t)(((int64_t)(sq - 1) * p.o_row + (int64_t)(p.h - 1) * p.o_head + HD) * 2);
-    const i32x4 qsrd = fwdpp_srd(qseq, qbytes), osrd = fwdpp_srd(oseq, obytes);
-    const float* lseq = p.lse ? p.lse + (int64_t)bidx * p.lse_batch + q_off : p.lse;
-    const int64_t lbytes = p.lse ? ((int64_t)(p.h - 1) * p.lse_head + sq) * 4 : 0;
-    const i32x4 lsrd = fwdpp_srd(lseq, (uint32_t)min(lbytes, (int64_t)kOOB - 1));
+    const RowSrds srd = row_srds<2>(p, bidx, q_off, sq);
+    const i32x4 qsrd = srd.q, osrd = srd.o, lsrd = srd.lse;
     const int k_row = (int)p.k_row;
     const int64_t k0 = (int64_t)k_off + (int64_t)kBlockN * T0;   // the item's first key row
     const char* kseq = reinterpret_cast<const char*>(p.k) +
@@ -163,10 +130,7 @@ __device__ __forceinline__ void fwdpp_item(const FwdParams& p, char* smem, const
                        ((int64_t)bidx * p.v_batch + k0 * p.v_row + (int64_t)hk_i * p.v_head) * 2;
     const int nk = min(sk, ntl_abs * kBlockN) - kBlockN * T0;
     const int kvbytes = __builtin_amdgcn_readfirstlane((int)(((nk - 1) * k_row + HD) * 2));
-    const int kblo = __builtin_amdgcn_readfirstlane((int)(uint32_t)(uint64_t)kseq);
-    const int kbhi = __builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)kseq >> 32) & 0xFFFF);
-    const int vblo = __builtin_amdgcn_readfirstlane((int)(uint32_t)(uint64_t)vseq);
-    const int vbhi = __builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)vseq >> 32) & 0xFFFF);
+    const int kblo = ptr_lo(kseq), kbhi = ptr_hi(kseq), vblo = ptr_lo(vseq), vbhi = ptr_hi(vseq);
 
     // LDS-DMA: wave w loads 8-row block w of every K / V tile, pieces i = chunks 8i .. 8i+7 of
     // the kv_off image (lane l lands at +16 l); K and V share the offsets (k_row == v_row)
@@ -197,18 +161,11 @@ __device__ __forceinline__ void fwdpp_item(const FwdParams& p, char* smem, const
         static_assert(kFwdpp16Ring == kFwdppRing, "both bodies address the same LDS ring");
         // row tile rt of this lane: row wrow0 + 16 rt + l16, 4 keys per 16-key block from 4 g
         const int g = lane >> 4, l16 = lane & 15;
-        int qo[2], oo[2], lo[2], li[2];
+        // (Q chunk 4 s + g, O columns 16 dt + 4 g)
+        LaneRow rt[2];
 #pragma unroll
-        for (int rt = 0; rt < 2; ++rt) {
-            const int rrow = wrow0 + 16 * rt + l16;
-            const bool rok = rrow < rows_total;
-            const int rpos = rok ? rrow / G : 0;
-            const int rhead = hk_i * G + (rok ? rrow - rpos * G : 0);
-            qo[rt] = rok ? (rpos * (int)p.q_row + rhead * (int)p.q_head) * 2 + 16 * g : kOOB;  // chunk 4 s + g
-            oo[rt] = rok ? (rpos * (int)p.o_row + rhead * (int)p.o_head) * 2 + 8 * g : kOOB;   // d 16 dt + 4 g
-            lo[rt] = (rok && g == 0) ? (int)(rhead * p.lse_head + rpos) * 4 : kOOB;
-            li[rt] = (rok ? lim_r(rpos) : sk) - 4 * g;
-        }
+        for (int t = 0; t < 2; ++t)
+            rt[t] = lane_row<2>(p, lim_r, wrow0 + 16 * t + l16, rows_total, hk_i, 16 * g, 8 * g, g);
         // K row reads: key 16 kt + l16, chunk 4 s + g; V^T reads: lane 4 q + p of group g, key
         // 4 g + q (+ 32 ks + 16 h), d 16 dt + 4 p, base per dt parity e (kv_off image)
         const int kb0 = sbase + 2048 * ((lane >> 3) & 1) + 64 * (lane & 7) + 16 * (g ^ ppx16((lane >> 2) & 3));
@@ -225,12 +182,12 @@ __device__ __forceinline__ void fwdpp_item(const FwdParams& p, char* smem, const
 #endif
         if constexpr (BF16)
             fwdpp16_item_bf16(kblo, kbhi, vblo, vbhi, kvbytes, qsrd, osrd, lsrd, kstep, kdst, ntl, t_w, e_w, grp,
-                              p.scale_log2, thr, kb0, vb16[0], vb16[1], dma0, dma0 + 128, li[0], li[1], qo[0], qo[1],
-                              oo[0], oo[1], lo[0], lo[1] XFA_PP16_ACC_ARG);
+                              p.scale_log2, thr, kb0, vb16[0], vb16[1], dma0, dma0 + 128, rt[0].lim, rt[1].lim, rt[0].qoff,
+                              rt[1].qoff, rt[0].ooff, rt[1].ooff, rt[0].loff, rt[1].loff XFA_PP16_ACC_ARG);
         else
             fwdpp16_item_f16(kblo, kbhi, vblo, vbhi, kvbytes, qsrd, osrd, lsrd, kstep, kdst, ntl, t_w, e_w, grp,
-                             p.scale_log2, thr, kb0, vb16[0], vb16[1], dma0, dma0 + 128, li[0], li[1], qo[0], qo[1],
-                             oo[0], oo[1], lo[0], lo[1] XFA_PP16_ACC_ARG);
+                             p.scale_log2, thr, kb0, vb16[0], vb16[1], dma0, dma0 + 128, rt[0].lim, rt[1].lim, rt[0].qoff,
+                             rt[1].qoff, rt[0].ooff, rt[1].ooff, rt[0].loff, rt[1].loff XFA_PP16_ACC_ARG);
 #undef XFA_PP16_ACC_ARG
         return;
     }
@@ -262,10 +219,7 @@ __device__ __forceinline__ void fwdpp_item(const FwdParams& p, char* smem, const
         const int* btab = p.block_table + (int64_t)bidx * p.bt_stride;
         const char* kpool = reinterpret_cast<const char*>(p.k) + (int64_t)hk_i * p.k_head * 2;
         const char* vpool = reinterpret_cast<const char*>(p.v) + (int64_t)hk_i * p.v_head * 2;
-        const int pkl = __builtin_amdgcn_readfirstlane((int)(uint32_t)(uint64_t)kpool);
-        const int pkh = __builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)kpool >> 32) & 0xFFFF);
-        const int pvl = __builtin_amdgcn_readfirstlane((int)(uint32_t)(uint64_t)vpool);
-        const int pvh = __builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)vpool >> 32) & 0xFFFF);
+        const int pkl = ptr_lo(kpool), pkh = ptr_hi(kpool), pvl = ptr_lo(vpool), pvh = ptr_hi(vpool);
         const int pstr = __builtin_amdgcn_readfirstlane((int)(p.k_batch * 2));
         const int rowb = __builtin_amdgcn_readfirstlane(k_row * 2);
         const int lgp = __builtin_amdgcn_readfirstlane(31 - __builtin_clz(p.page_size));
@@ -295,65 +249,17 @@ __device__ __forceinline__ void fwdpp_item(const FwdParams& p, char* smem, const
                        feat, scp2, alw, ald, alm, l_w, liml, wid, f_w, alw2, adiag XFA_PP_ACC_ARG);
 }
 
-// Persistent grid (one workgroup per CU) over the items, the 4-wave kernel's orders: XCD-grouped
-// (n-1-i, i) row-block pairs (dense) or per-XCD dynamic queues (varlen).
+// Persistent grid (one workgroup per CU) over the items (fwd_walk, fmha_fwd_sched.h).
 template <bool BF16, bool M16 = false, bool PG = false>
 __global__ void __launch_bounds__(512, 1) fmha_fwdpp_kernel(const FwdParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    __shared__ int s_claim[2];
-    const int nbh = p.b * p.hk;
-    const int g = gridDim.x;
 #ifdef XFA_FWDPP_STAMPS
     unsigned acc = 0;
 #endif
-    for (int k = 0;; ++k) {
-        int bh, m_block;
-        if (p.persistent == 2) {
-            const int nm = p.n_mblocks, npair = (nm + 1) >> 1;
-            const int bid = (int)blockIdx.x;
-            const int v = (bid & 7) * (g >> 3) + (bid >> 3);
-            const int q = (k >> 1) * g + v;
-            if (q >= nbh * npair) break;
-            bh = q / npair;
-            const int i = q - bh * npair;
-            m_block = (k & 1) ? i : nm - 1 - i;
-            if ((k & 1) && i == nm - 1 - i) continue;
-        } else if (p.persistent == 1) {
-            const int lin = k * g + ((k & 1) ? g - 1 - (int)blockIdx.x : (int)blockIdx.x);
-            if (lin >= nbh * p.n_mblocks) break;
-            bh = lin % nbh;
-            m_block = p.n_mblocks - 1 - lin / nbh;
-        } else if (p.persistent == 3) {
-            const int x = p.xcd_queues ? (int)(blockIdx.x & 7) : 0;
-            const int nq = p.xcd_queues ? (nbh - x + 7) >> 3 : nbh;
-            if (threadIdx.x == 0) s_claim[k & 1] = atomicAdd(p.work_ctr + 2 + x, 1);
-            __syncthreads();
-            const int q = s_claim[k & 1];
-            if (q >= nq * p.n_mblocks) break;
-            if (p.xcd_queues) {
-                bh = x + 8 * (q / p.n_mblocks);
-                m_block = p.n_mblocks - 1 - q % p.n_mblocks;
-            } else {
-                bh = q % nq;
-                m_block = p.n_mblocks - 1 - q / nq;
-            }
-        } else {
-            if (k > 0) break;
-            bh = blockIdx.x;
-            m_block = gridDim.y - 1 - blockIdx.y;
-        }
-        fwdpp_item<BF16, M16, PG>(p, smem, bh, m_block XFA_PP_ACC_ARG);
-    }
+    fwd_walk<kFwdppQueue>(p, [&](int bh, int m_block) { fwdpp_item<BF16, M16, PG>(p, smem, bh, m_block XFA_PP_ACC_ARG); });
 #ifdef XFA_FWDPP_STAMPS
     if ((threadIdx.x & 63) < 8) atomicAdd(&g_fwdpp_stamps[(threadIdx.x >> 6) * 8 + (threadIdx.x & 63)], acc);
 #endif
-    if (p.persistent == 3 && threadIdx.x == 0) {
-        const int total = (int)(gridDim.x * gridDim.y * gridDim.z);
-        if (atomicAdd(p.work_ctr + 1, 1) == total - 1) {
-            for (int i = 2; i < 10; ++i) atomicExch(p.work_ctr + i, 0);
-            atomicExch(p.work_ctr + 1, 0);
-        }
-    }
 }
 
 }  // namespace xfa

@@ -5,6 +5,7 @@
 #pragma once
 
 #include "fmha_common.h"
+#include "fmha_fwd_sched.h"
 
 #include <atomic>
 
@@ -91,14 +92,14 @@ void note_launch(const char* kernel, int persistent, int xcdq, unsigned gx, unsi
 // kernel gets them (n_mblocks, persistent, xcd_queues filled in) and the grid.  An item is one
 // row block of `rows_per_item` query rows (seqlen_q * group of them) of one (b, kv head);
 // `slots` workgroups stay resident once there are more items than slots (and fwd_persistent
-// > 0), else one workgroup runs one item.
+// > 0), else one workgroup runs one item.  By the kernel's FwdQueue (fmha_fwd_sched.h, where
+// the modes are described and fwd_walk walks them):
 //   kQueueStatic: boustrophedon (1) or XCD-grouped pairs (2, fwd_order = 1 and slots % 8 == 0);
 //   kQueueXcd:    the same, or with p.work_ctr the dynamic item queue (3), one queue per XCD
 //                 where fwd_xcdq asks and the slots and (b, kv head) units fill 8 XCDs;
 //   kQueueRagged: the 8-wave fp8 kernel's packed launches (it has no per-XCD queues): one
 //                 dynamic queue as soon as there are more items than CUs, walked by
 //                 min(items, slots) workgroups.
-enum FwdQueue { kQueueStatic, kQueueXcd, kQueueRagged };
 struct FwdPlan { FwdParams pp; dim3 grid; };
 inline FwdPlan plan_fwd(const FwdParams& p, int rows_per_item, int slots, int splits, FwdQueue queue) {
     FwdPlan s{p, dim3()};
