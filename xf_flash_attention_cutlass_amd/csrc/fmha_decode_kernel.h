@@ -297,7 +297,8 @@ __global__ void __launch_bounds__(NWV * 64, 2) fmha_decode_kernel(const FwdParam
     auto issue = [&](const int t, const int (&pg)[3], u32x4 (&kr)[NLD], u32x4 (&vr)[NLD]) __attribute__((always_inline)) {
         if (paged) {
             // past the last key the page index is clamped, so the rows of a group that wraps
-            // there re-read rows of the last page: keys >= seqlen, masked in registers
+            // there re-read rows of the last page: keys >= seqlen, whose scores are masked in
+            // registers and whose V rows are zeroed in the LDS image (tile())
 #pragma unroll
             for (int i = 0; i < NLD; ++i) {
                 // (readfirstlane: the divergence analysis loses the uniformity of the page
@@ -456,6 +457,20 @@ __global__ void __launch_bounds__(NWV * 64, 2) fmha_decode_kernel(const FwdParam
                     const int key = keyb + keyof(kb, r);
                     if (edge && (key >= my_lr || key < my_ll)) st[kb][r] = -INFINITY;
                 }
+            // The tile that holds the sequence's end (every lane is on the edge there): the paged
+            // loads brought cache rows >= sk, whatever they hold; their scores were replaced
+            // above, but V enters O^T += V^T P^T as 0 * V, which a NaN or Inf survives — zero
+            // those rows of the V image (this lane's own chunks, behind its own writes).  Full
+            // tiles never get here.
+            if ((t + 1) * kDecKeys > sk) {
+#pragma unroll
+                for (int i = 0; i < NLD; ++i)
+                    if (keyb + RPI * i + lrow >= sk) {
+#pragma unroll
+                        for (int h2 = 0; h2 < 3 - ESZ; ++h2)
+                            *reinterpret_cast<u32x4*>(vsl + kw[i][h2]) = u32x4{0u, 0u, 0u, 0u};
+                    }
+            }
         }
         float mx = -INFINITY;
 #pragma unroll
