@@ -127,7 +127,7 @@ void fmha_set_rng_state(uint64_t seed, uint64_t offset);
 void fmha_set_rng_state_device(const int64_t* seed_ptr, const int64_t* offset_ptr,
                                uint64_t offset_add, int64_t* rng_out);
 
-/* Library version / build identification, e.g. "xf-fmha-gfx950 2.2".  2.0 (round 3) changed
+/* Library version / build identification, e.g. "xf-fmha-gfx950 2.7".  2.0 (round 3) changed
  * argument lists of existing symbols; 2.1 exports those under _v2 names (see INTEGRATION.md
  * "ABI history"). */
 const char* fmha_version(void);
@@ -353,6 +353,68 @@ void fmha_varlen_bwd_v2(void* dout, void* q, void* k, void* v, void* out, void* 
 size_t fmha_varlen_bwd_workspace_size_v2(int32_t total_q, int32_t max_seqlen_k, int32_t batch_size,
                                       int32_t num_heads, int32_t num_heads_k, int32_t head_size,
                                       bool deterministic);
+
+/* ------------------------------------------------------------ attention sinks (2.7) --- */
+
+/* Attention sink (gpt-oss; other builds' s_aux / learnable_sink): `sink` is fp32 [num_heads] on
+ * the device, one logit per QUERY head that joins the softmax denominator and carries no value.
+ * It is in the units of the scaled scores: not multiplied by softmax_scale, not soft-capped.
+ * For row i of head h over its visible keys j (scores S after scale, softcap and masks):
+ *   P_ij = exp(S_ij) / (sum_j exp(S_ij) + exp(sink[h])),  O_i = sum_j P_ij V_j,
+ *   LSE_i = log(sum_j exp(S_ij) + exp(sink[h])).
+ * A row without a visible key keeps O = 0 and LSE = +inf; sink[h] = -inf is no sink for head h
+ * (bit-identical to the base entry); sink == NULL is the base entry, bit for bit.  Refused with
+ * an error, outputs untouched: a sink with ALiBi, with p_dropout > 0 or with s_dmask.  Causal
+ * and left / right windows, softcap, GQA / MQA, seqused_k, paged and fp8 caches, cache_leftpad,
+ * split-KV and every head size of the base entries are allowed.  fmha_last_kernel() ends in
+ * " sink=epilogue" (applied in the forward kernel), " sink=combine" (in the split combine) or
+ * " sink=pass" (a pass over O and LSE after a launch whose kernel cannot apply it; when
+ * softmax_lse is NULL the LSE it needs lives in pool scratch).  No allocation per call, no host
+ * sync.
+ *
+ * fmha_fwd_sink: fmha_fwd_strided plus sink. */
+void fmha_fwd_sink(void* q, void* k, void* v, void* o, void* alibi_slopes, void* softmax_lse,
+                   int32_t seqlen_q, int32_t seqlen_k, int32_t batch_size, int32_t num_heads,
+                   int32_t num_heads_k, int32_t head_size, const int64_t* strides,
+                   float softmax_scale, int window_size_left, int window_size_right,
+                   float softcap, bool is_fp16, int num_splits, hipStream_t stream,
+                   float p_dropout, void* s_dmask, const float* sink);
+
+/* fmha_varlen_fwd_ex plus sink; total_q must be given with a sink. */
+void fmha_varlen_fwd_sink(void* q, void* k, void* v, void* o, void* softmax_lse,
+                          void* cu_seqlens_q, void* cu_seqlens_k, void* seqused_k,
+                          void* block_table, int32_t block_table_stride, int32_t page_block_size,
+                          void* alibi_slopes, int32_t alibi_batch_stride,
+                          int32_t max_seqlen_q, int32_t max_seqlen_k, int32_t total_q,
+                          int32_t batch_size, int32_t num_heads, int32_t num_heads_k,
+                          int32_t head_size, float softmax_scale, int window_size_left,
+                          int window_size_right, float softcap, bool is_fp16, hipStream_t stream,
+                          float p_dropout, void* s_dmask, const float* sink);
+
+/* fmha_page_kvcache_fwd_ex plus sink (bf16 / fp16 and fp8 caches alike). */
+void fmha_page_kvcache_fwd_sink(void* q, void* kcache, void* vcache, void* o, void* softmax_lse,
+                                void* block_table, int32_t block_table_stride, void* cache_seqlens,
+                                int32_t seqlen_q, int32_t max_seqlen_k, int32_t batch_size,
+                                int32_t num_heads, int32_t num_heads_k, int32_t head_size,
+                                int32_t page_block_size, float softmax_scale,
+                                int window_size_left, int window_size_right, float softcap,
+                                void* alibi_slopes, int32_t alibi_batch_stride, int32_t num_splits,
+                                int32_t kv_dtype, float k_scale, float v_scale,
+                                void* cache_leftpad, bool is_fp16, hipStream_t stream,
+                                const float* sink);
+
+/* Gradient of the sink.  fmha_bwd / fmha_varlen_bwd need no change for a sink forward: given its
+ * out and softmax_lse, P = exp(S - LSE) and D = rowsum(dO * O) are already those of the sink
+ * softmax (the sink column has V = 0, hence dP = 0), so dq / dk / dv come out right.  This entry
+ * adds dsink[h] = - sum over (batch, row) of exp(sink[h] - LSE) * D; rows with LSE = +inf add 0.
+ * Run it after fmha_bwd / fmha_varlen_bwd called with a non-NULL softmax_d.  softmax_lse and
+ * softmax_d: element (b, h, row) at b * batch_stride + h * head_stride + row - dense
+ * [batch, heads, seqlen_q]: (heads * seqlen_q, seqlen_q); packed: batch = 1, rows = total_q,
+ * head_stride = total_q.  dsink: fp32 [num_heads].  One workgroup per head sums in a fixed
+ * order without atomics: bitwise reproducible. */
+void fmha_bwd_sink(const float* softmax_lse, const float* softmax_d, const float* sink, float* dsink,
+                   int32_t batch, int32_t num_heads, int32_t rows, int64_t batch_stride,
+                   int64_t head_stride, hipStream_t stream);
 
 #ifdef __cplusplus
 } /* extern "C" */

@@ -1,9 +1,15 @@
 """Is the device code of two source trees the same?  Compiles every translation unit build.py
 compiles (and the ones XFA_VARIANTS=1 rebuilds) device-only to assembly with build.py's flags,
-in both trees, and compares kernel by kernel after renumbering the .LBB labels.  Only the
-__hip_cuid_<hash> symbol (a hash of the source text) may differ.
+in both trees, and compares kernel by kernel after renumbering the .LBB labels and dropping the
+assembler comments (which name labels by the function's index in its unit).  Only the
+__hip_cuid_<hash> symbol (a hash of the source text) may differ.  A kernel only one tree has is
+listed as ONLY IN A / B and does not count as a difference.
 
-  python tools/isa_diff.py <tree A> <tree B> [-j N]      exit status 1 if any kernel differs
+  python tools/isa_diff.py <tree A> <tree B> [-j N] [--kernarg]    exit status 1 if any kernel differs
+
+--kernarg: for trees whose parameter blocks differ in size (a field added at the end): the
+kernarg size and the offsets of scalar loads / address adds from the kernarg pointer s[0:1] are
+masked, so a kernel counts as identical when nothing but where its arguments lie has changed.
 """
 import argparse
 import concurrent.futures as cf
@@ -28,27 +34,44 @@ def units(tree):
     return b, tus
 
 
+MASK_KERNARG = False
+
+
 def kernels(tree, tu, out_dir):
     """{kernel symbol: normalised body} of one translation unit"""
     b, (name, src, defs) = tu
     asm = os.path.join(out_dir, name + ".s")
     subprocess.run([b.HIPCC, "-x", "hip", *b.HIP_FLAGS, *defs, "--cuda-device-only", "-S",
                     os.path.join(b.CSRC, src), "-o", asm], check=True)
-    text = re.sub(r"(?m)^.*__hip_cuid_.*\n", "", open(asm).read())
+    return name, normalise(open(asm).read())
+
+
+def normalise(text):
+    """{kernel symbol: normalised body + kernel descriptor} of one unit's assembly"""
+    text = re.sub(r"(?m)^.*__hip_cuid_.*\n", "", text)
+    if MASK_KERNARG:
+        text = re.sub(r"\.amdhsa_kernarg_size \d+", ".amdhsa_kernarg_size <n>", text)
+        text = re.sub(r"(?m)^(\s*s_load_dword\w* \S+ s\[0:1\], |\s*s_add_u32 s\d+, s0, |\s*s_addc_u32 s\d+, s1, )0x[0-9a-f]+",
+                      r"\1<kernarg>", text)
     out = {}
     for m in re.finditer(r"(?ms)^(\w+):.*?^\.Lfunc_end\d+:", text):
         labels = {}
-        out[m.group(1)] = re.sub(r"\.LBB\d+_\d+", lambda l: labels.setdefault(l.group(0), f".L{len(labels)}"), m.group(0))
+        body = re.sub(r"\.Lfunc_end\d+", ".Lfunc_end", m.group(0))     # (a function's index in its unit)
+        body = re.sub(r"(?m)[ \t]*;.*$", "", body)
+        out[m.group(1)] = re.sub(r"\.LBB\d+_\d+", lambda l: labels.setdefault(l.group(0), f".L{len(labels)}"), body)
     for m in re.finditer(r"(?ms)^\s*\.amdhsa_kernel (\w+)\n.*?\.end_amdhsa_kernel", text):
         out[m.group(1)] += m.group(0)          # registers, LDS, the kernel descriptor's settings
-    return name, out
+    return out
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("trees", nargs=2)
     ap.add_argument("-j", type=int, default=8)
+    ap.add_argument("--kernarg", action="store_true", help="mask kernarg size and offsets")
     a = ap.parse_args()
+    global MASK_KERNARG
+    MASK_KERNARG = a.kernarg
     res, bad = [], 0
     with tempfile.TemporaryDirectory() as tmp, cf.ThreadPoolExecutor(a.j) as ex:
         for i, tree in enumerate(a.trees):
@@ -57,10 +80,12 @@ def main():
             res.append(dict(ex.map(lambda tu: kernels(tree, (b, tu), os.path.join(tmp, str(i))), tus)))
     for name in sorted(set(res[0]) | set(res[1])):
         ka, kb = res[0].get(name, {}), res[1].get(name, {})
-        diff = sorted(k for k in set(ka) | set(kb) if ka.get(k) != kb.get(k))
+        diff = sorted(k for k in set(ka) & set(kb) if ka[k] != kb[k])
         bad += len(diff)
-        print(f"{name}: {len(ka)} kernels, {len(ka) - len([k for k in diff if k in ka])} identical"
-              + "".join(f"\n  DIFFERS {k}" for k in diff))
+        print(f"{name}: {len(ka)} kernels, {len(set(ka) & set(kb)) - len(diff)} identical"
+              + "".join(f"\n  DIFFERS {k}" for k in diff)
+              + "".join(f"\n  ONLY IN A {k}" for k in sorted(set(ka) - set(kb)))
+              + "".join(f"\n  ONLY IN B {k}" for k in sorted(set(kb) - set(ka))))
     print("device code identical" if not bad else f"{bad} kernels differ")
     return 1 if bad else 0
 

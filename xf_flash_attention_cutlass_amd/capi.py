@@ -54,6 +54,15 @@ _SIGS = {
                             b_, i32, i32, i32, i32, i32, b_, vp],
     "fmha_kvcache_append_fp8": [vp, vp, vp, vp, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, i32, b_,
                                 b_, i32, i32, i32, i32, i32, b_, vp, f32, f32],
+    "fmha_fwd_sink": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32,
+                      C.POINTER(C.c_int64), f32, C.c_int, C.c_int, f32, b_, C.c_int, vp,
+                      f32, vp, vp],
+    "fmha_varlen_fwd_sink": [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, i32, i32, i32, i32,
+                             i32, i32, i32, i32, f32, C.c_int, C.c_int, f32, b_, vp, f32, vp, vp],
+    "fmha_page_kvcache_fwd_sink": [vp, vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32,
+                                   i32, f32, C.c_int, C.c_int, f32, vp, i32, i32, i32, f32, f32, vp,
+                                   b_, vp, vp],
+    "fmha_bwd_sink": [vp, vp, vp, vp, i32, i32, i32, C.c_int64, C.c_int64, vp],
     "fmha_last_error": [],
     "fmha_last_status": [],
     "fmha_last_num_splits": [],

@@ -36,6 +36,8 @@ void note_launch(const char* kernel, int persistent, int xcdq, unsigned gx, unsi
     snprintf(g_last_kernel, sizeof(g_last_kernel), "%s persistent=%d xcdq=%d grid=%ux%ux%u block=%d",
              kernel, persistent, xcdq, gx, gy, gz, block);
 }
+thread_local SinkMech g_sink_mech = kSinkNone;   // how this thread's last forward applied its sink
+void note_sink(SinkMech mech) { g_sink_mech = mech; }
 }  // namespace xfa
 
 namespace {
@@ -47,7 +49,7 @@ thread_local int g_last_splits = 0;     // split count of this thread's last for
 void clear_error() { g_err.clear(); g_status = 0; }
 // forward entries: also forget the last forward's kernel / splits, so a call that fails
 // validation or launches nothing reports "" / 0 (fmha_last_kernel's contract)
-void begin_fwd() { clear_error(); g_last_kernel[0] = 0; g_last_splits = 0; }
+void begin_fwd() { clear_error(); g_last_kernel[0] = 0; g_last_splits = 0; g_sink_mech = kSinkNone; }
 bool fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 bool fail(int code, const char* fmt, ...) {
     char buf[512];
@@ -244,7 +246,8 @@ bool check_common(const void* q, const void* k, const void* v, const void* o, in
 // pointers, shape, windows, scales, ALiBi
 void fwd_common(FwdParams& p, void* q, void* k, void* v, void* o, void* lse, int b, int h, int hk,
                 int d, int seqlen_q, int seqlen_k, int wl, int wr, float softmax_scale,
-                float softcap, const void* alibi, int alibi_bstride) {
+                float softcap, const void* alibi, int alibi_bstride, const float* sink = nullptr) {
+    p.sink = sink;
     p.q = q; p.k = k; p.v = v; p.o = o; p.lse = (float*)lse;
     p.b = b; p.h = h; p.hk = hk; p.group = h / hk; p.d = d;
     p.seqlen_q = seqlen_q; p.seqlen_k = seqlen_k;
@@ -393,17 +396,28 @@ void run_fwd(FwdParams& p, bool bf16, hipStream_t st, int num_splits_req) {
     p.dec_ns = nullptr;
     p.comb_row = o.comb_row.load();
     const int ext = p.dec_bal ? p.dec_cap : splits;   // split extent of the scratch
-    if (splits > 1) {
+    // The sink post-pass (a launch that ends in a generated D = 128 body, or in the folded decode
+    // merge) reads the LSE the launch wrote: a caller that asked for none gets it in pool scratch,
+    // behind the split scratch in the same block (the pool is one block per stream, so two
+    // requests would alias).  Rows as the LSE's own layout: packed launches [h, total_q].
+    const size_t lse_rows = p.cu_seqlens_q ? (size_t)p.h * p.lse_head : (size_t)p.b * p.h * p.seqlen_q;
+    const size_t sink_lse = (p.sink && !p.lse && (p.d == 128 || (p.decode && o.dec_fold.load())))
+                                ? lse_rows * sizeof(float) : 0;
+    if (splits > 1 || sink_lse) {
         const int hd = hd_bucket(p.d);
         const size_t rows = (size_t)p.b * p.h * p.seqlen_q;
-        const size_t obytes = (size_t)ext * rows * hd * sizeof(float);
-        const size_t lbytes = (size_t)ext * rows * sizeof(float);
-        const size_t bytes = obytes + lbytes + (p.dec_bal ? (size_t)p.b * sizeof(int) : 0);
+        const size_t obytes = splits > 1 ? (size_t)ext * rows * hd * sizeof(float) : 0;
+        const size_t lbytes = splits > 1 ? (size_t)ext * rows * sizeof(float) : 0;
+        const size_t nbytes = ((p.dec_bal ? (size_t)p.b * sizeof(int) : 0) + 15) / 16 * 16;
+        const size_t bytes = obytes + lbytes + nbytes + sink_lse;
         char* base = (char*)pool_get(st, bytes);
         if (!base) { fail(3, "could not allocate %zu bytes of split scratch", bytes); return; }
-        p.oaccum = (float*)base;
-        p.lseaccum = (float*)(base + obytes);
-        if (p.dec_bal) p.dec_ns = (int*)(base + obytes + lbytes);
+        if (splits > 1) {
+            p.oaccum = (float*)base;
+            p.lseaccum = (float*)(base + obytes);
+            if (p.dec_bal) p.dec_ns = (int*)(base + obytes + lbytes);
+        }
+        if (sink_lse) p.lse = (float*)(base + obytes + lbytes + nbytes);
     }
     p.dec_ctr = nullptr;
     if (p.decode && o.dec_fold.load()) {
@@ -427,6 +441,31 @@ void run_fwd(FwdParams& p, bool bf16, hipStream_t st, int num_splits_req) {
     if (!hip_ok(dispatch_fwd(p, bf16, st), "forward launch")) return;
     // causal ALiBi: the LSE in the reference's convention (+slope key, mask_hip.h:163-164)
     if (p.lse && p.alibi && p.alibi_causal) hip_ok(launch_lse_alibi(lse_alibi_params(p, +1.f), st), "LSE ALiBi pass");
+    if (!p.sink) return;
+    // the launcher recorded which mechanism applies the sink (fmha_launch.h SinkMech)
+    if (g_sink_mech == kSinkPass) {
+        SinkPassParams sp{};
+        sp.o = p.o; sp.lse = p.lse; sp.sink = p.sink;
+        sp.o_batch = p.o_batch; sp.o_row = p.o_row; sp.o_head = p.o_head;
+        sp.lse_batch = p.lse_batch; sp.lse_head = p.lse_head;
+        sp.b = p.cu_seqlens_q ? 1 : p.b;
+        sp.rows = p.cu_seqlens_q ? (int)p.lse_head : p.seqlen_q;    // packed: total_q rows
+        sp.h = p.h; sp.d = p.d;
+        if (!hip_ok(launch_sink_pass(sp, !bf16, st), "sink post-pass")) return;
+    }
+    static const char* const kMech[] = {"", " sink=epilogue", " sink=combine", " sink=pass"};
+    strncat(g_last_kernel, kMech[g_sink_mech], sizeof(g_last_kernel) - strlen(g_last_kernel) - 1);
+}
+
+// An attention sink (the _sink entries; null: none): not with ALiBi (the kernels' causal-ALiBi
+// frame shifts a row's scores by a constant, and a sink is not shift-invariant), dropout or
+// return_softmax
+bool check_sink(const float* sink, const void* alibi, float p_dropout, const void* s_dmask) {
+    if (!sink) return true;
+    if (((uintptr_t)sink) & 3) return fail(1, "sink must be a 4-byte aligned device pointer (fp32 [num_heads])");
+    if (alibi) return fail(1, "an attention sink does not support ALiBi");
+    if (p_dropout > 0.f || s_dmask) return fail(1, "an attention sink does not support dropout / return_softmax");
+    return true;
 }
 
 // The fp8 forward's launch (one pass, D = 128): the schedule knobs with fp8_w4 as the kernel
@@ -479,7 +518,7 @@ const char* fmha_last_error(void) { return g_err.c_str(); }
 int fmha_last_status(void) { return g_status; }
 int fmha_last_num_splits(void) { return g_last_splits; }
 const char* fmha_last_kernel(void) { return g_last_kernel; }
-const char* fmha_version(void) { return XFA_VARIANTS ? "xf-fmha-gfx950 2.6 (variants)" : "xf-fmha-gfx950 2.6"; }
+const char* fmha_version(void) { return XFA_VARIANTS ? "xf-fmha-gfx950 2.7 (variants)" : "xf-fmha-gfx950 2.7"; }
 
 void fmha_set_rng_state(uint64_t seed, uint64_t offset) {
     g_seed = seed;
@@ -554,16 +593,22 @@ void fmha_fwd(void* q_ptr, void* k_ptr, void* v_ptr, void* o_ptr, void* alibi_sl
     }
 }
 
-void fmha_fwd_strided(void* q, void* k, void* v, void* o, void* alibi_slopes, void* softmax_lse,
-                      int32_t seqlen_q, int32_t seqlen_k, int32_t batch_size, int32_t num_heads,
-                      int32_t num_heads_k, int32_t head_size, const int64_t* st,
-                      float softmax_scale, int window_size_left, int window_size_right,
-                      float softcap, bool is_fp16, int num_splits, hipStream_t stream,
-                      float p_dropout, void* s_dmask) {
+}  // extern "C"
+
+namespace {
+
+// fmha_fwd_strided (sink = null) and fmha_fwd_sink
+void fwd_strided_entry(const char* entry, void* q, void* k, void* v, void* o, void* alibi_slopes,
+                       void* softmax_lse, int32_t seqlen_q, int32_t seqlen_k, int32_t batch_size,
+                       int32_t num_heads, int32_t num_heads_k, int32_t head_size, const int64_t* st,
+                       float softmax_scale, int window_size_left, int window_size_right,
+                       float softcap, bool is_fp16, int num_splits, hipStream_t stream,
+                       float p_dropout, void* s_dmask, const float* sink) {
     try {
         begin_fwd();
         DevRngScope rng_scope;
         if (!check_common(q, k, v, o, batch_size, num_heads, num_heads_k, head_size)) return;
+        if (!check_sink(sink, alibi_slopes, p_dropout, s_dmask)) return;
         REQUIRE(st != nullptr, "strides must be non-null");
         REQUIRE(seqlen_q > 0 && seqlen_k > 0, "seqlen_q/seqlen_k must be positive (%d, %d)", seqlen_q, seqlen_k);
         for (int i = 0; i < 12; ++i) REQUIRE(st[i] >= 0, "strides must be non-negative");
@@ -588,7 +633,7 @@ void fmha_fwd_strided(void* q, void* k, void* v, void* o, void* alibi_slopes, vo
         FwdParams p{};
         fwd_common(p, q, k, v, o, softmax_lse, batch_size, num_heads, num_heads_k, head_size,
                    seqlen_q, seqlen_k, window_size_left, window_size_right, softmax_scale, softcap,
-                   alibi_slopes, batch_size > 1 ? num_heads : 0);
+                   alibi_slopes, batch_size > 1 ? num_heads : 0, sink);
         p.q_batch = st[0]; p.q_row = st[1]; p.q_head = st[2];
         p.k_batch = st[3]; p.k_row = st[4]; p.k_head = st[5];
         p.v_batch = st[6]; p.v_row = st[7]; p.v_head = st[8];
@@ -599,13 +644,9 @@ void fmha_fwd_strided(void* q, void* k, void* v, void* o, void* alibi_slopes, vo
         run_fwd(p, !is_fp16, stream, num_splits);
         if (s_dmask && g_status == 0) run_sdmask(p, s_dmask, !is_fp16, stream);
     } catch (...) {
-        fail(9, "internal error in fmha_fwd_strided");
+        fail(9, "internal error in %s", entry);
     }
 }
-
-}  // extern "C"
-
-namespace {
 
 void fwd_fp8_entry(const char* entry, void* q, void* k, void* v, void* o, void* softmax_lse,
                    const Fp8Descales& ds, bool device_descales, int32_t seqlen_q, int32_t seqlen_k,
@@ -776,19 +817,27 @@ void fmha_quantize_fp8(const void* x, void* x8, float* descale, const void* cu_s
     }
 }
 
-void fmha_varlen_fwd_ex(void* q, void* k, void* v, void* o, void* softmax_lse,
-                        void* cu_seqlens_q, void* cu_seqlens_k, void* seqused_k,
-                        void* block_table, int32_t block_table_stride, int32_t page_block_size,
-                        void* alibi_slopes, int32_t alibi_batch_stride,
-                        int32_t max_seqlen_q, int32_t max_seqlen_k, int32_t total_q,
-                        int32_t batch_size, int32_t num_heads, int32_t num_heads_k,
-                        int32_t head_size, float softmax_scale, int window_size_left,
-                        int window_size_right, float softcap, bool is_fp16, hipStream_t stream,
-                        float p_dropout, void* s_dmask) {
+}  // extern "C"
+
+namespace {
+
+// fmha_varlen_fwd_ex (sink = null) and fmha_varlen_fwd_sink
+void varlen_fwd_entry(const char* entry, void* q, void* k, void* v, void* o, void* softmax_lse,
+                      void* cu_seqlens_q, void* cu_seqlens_k, void* seqused_k,
+                      void* block_table, int32_t block_table_stride, int32_t page_block_size,
+                      void* alibi_slopes, int32_t alibi_batch_stride,
+                      int32_t max_seqlen_q, int32_t max_seqlen_k, int32_t total_q,
+                      int32_t batch_size, int32_t num_heads, int32_t num_heads_k,
+                      int32_t head_size, float softmax_scale, int window_size_left,
+                      int window_size_right, float softcap, bool is_fp16, hipStream_t stream,
+                      float p_dropout, void* s_dmask, const float* sink) {
     try {
         begin_fwd();
         DevRngScope rng_scope;
         if (!check_common(q, k, v, o, batch_size, num_heads, num_heads_k, head_size)) return;
+        if (!check_sink(sink, alibi_slopes, p_dropout, s_dmask)) return;
+        // (the post-pass walks the packed rows [0, total_q))
+        REQUIRE(!sink || total_q > 0, "total_q must be given with a sink");
         REQUIRE(cu_seqlens_q && (cu_seqlens_k || block_table),
                 "cu_seqlens_q and cu_seqlens_k (or a block table) must be given");
         REQUIRE(max_seqlen_q > 0 && max_seqlen_k >= 0, "max_seqlen_q must be positive");
@@ -807,7 +856,7 @@ void fmha_varlen_fwd_ex(void* q, void* k, void* v, void* o, void* softmax_lse,
         FwdParams p{};
         fwd_common(p, q, k, v, o, softmax_lse, batch_size, num_heads, num_heads_k, head_size,
                    max_seqlen_q, max_seqlen_k, window_size_left, window_size_right, softmax_scale,
-                   softcap, alibi_slopes, alibi_batch_stride);
+                   softcap, alibi_slopes, alibi_batch_stride, sink);
         packed_strides(p, num_heads, num_heads_k, head_size, total_q);
         if (block_table) paged_kv(p, block_table, block_table_stride, page_block_size, num_heads_k, head_size);
         p.cu_seqlens_q = (const int*)cu_seqlens_q;
@@ -817,8 +866,108 @@ void fmha_varlen_fwd_ex(void* q, void* k, void* v, void* o, void* softmax_lse,
         run_fwd(p, !is_fp16, stream, 1);
         if (s_dmask && g_status == 0) run_sdmask(p, s_dmask, !is_fp16, stream);
     } catch (...) {
-        fail(9, "internal error in fmha_varlen_fwd_ex");
+        fail(9, "internal error in %s", entry);
     }
+}
+
+// fmha_page_kvcache_fwd_ex (sink = null) and fmha_page_kvcache_fwd_sink
+void page_kvcache_entry(const char* entry, void* q, void* kcache, void* vcache, void* o, void* softmax_lse,
+                        void* block_table, int32_t block_table_stride, void* cache_seqlens,
+                        int32_t seqlen_q, int32_t max_seqlen_k, int32_t batch_size,
+                        int32_t num_heads, int32_t num_heads_k, int32_t head_size,
+                        int32_t page_block_size, float softmax_scale,
+                        int window_size_left, int window_size_right, float softcap,
+                        void* alibi_slopes, int32_t alibi_batch_stride, int32_t num_splits,
+                        int32_t kv_dtype, float k_scale, float v_scale,
+                        void* cache_leftpad, bool is_fp16, hipStream_t stream, const float* sink) {
+    try {
+        begin_fwd();
+        if (!check_common(q, kcache, vcache, o, batch_size, num_heads, num_heads_k, head_size)) return;
+        if (!check_sink(sink, alibi_slopes, 0.f, nullptr)) return;
+        REQUIRE(block_table, "block_table must be given for the paged KV path");
+        REQUIRE(page_block_size > 0, "page_block_size must be positive");
+        REQUIRE(seqlen_q > 0 && max_seqlen_k > 0, "seqlen_q / seqlen_k must be positive");
+        REQUIRE(kv_dtype == 0 || kv_dtype == 1, "kv_dtype must be 0 (same as q) or 1 (fp8 e4m3fn)");
+        REQUIRE(block_table_stride > 0, "block_table_stride must be positive");
+        // export.cpp:1627-1628 (commented out in the reference): no paged KV with leftpad
+        REQUIRE(!cache_leftpad || max_seqlen_k <= page_block_size,
+                "cache_leftpad needs a non-paged cache (one page per sequence): Paged KV and "
+                "leftpad_k are not supported at the same time");
+        if (!slab_ok("q/o", seqlen_q, (int64_t)num_heads * head_size, 2) ||
+            !slab_ok("kcache/vcache page", page_block_size, (int64_t)num_heads_k * head_size, kv_dtype == 1 ? 1 : 2)) return;
+        FwdParams p{};
+        fwd_common(p, q, kcache, vcache, o, softmax_lse, batch_size, num_heads, num_heads_k, head_size,
+                   seqlen_q, max_seqlen_k, window_size_left, window_size_right, softmax_scale, softcap,
+                   alibi_slopes, alibi_batch_stride, sink);
+        dense_strides(p, seqlen_q, max_seqlen_k, num_heads, num_heads_k, head_size);
+        paged_kv(p, block_table, block_table_stride, page_block_size, num_heads_k, head_size);
+        p.seqused_k = (const int*)cache_seqlens;         // non-cumulative (paged_attn.cpp:518-519)
+        p.leftpad_k = (const int*)cache_leftpad;
+        p.kv_fp8 = kv_dtype == 1; p.k_scale = k_scale; p.v_scale = v_scale;
+        run_fwd(p, !is_fp16, stream, num_splits);
+    } catch (...) {
+        fail(9, "internal error in %s", entry);
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+void fmha_fwd_strided(void* q, void* k, void* v, void* o, void* alibi_slopes, void* softmax_lse,
+                      int32_t seqlen_q, int32_t seqlen_k, int32_t batch_size, int32_t num_heads,
+                      int32_t num_heads_k, int32_t head_size, const int64_t* st,
+                      float softmax_scale, int window_size_left, int window_size_right,
+                      float softcap, bool is_fp16, int num_splits, hipStream_t stream,
+                      float p_dropout, void* s_dmask) {
+    fwd_strided_entry("fmha_fwd_strided", q, k, v, o, alibi_slopes, softmax_lse, seqlen_q, seqlen_k,
+                      batch_size, num_heads, num_heads_k, head_size, st, softmax_scale,
+                      window_size_left, window_size_right, softcap, is_fp16, num_splits, stream,
+                      p_dropout, s_dmask, nullptr);
+}
+
+void fmha_fwd_sink(void* q, void* k, void* v, void* o, void* alibi_slopes, void* softmax_lse,
+                   int32_t seqlen_q, int32_t seqlen_k, int32_t batch_size, int32_t num_heads,
+                   int32_t num_heads_k, int32_t head_size, const int64_t* st,
+                   float softmax_scale, int window_size_left, int window_size_right,
+                   float softcap, bool is_fp16, int num_splits, hipStream_t stream,
+                   float p_dropout, void* s_dmask, const float* sink) {
+    fwd_strided_entry("fmha_fwd_sink", q, k, v, o, alibi_slopes, softmax_lse, seqlen_q, seqlen_k,
+                      batch_size, num_heads, num_heads_k, head_size, st, softmax_scale,
+                      window_size_left, window_size_right, softcap, is_fp16, num_splits, stream,
+                      p_dropout, s_dmask, sink);
+}
+
+void fmha_varlen_fwd_ex(void* q, void* k, void* v, void* o, void* softmax_lse,
+                        void* cu_seqlens_q, void* cu_seqlens_k, void* seqused_k,
+                        void* block_table, int32_t block_table_stride, int32_t page_block_size,
+                        void* alibi_slopes, int32_t alibi_batch_stride,
+                        int32_t max_seqlen_q, int32_t max_seqlen_k, int32_t total_q,
+                        int32_t batch_size, int32_t num_heads, int32_t num_heads_k,
+                        int32_t head_size, float softmax_scale, int window_size_left,
+                        int window_size_right, float softcap, bool is_fp16, hipStream_t stream,
+                        float p_dropout, void* s_dmask) {
+    varlen_fwd_entry("fmha_varlen_fwd_ex", q, k, v, o, softmax_lse, cu_seqlens_q, cu_seqlens_k,
+                     seqused_k, block_table, block_table_stride, page_block_size, alibi_slopes,
+                     alibi_batch_stride, max_seqlen_q, max_seqlen_k, total_q, batch_size, num_heads,
+                     num_heads_k, head_size, softmax_scale, window_size_left, window_size_right,
+                     softcap, is_fp16, stream, p_dropout, s_dmask, nullptr);
+}
+
+void fmha_varlen_fwd_sink(void* q, void* k, void* v, void* o, void* softmax_lse,
+                          void* cu_seqlens_q, void* cu_seqlens_k, void* seqused_k,
+                          void* block_table, int32_t block_table_stride, int32_t page_block_size,
+                          void* alibi_slopes, int32_t alibi_batch_stride,
+                          int32_t max_seqlen_q, int32_t max_seqlen_k, int32_t total_q,
+                          int32_t batch_size, int32_t num_heads, int32_t num_heads_k,
+                          int32_t head_size, float softmax_scale, int window_size_left,
+                          int window_size_right, float softcap, bool is_fp16, hipStream_t stream,
+                          float p_dropout, void* s_dmask, const float* sink) {
+    varlen_fwd_entry("fmha_varlen_fwd_sink", q, k, v, o, softmax_lse, cu_seqlens_q, cu_seqlens_k,
+                     seqused_k, block_table, block_table_stride, page_block_size, alibi_slopes,
+                     alibi_batch_stride, max_seqlen_q, max_seqlen_k, total_q, batch_size, num_heads,
+                     num_heads_k, head_size, softmax_scale, window_size_left, window_size_right,
+                     softcap, is_fp16, stream, p_dropout, s_dmask, sink);
 }
 
 void fmha_varlen_fwd(void* q_ptrs, void* k_ptrs, void* v_ptrs, void* o_ptrs,
@@ -844,33 +993,30 @@ void fmha_page_kvcache_fwd_ex(void* q, void* kcache, void* vcache, void* o, void
                               void* alibi_slopes, int32_t alibi_batch_stride, int32_t num_splits,
                               int32_t kv_dtype, float k_scale, float v_scale,
                               void* cache_leftpad, bool is_fp16, hipStream_t stream) {
-    try {
-        begin_fwd();
-        if (!check_common(q, kcache, vcache, o, batch_size, num_heads, num_heads_k, head_size)) return;
-        REQUIRE(block_table, "block_table must be given for the paged KV path");
-        REQUIRE(page_block_size > 0, "page_block_size must be positive");
-        REQUIRE(seqlen_q > 0 && max_seqlen_k > 0, "seqlen_q / seqlen_k must be positive");
-        REQUIRE(kv_dtype == 0 || kv_dtype == 1, "kv_dtype must be 0 (same as q) or 1 (fp8 e4m3fn)");
-        REQUIRE(block_table_stride > 0, "block_table_stride must be positive");
-        // export.cpp:1627-1628 (commented out in the reference): no paged KV with leftpad
-        REQUIRE(!cache_leftpad || max_seqlen_k <= page_block_size,
-                "cache_leftpad needs a non-paged cache (one page per sequence): Paged KV and "
-                "leftpad_k are not supported at the same time");
-        if (!slab_ok("q/o", seqlen_q, (int64_t)num_heads * head_size, 2) ||
-            !slab_ok("kcache/vcache page", page_block_size, (int64_t)num_heads_k * head_size, kv_dtype == 1 ? 1 : 2)) return;
-        FwdParams p{};
-        fwd_common(p, q, kcache, vcache, o, softmax_lse, batch_size, num_heads, num_heads_k, head_size,
-                   seqlen_q, max_seqlen_k, window_size_left, window_size_right, softmax_scale, softcap,
-                   alibi_slopes, alibi_batch_stride);
-        dense_strides(p, seqlen_q, max_seqlen_k, num_heads, num_heads_k, head_size);
-        paged_kv(p, block_table, block_table_stride, page_block_size, num_heads_k, head_size);
-        p.seqused_k = (const int*)cache_seqlens;         // non-cumulative (paged_attn.cpp:518-519)
-        p.leftpad_k = (const int*)cache_leftpad;
-        p.kv_fp8 = kv_dtype == 1; p.k_scale = k_scale; p.v_scale = v_scale;
-        run_fwd(p, !is_fp16, stream, num_splits);
-    } catch (...) {
-        fail(9, "internal error in fmha_page_kvcache_fwd_ex");
-    }
+    page_kvcache_entry("fmha_page_kvcache_fwd_ex", q, kcache, vcache, o, softmax_lse, block_table,
+                       block_table_stride, cache_seqlens, seqlen_q, max_seqlen_k, batch_size,
+                       num_heads, num_heads_k, head_size, page_block_size, softmax_scale,
+                       window_size_left, window_size_right, softcap, alibi_slopes,
+                       alibi_batch_stride, num_splits, kv_dtype, k_scale, v_scale, cache_leftpad,
+                       is_fp16, stream, nullptr);
+}
+
+void fmha_page_kvcache_fwd_sink(void* q, void* kcache, void* vcache, void* o, void* softmax_lse,
+                                void* block_table, int32_t block_table_stride, void* cache_seqlens,
+                                int32_t seqlen_q, int32_t max_seqlen_k, int32_t batch_size,
+                                int32_t num_heads, int32_t num_heads_k, int32_t head_size,
+                                int32_t page_block_size, float softmax_scale,
+                                int window_size_left, int window_size_right, float softcap,
+                                void* alibi_slopes, int32_t alibi_batch_stride, int32_t num_splits,
+                                int32_t kv_dtype, float k_scale, float v_scale,
+                                void* cache_leftpad, bool is_fp16, hipStream_t stream,
+                                const float* sink) {
+    page_kvcache_entry("fmha_page_kvcache_fwd_sink", q, kcache, vcache, o, softmax_lse, block_table,
+                       block_table_stride, cache_seqlens, seqlen_q, max_seqlen_k, batch_size,
+                       num_heads, num_heads_k, head_size, page_block_size, softmax_scale,
+                       window_size_left, window_size_right, softcap, alibi_slopes,
+                       alibi_batch_stride, num_splits, kv_dtype, k_scale, v_scale, cache_leftpad,
+                       is_fp16, stream, sink);
 }
 
 }  // extern "C"
@@ -1171,6 +1317,27 @@ void fmha_varlen_bwd(void* dout, void* q, void* k, void* v, void* out, void* sof
                 "varlen backward launch");
     } catch (...) {
         fail(9, "internal error in fmha_varlen_bwd");
+    }
+}
+
+void fmha_bwd_sink(const float* softmax_lse, const float* softmax_d, const float* sink, float* dsink,
+                   int32_t batch, int32_t num_heads, int32_t rows, int64_t batch_stride,
+                   int64_t head_stride, hipStream_t stream) {
+    try {
+        clear_error();
+        REQUIRE(softmax_lse && softmax_d && sink && dsink,
+                "softmax_lse, softmax_d, sink and dsink must be non-null device pointers");
+        REQUIRE(batch > 0 && num_heads > 0 && rows > 0,
+                "batch, num_heads and rows must be positive (got %d, %d, %d)", batch, num_heads, rows);
+        REQUIRE(batch_stride >= 0 && head_stride >= rows,
+                "strides: batch_stride must be non-negative and head_stride at least rows");
+        SinkBwdParams p{};
+        p.lse = softmax_lse; p.dsum = softmax_d; p.sink = sink; p.dsink = dsink;
+        p.b = batch; p.h = num_heads; p.rows = rows;
+        p.batch_stride = batch_stride; p.head_stride = head_stride;
+        hip_ok(launch_bwd_sink(p, stream), "sink backward launch");
+    } catch (...) {
+        fail(9, "internal error in fmha_bwd_sink");
     }
 }
 

@@ -203,4 +203,49 @@ hipError_t launch_lse_alibi(const LseAlibiParams& p, hipStream_t st) {
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------- attention-sink post-pass
+// One thread per 16-byte chunk of an O row, d / 8 threads per (row, head), 256 / (d / 8) rows per
+// workgroup; the row's LSE and sink[head] are one address for all of its threads (one request per
+// wave).  fp32 arithmetic, rounded once to T.  The barrier orders every read of a row's LSE
+// before its one write (the threads of a row may sit in two waves when d / 8 does not divide 64).
+template <typename T>
+__global__ void __launch_bounds__(256) fmha_sink_kernel(const SinkPassParams p) {
+    const int cpr = p.d >> 3, rpb = 256 / cpr;
+    const int t = threadIdx.x, ri = t / cpr, c = t - ri * cpr;
+    const int64_t rh = (int64_t)blockIdx.x * rpb + ri;
+    const bool ok = ri < rpb && rh < (int64_t)p.b * p.rows * p.h;
+    float l0 = INFINITY, s = 0.f;
+    int64_t li = 0;
+    T* orow = nullptr;
+    if (ok) {
+        const int head = (int)(rh % p.h);
+        const int64_t r = rh / p.h;
+        const int64_t bi = r / p.rows, pos = r - bi * p.rows;
+        li = bi * p.lse_batch + (int64_t)head * p.lse_head + pos;
+        orow = reinterpret_cast<T*>(p.o) + bi * p.o_batch + pos * p.o_row + (int64_t)head * p.o_head;
+        l0 = p.lse[li];
+        s = p.sink[head];
+    }
+    __syncthreads();
+    if (!ok || l0 == INFINITY) return;       // no visible key: O = 0 and LSE = +inf stay
+    const SinkMerge sm = sink_merge(l0, s);
+    if (c == 0) p.lse[li] = sm.lse;
+    if (sm.f == 1.f) return;                 // (a sink of -inf leaves O untouched)
+    float x[8];
+    load8(orow + 8 * c, x);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) x[i] *= sm.f;
+    store8(orow + 8 * c, x);
+}
+
+hipError_t launch_sink_pass(const SinkPassParams& p, bool fp16, hipStream_t st) {
+    const int rpb = 256 / (p.d / 8);
+    const int64_t rh = (int64_t)p.b * p.rows * p.h;
+    if (rh <= 0) return hipSuccess;
+    const dim3 grid((unsigned)((rh + rpb - 1) / rpb));
+    if (fp16) hipLaunchKernelGGL(fmha_sink_kernel<_Float16>, grid, dim3(256), 0, st, p);
+    else hipLaunchKernelGGL(fmha_sink_kernel<__bf16>, grid, dim3(256), 0, st, p);
+    return hipGetLastError();
+}
+
 }  // namespace xfa

@@ -56,6 +56,41 @@ static hipError_t launch_bwd_impl(const BwdParams& p, hipStream_t st) {
     return hipGetLastError();
 }
 
+#if XFA_HD == 64 && XFA_DT_BF16
+// Gradient of the attention sink (one copy in the library: it knows no head dim or dtype):
+// dsink[h] = - sum over (batch, row) of exp(sink[h] - LSE) * D, D = rowsum(dO * O) as the
+// backward's preprocess wrote it; rows without keys (LSE = +inf) add nothing.  One workgroup
+// per head; thread t sums rows t, t + 256, .. of batch 0, 1, .. in that order, then a fixed LDS
+// tree: no atomics, so the result is bitwise reproducible.  LSE and D are read with coalesced
+// 4-byte loads (a head's rows start at any multiple of 4 bytes).
+__global__ void __launch_bounds__(256) fmha_bwd_sink_kernel(const SinkBwdParams p) {
+    __shared__ float red[256];
+    const int h = blockIdx.x, t = threadIdx.x;
+    const float s = p.sink[h];
+    float acc = 0.f;
+    for (int b = 0; b < p.b; ++b) {
+        const int64_t base = (int64_t)b * p.batch_stride + (int64_t)h * p.head_stride;
+        for (int r = t; r < p.rows; r += 256) {
+            const float l = p.lse[base + r];
+            if (l != INFINITY) acc += __expf(s - l) * p.dsum[base + r];
+        }
+    }
+    red[t] = acc;
+    __syncthreads();
+#pragma unroll
+    for (int w = 128; w >= 1; w >>= 1) {
+        if (t < w) red[t] += red[t + w];
+        __syncthreads();
+    }
+    if (t == 0) p.dsink[h] = -red[0];
+}
+
+hipError_t launch_bwd_sink(const SinkBwdParams& p, hipStream_t st) {
+    hipLaunchKernelGGL(fmha_bwd_sink_kernel, dim3(p.h), dim3(256), 0, st, p);
+    return hipGetLastError();
+}
+#endif
+
 hipError_t XFA_FN(XFA_HD, XFA_DTN)(const BwdParams& p, hipStream_t st) {
     return launch_bwd_impl<XFA_HD, elem_t>(p, st);
 }

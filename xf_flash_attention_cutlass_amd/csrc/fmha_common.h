@@ -167,7 +167,22 @@ struct FwdParams {
     const float* k_descale;
     const float* v_descale;
     int ds_batch, ds_head;
+    // attention sink (the _sink entries): fp32 [h], one logit per QUERY head in the units of the
+    // scaled scores, or null (sink_merge below)
+    const float* sink;
 };
+
+// Attention sink: one extra logit s in a row's softmax denominator that carries no value.  From
+// the sink-free log-sum-exp l0 (finite, or -inf) of a row: the factor f = 1 / (1 + exp(s - l0))
+// on its normalised output and its log-sum-exp log(exp(l0) + exp(s)), in the form that never
+// exponentiates s or l0 alone (s = 50 against scores near -50 stays finite).  s = -inf gives
+// f = 1 and lse = l0 exactly.  Every sink mechanism (forward epilogue, split combine, post-pass)
+// computes both here; rows without a visible key (O = 0, LSE = +inf) are the caller's to skip.
+struct SinkMerge { float f, lse; };
+__device__ __forceinline__ SinkMerge sink_merge(const float l0, const float s) {
+    const float d = s - l0;
+    return SinkMerge{1.f / (1.f + __expf(d)), fmaxf(l0, s) + log1pf(__expf(-fabsf(d)))};
+}
 
 // The fp8 forward's descales of item (batch, kv head), workgroup-uniform.  DSC = true (the
 // instantiation the _ex entries launch): read from the device tensors with scalar loads; false:
@@ -213,6 +228,7 @@ struct CombineParams {
     int64_t lse_batch, lse_head;
     int b, h, seqlen_q, d, hd, num_splits;
     const int* dec_ns;   // per-batch split counts (balanced decode), or null: num_splits
+    const float* sink;   // attention sink [h] merged after the splits, or null
 };
 
 struct BwdParams {

@@ -42,6 +42,7 @@ static hipError_t launch_combine(const FwdParams& p, int hd, hipStream_t st,
     cp.b = p.b; cp.h = p.h; cp.seqlen_q = p.seqlen_q; cp.d = p.d; cp.hd = hd;
     cp.num_splits = p.num_splits;
     cp.dec_ns = p.decode && p.dec_bal ? p.dec_ns : nullptr;
+    cp.sink = p.sink;
     const int64_t crow = (int64_t)p.b * p.h * p.seqlen_q;
     const int ext = cp.dec_ns ? p.dec_cap : p.num_splits;
     // few rows (the decode shapes): one workgroup per row, all of its partials in flight at once
@@ -90,6 +91,8 @@ static hipError_t launch_decode(const FwdParams& p, hipStream_t st) {
     }
     e = hipGetLastError();
     if (e != hipSuccess) return e;
+    // an attention sink joins in the combine; the folded merge stays sink-free (post-pass)
+    if (p.sink) note_sink(p.dec_ctr ? kSinkPass : kSinkCombine);
     if (p.dec_ctr) return hipSuccess;          // the last split of each (b, kv head) merged
     return launch_combine(p, HD, st, fmha_combine_kernel<HD, T>,
                           (HD == 64 || HD == 128 || HD == 256) ? fmha_combine_row_kernel<HD, T> : nullptr);
@@ -102,12 +105,21 @@ static hipError_t launch_fwd_nw(const FwdParams& p, hipStream_t st) {
     const bool feat = p.alibi || p.softcap_pre > 0.f || p.block_table || p.kv_fp8 || p.drop;
     const FwdPlan s = plan_fwd(p, NW * 32, p.num_cus * p.persist_per_cu, p.num_splits, kFwdQueue);
     const size_t smem = (size_t)(fwd_nbuf(HD) * 2 * kBlockN * HD * 2);
+    // SINK: the sink in the epilogue; a split launch keeps its partials sink-free (the combine
+    // merges the sink), so it runs the plain instantiation
+    const bool sink = p.sink && p.num_splits <= 1;
     void (*kern)(const FwdParams) =
-        mask ? (feat ? fmha_fwd_kernel<HD, T, NW, true, true> : fmha_fwd_kernel<HD, T, NW, true, false>)
-             : (feat ? fmha_fwd_kernel<HD, T, NW, false, true> : fmha_fwd_kernel<HD, T, NW, false, false>);
+        sink ? (mask ? (feat ? fmha_fwd_sink_kernel<HD, T, NW, true, true> : fmha_fwd_sink_kernel<HD, T, NW, true, false>)
+                     : (feat ? fmha_fwd_sink_kernel<HD, T, NW, false, true> : fmha_fwd_sink_kernel<HD, T, NW, false, false>))
+             : (mask ? (feat ? fmha_fwd_kernel<HD, T, NW, true, true> : fmha_fwd_kernel<HD, T, NW, true, false>)
+                     : (feat ? fmha_fwd_kernel<HD, T, NW, false, true> : fmha_fwd_kernel<HD, T, NW, false, false>));
     allow_lds<fmha_fwd_kernel<HD, T, NW, true, true>, fmha_fwd_kernel<HD, T, NW, true, false>,
-              fmha_fwd_kernel<HD, T, NW, false, true>, fmha_fwd_kernel<HD, T, NW, false, false>>(p.device, (int)smem);
+              fmha_fwd_kernel<HD, T, NW, false, true>, fmha_fwd_kernel<HD, T, NW, false, false>,
+              fmha_fwd_sink_kernel<HD, T, NW, true, true>, fmha_fwd_sink_kernel<HD, T, NW, true, false>,
+              fmha_fwd_sink_kernel<HD, T, NW, false, true>, fmha_fwd_sink_kernel<HD, T, NW, false, false>>(p.device, (int)smem);
     hipError_t e = launch_planned(NW == 8 ? "fmha_fwd_kernel<8 waves>" : "fmha_fwd_kernel<4 waves>", kern, s, NW * 64, smem, st);
+    // an attention sink: in this kernel's epilogue, or after the splits in the combine
+    if (p.sink) note_sink(p.num_splits > 1 ? kSinkCombine : kSinkEpilogue);
     if (e != hipSuccess || p.num_splits <= 1) return e;
     return launch_combine(p, HD, st, fmha_combine_kernel<HD, T>,
                           (HD == 64 || HD == 128 || HD == 256) ? fmha_combine_row_kernel<HD, T> : nullptr);
@@ -148,6 +160,7 @@ static hipError_t launch_fwdpp(const FwdParams& p, hipStream_t st) {
 }
 
 static hipError_t launch_fwd4(const FwdParams& p, hipStream_t st) {
+    if (p.sink) note_sink(kSinkPass);   // generated bodies: their epilogues know no sink
     if (p.fwd4 >= 2) return launch_fwdpp(p, st);
 #if !XFA_VARIANTS
     return hipErrorNotSupported;   // (fmha_set_option refuses fwd_w4 = 1 in this build)

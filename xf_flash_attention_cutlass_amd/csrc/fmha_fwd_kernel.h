@@ -37,8 +37,11 @@ namespace xfa {
 constexpr bool SCHED_FENCE = XFA_SCHED_FENCE;
 
 
-// One work item = (batch x kv-head, query row block, split).
-template <int HD, typename T, int NW, bool MASK, bool FEAT>
+// One work item = (batch x kv-head, query row block, split).  SINK: the instantiation the _sink
+// entries launch, whose epilogue merges the attention sink; the others compile to the code they
+// had before sinks existed (a runtime branch in the shared epilogue measured + 0.75 % on the
+// B2 S4096 H64/Hk8 D64 window (127, 0) forward, profiles/sink_ab.log).
+template <int HD, typename T, int NW, bool MASK, bool FEAT, bool SINK = false>
 __device__ __forceinline__ void fwd_item(const FwdParams& p, char* smem, const int bh,
                                          const int m_block, const int split) {
     using V8 = typename DT<T>::v8;
@@ -741,6 +744,20 @@ __device__ __forceinline__ void fwd_item(const FwdParams& p, char* smem, const i
     }
     T* orow = reinterpret_cast<T*>(p.o) + (int64_t)bidx * p.o_batch +
               (int64_t)(q_off + pos) * p.o_row + (int64_t)head * p.o_head;
+    if constexpr (SINK) {
+        // attention sink, once per row, outside the key loop: `head` is the query head (GQA rows
+        // are packed per kv head); the entries refuse dropout with a sink, so no rp_keep here
+        float inv_o = inv, lse_o = INFINITY;
+        if (!empty) {
+            const SinkMerge sm = sink_merge((m_sc + __log2f(l_full)) * kLn2, p.sink[head]);
+            inv_o = inv * sm.f;
+            lse_o = sm.lse;
+        }
+        store_o_row16<T, ND>(orow, acc_o, inv_o, p.d, hh);
+        if (p.lse && hh == 0)
+            p.lse[(int64_t)bidx * p.lse_batch + (int64_t)head * p.lse_head + q_off + pos] = lse_o;
+        return;
+    }
     store_o_row16<T, ND>(orow, acc_o, (FEAT && p.drop) ? inv * p.rp_keep : inv, p.d, hh);
     if (p.lse && hh == 0) {
         p.lse[(int64_t)bidx * p.lse_batch + (int64_t)head * p.lse_head + q_off + pos] =
@@ -764,6 +781,14 @@ __global__ void __launch_bounds__(NW * 64, fwd_waves_per_simd(HD)) fmha_fwd_kern
         p.rng_out[1] = (int64_t)doff;
     }
     fwd_walk<kFwdQueue>(p, [&](int bh, int m_block) { fwd_item<HD, T, NW, MASK, FEAT>(p, smem, bh, m_block, blockIdx.z); });
+}
+
+// The same launch with an attention sink merged in the epilogue (one split, no dropout: the
+// _sink entries refuse it); reported under fmha_fwd_kernel's name with " sink=epilogue".
+template <int HD, typename T, int NW, bool MASK, bool FEAT>
+__global__ void __launch_bounds__(NW * 64, fwd_waves_per_simd(HD)) fmha_fwd_sink_kernel(const FwdParams p) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    fwd_walk<kFwdQueue>(p, [&](int bh, int m_block) { fwd_item<HD, T, NW, MASK, FEAT, true>(p, smem, bh, m_block, blockIdx.z); });
 }
 
 // Split-KV combine: lse = log sum_s exp(lse_s); O = sum_s exp(lse_s - lse) O_s
@@ -794,7 +819,10 @@ __global__ void __launch_bounds__(256) fmha_combine_kernel(const CombineParams c
 #pragma unroll
     for (int off = 16; off >= 1; off >>= 1) sum += __shfl_xor(sum, off);
     const bool empty = (mx == -INFINITY) || sum == 0.f;
-    const float lse = empty ? INFINITY : __logf(sum) + mx;
+    float lse = empty ? INFINITY : __logf(sum) + mx;
+    // attention sink: merged once after the splits; the partials are then weighted against the
+    // merged LSE, which is also the one stored
+    if (cp.sink && !empty) lse = sink_merge(lse, cp.sink[head]).lse;
     constexpr int PER = HD / 64;
     constexpr int CU = 8;
     typedef float __attribute__((ext_vector_type(PER))) fv;
@@ -869,7 +897,8 @@ __global__ void __launch_bounds__(256) fmha_combine_row_kernel(const CombinePara
 #pragma unroll
         for (int off = 16; off >= 1; off >>= 1) sum += __shfl_xor(sum, off);
         const bool empty = (mx == -INFINITY) || sum == 0.f;
-        const float lse = empty ? INFINITY : __logf(sum) + mx;
+        float lse = empty ? INFINITY : __logf(sum) + mx;
+        if (cp.sink && !empty) lse = sink_merge(lse, cp.sink[head]).lse;   // (as fmha_combine_kernel)
         wsh[t] = empty ? 0.f : __expf(l0 - lse);
         wsh[t + 64] = empty ? 0.f : __expf(l1 - lse);
         if (cp.lse && t == 0) cp.lse[(int64_t)bidx * cp.lse_batch + (int64_t)head * cp.lse_head + pos] = lse;

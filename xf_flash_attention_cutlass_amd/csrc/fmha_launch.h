@@ -88,6 +88,12 @@ Options& options();
 // 3 dynamic queue), the per-XCD queues flag and the grid.  Thread-local, set by the launchers.
 void note_launch(const char* kernel, int persistent, int xcdq, unsigned gx, unsigned gy, unsigned gz, int block);
 
+// Which mechanism applies the attention sink of a launch with p.sink: the
+// launcher records it, the C ABI then runs the post-pass where it is kSinkPass and names the
+// mechanism in fmha_last_kernel().  Thread-local, cleared by every forward entry.
+enum SinkMech { kSinkNone = 0, kSinkEpilogue, kSinkCombine, kSinkPass };
+void note_sink(SinkMech mech);
+
 // The schedule of one forward launch, shared by every forward launcher: the params as the
 // kernel gets them (n_mblocks, persistent, xcd_queues filled in) and the grid.  An item is one
 // row block of `rows_per_item` query rows (seqlen_q * group of them) of one (b, kv head);
@@ -210,6 +216,33 @@ struct LseAlibiParams {
     int64_t lse_batch, lse_head;
 };
 hipError_t launch_lse_alibi(const LseAlibiParams& p, hipStream_t st);
+
+// Attention-sink post-pass (fmha_append.hip), for launches that end in a generated body or in
+// the folded decode merge: in place, O[row] *= f and LSE[row] = merged over all (batch, row,
+// head) with f and the merged LSE from sink_merge(LSE[row], sink[head]).  O by the call's own
+// element strides, LSE [.., rows] by its strides; a packed (varlen) launch is batch 1 with
+// rows = total_q.  Rows with f == 1 are not stored, rows without keys (LSE = +inf) are left alone.
+struct SinkPassParams {
+    void* o;
+    float* lse;
+    const float* sink;
+    int64_t o_batch, o_row, o_head;
+    int64_t lse_batch, lse_head;
+    int b, h, rows, d;
+};
+hipError_t launch_sink_pass(const SinkPassParams& p, bool fp16, hipStream_t st);
+
+// Gradient of the attention sink (fmha_bwd.hip): dsink[h] = - sum_(b, row) exp(sink[h] - LSE) D
+// over LSE / D [b][h][rows] by element strides
+struct SinkBwdParams {
+    const float* lse;
+    const float* dsum;
+    const float* sink;
+    float* dsink;
+    int b, h, rows;
+    int64_t batch_stride, head_stride;
+};
+hipError_t launch_bwd_sink(const SinkBwdParams& p, hipStream_t st);
 
 // D = 256 (bucket of 129..256): 4 waves x 32 rows, one wave per SIMD (512 registers:
 // Q fragments and the O accumulator alone are 192), no LDS-DMA pipeline

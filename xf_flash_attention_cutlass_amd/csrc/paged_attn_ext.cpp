@@ -141,6 +141,17 @@ struct RngDisarm {
     ~RngDisarm() { fmha_set_rng_state_device(nullptr, nullptr, 0, nullptr); }
 };
 
+// The sink of the _sink ops: fp32 [num_heads], contiguous, on q's device (null when absent).
+const float* sink_for_c(const c10::optional<at::Tensor>& sink_, const at::Tensor& q, int num_heads) {
+    if (!sink_.has_value()) return nullptr;
+    const at::Tensor& s = sink_.value();
+    TORCH_CHECK(s.dtype() == torch::kFloat32, "sink must have dtype fp32");
+    TORCH_CHECK(s.is_cuda() && s.device() == q.device(), "sink must be on q's device");
+    TORCH_CHECK(s.dim() == 1 && s.size(0) == num_heads, "sink must have shape (num_heads)");
+    CHECK_CONTIGUOUS(s);
+    return s.data_ptr<float>();
+}
+
 at::Tensor sdmask_buffer(bool want, const at::TensorOptions& opts, int b, int h, int sq, int sk) {
     if (!want) return at::Tensor();
     auto r128 = [](int x) { return (x + 127) / 128 * 128; };
@@ -149,11 +160,12 @@ at::Tensor sdmask_buffer(bool want, const at::TensorOptions& opts, int b, int h,
 
 }  // namespace
 
-std::vector<at::Tensor>
-mha_fwd(at::Tensor& q, const at::Tensor& k, const at::Tensor& v, c10::optional<at::Tensor>& out_,
+static std::vector<at::Tensor>
+mha_fwd_impl(at::Tensor& q, const at::Tensor& k, const at::Tensor& v, c10::optional<at::Tensor>& out_,
         c10::optional<at::Tensor>& alibi_slopes_, const float p_dropout, const float softmax_scale,
         bool is_causal, int window_size_left, int window_size_right, const float softcap,
-        const bool return_softmax, c10::optional<at::Generator> gen_) {
+        const bool return_softmax, c10::optional<at::Generator> gen_,
+        const c10::optional<at::Tensor>& sink_) {
     check_qkv_dtype(q, k, v);
     const auto sizes = q.sizes();
     TORCH_CHECK(q.dim() == 4, "q must be (batch, seqlen, heads, head_size)");
@@ -206,7 +218,21 @@ mha_fwd(at::Tensor& q, const at::Tensor& k, const at::Tensor& v, c10::optional<a
     int64_t alibi_bs = 0;
     at::Tensor alibi = alibi_for_c(alibi_slopes_, batch_size, num_heads, &alibi_bs);
 
-    if (seqlen_k > 0 && strided) {
+    const float* sink = sink_for_c(sink_, q, num_heads);
+    if (seqlen_k > 0 && sink) {
+        // (the padded copies by their own strides where the views cannot run in place)
+        const at::Tensor &qs = strided ? q : q_padded, &ks = strided ? k : k_padded, &vs = strided ? v : v_padded;
+        const int64_t st[12] = {qs.stride(0), qs.stride(1), qs.stride(2), ks.stride(0), ks.stride(1),
+                                ks.stride(2), vs.stride(0), vs.stride(1), vs.stride(2), out.stride(0),
+                                out.stride(1), out.stride(2)};
+        fmha_fwd_sink(qs.data_ptr(), ks.data_ptr(), vs.data_ptr(), out.data_ptr(),
+                      alibi.defined() ? alibi.data_ptr() : nullptr, softmax_lse.data_ptr(),
+                      seqlen_q, seqlen_k, batch_size, num_heads, num_heads_k, head_size, st,
+                      softmax_scale, window_size_left, window_size_right, softcap,
+                      q.dtype() == torch::kFloat16, 0, cur_stream(), p_dropout,
+                      p.defined() ? p.data_ptr() : nullptr, sink);
+        raise_if_failed("fwd_sink");
+    } else if (seqlen_k > 0 && strided) {
         const int64_t st[12] = {q.stride(0), q.stride(1), q.stride(2), k.stride(0), k.stride(1),
                                 k.stride(2), v.stride(0), v.stride(1), v.stride(2), out.stride(0),
                                 out.stride(1), out.stride(2)};
@@ -235,14 +261,34 @@ mha_fwd(at::Tensor& q, const at::Tensor& k, const at::Tensor& v, c10::optional<a
 }
 
 std::vector<at::Tensor>
-mha_varlen_fwd(at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+mha_fwd(at::Tensor& q, const at::Tensor& k, const at::Tensor& v, c10::optional<at::Tensor>& out_,
+        c10::optional<at::Tensor>& alibi_slopes_, const float p_dropout, const float softmax_scale,
+        bool is_causal, int window_size_left, int window_size_right, const float softcap,
+        const bool return_softmax, c10::optional<at::Generator> gen_) {
+    return mha_fwd_impl(q, k, v, out_, alibi_slopes_, p_dropout, softmax_scale, is_causal,
+                        window_size_left, window_size_right, softcap, return_softmax, gen_, c10::nullopt);
+}
+
+// `fwd` plus a trailing sink (fp32 [num_heads]): fmha_fwd_sink
+std::vector<at::Tensor>
+mha_fwd_sink(at::Tensor& q, const at::Tensor& k, const at::Tensor& v, c10::optional<at::Tensor>& out_,
+             c10::optional<at::Tensor>& alibi_slopes_, const float p_dropout, const float softmax_scale,
+             bool is_causal, int window_size_left, int window_size_right, const float softcap,
+             const bool return_softmax, c10::optional<at::Generator> gen_, const at::Tensor& sink) {
+    return mha_fwd_impl(q, k, v, out_, alibi_slopes_, p_dropout, softmax_scale, is_causal,
+                        window_size_left, window_size_right, softcap, return_softmax, gen_, sink);
+}
+
+static std::vector<at::Tensor>
+mha_varlen_fwd_impl(at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
                c10::optional<at::Tensor>& out_, const at::Tensor& cu_seqlens_q,
                const at::Tensor& cu_seqlens_k, c10::optional<at::Tensor>& seqused_k,
                c10::optional<at::Tensor>& block_table_, c10::optional<at::Tensor>& alibi_slopes_,
                int max_seqlen_q, const int max_seqlen_k, const float p_dropout,
                const float softmax_scale, const bool zero_tensors, bool is_causal,
                int window_size_left, int window_size_right, const float softcap,
-               const bool return_softmax, c10::optional<at::Generator> gen_) {
+               const bool return_softmax, c10::optional<at::Generator> gen_,
+               const c10::optional<at::Tensor>& sink_) {
     check_qkv_dtype(q, k, v);
     TORCH_CHECK(cu_seqlens_q.dtype() == torch::kInt32, "cu_seqlens_q must have dtype int32");
     TORCH_CHECK(cu_seqlens_k.dtype() == torch::kInt32, "cu_seqlens_k must have dtype int32");
@@ -323,7 +369,20 @@ mha_varlen_fwd(at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
     }
     int64_t alibi_bs = 0;
     at::Tensor alibi = alibi_for_c(alibi_slopes_, batch_size, num_heads, &alibi_bs);
-    if (max_seqlen_k > 0) {
+    const float* sink = sink_for_c(sink_, q, num_heads);
+    if (max_seqlen_k > 0 && sink) {
+        fmha_varlen_fwd_sink(q_padded.data_ptr(), k_padded.data_ptr(), v_padded.data_ptr(),
+                             out.data_ptr(), softmax_lse.data_ptr(), cu_seqlens_q.data_ptr(),
+                             cu_seqlens_k.data_ptr(), seqused.defined() ? seqused.data_ptr() : nullptr,
+                             paged_KV ? block_table.data_ptr() : nullptr,
+                             paged_KV ? (int)block_table.stride(0) : 0, page_block_size,
+                             alibi.defined() ? alibi.data_ptr() : nullptr, (int)alibi_bs,
+                             max_seqlen_q, max_seqlen_k, total_q, batch_size, num_heads, num_heads_k,
+                             head_size, softmax_scale, window_size_left, window_size_right, softcap,
+                             q.dtype() == torch::kFloat16, cur_stream(), p_dropout,
+                             p.defined() ? p.data_ptr() : nullptr, sink);
+        raise_if_failed("varlen_fwd_sink");
+    } else if (max_seqlen_k > 0) {
         fmha_varlen_fwd_ex(q_padded.data_ptr(), k_padded.data_ptr(), v_padded.data_ptr(),
                            out.data_ptr(), softmax_lse.data_ptr(), cu_seqlens_q.data_ptr(),
                            cu_seqlens_k.data_ptr(), seqused.defined() ? seqused.data_ptr() : nullptr,
@@ -346,7 +405,39 @@ mha_varlen_fwd(at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
 }
 
 std::vector<at::Tensor>
-mha_fwd_kvcache(at::Tensor& q, const at::Tensor& kcache, const at::Tensor& vcache,
+mha_varlen_fwd(at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+               c10::optional<at::Tensor>& out_, const at::Tensor& cu_seqlens_q,
+               const at::Tensor& cu_seqlens_k, c10::optional<at::Tensor>& seqused_k,
+               c10::optional<at::Tensor>& block_table_, c10::optional<at::Tensor>& alibi_slopes_,
+               int max_seqlen_q, const int max_seqlen_k, const float p_dropout,
+               const float softmax_scale, const bool zero_tensors, bool is_causal,
+               int window_size_left, int window_size_right, const float softcap,
+               const bool return_softmax, c10::optional<at::Generator> gen_) {
+    return mha_varlen_fwd_impl(q, k, v, out_, cu_seqlens_q, cu_seqlens_k, seqused_k, block_table_,
+                               alibi_slopes_, max_seqlen_q, max_seqlen_k, p_dropout, softmax_scale,
+                               zero_tensors, is_causal, window_size_left, window_size_right, softcap,
+                               return_softmax, gen_, c10::nullopt);
+}
+
+// `varlen_fwd` plus a trailing sink: fmha_varlen_fwd_sink
+std::vector<at::Tensor>
+mha_varlen_fwd_sink(at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+                    c10::optional<at::Tensor>& out_, const at::Tensor& cu_seqlens_q,
+                    const at::Tensor& cu_seqlens_k, c10::optional<at::Tensor>& seqused_k,
+                    c10::optional<at::Tensor>& block_table_, c10::optional<at::Tensor>& alibi_slopes_,
+                    int max_seqlen_q, const int max_seqlen_k, const float p_dropout,
+                    const float softmax_scale, const bool zero_tensors, bool is_causal,
+                    int window_size_left, int window_size_right, const float softcap,
+                    const bool return_softmax, c10::optional<at::Generator> gen_,
+                    const at::Tensor& sink) {
+    return mha_varlen_fwd_impl(q, k, v, out_, cu_seqlens_q, cu_seqlens_k, seqused_k, block_table_,
+                               alibi_slopes_, max_seqlen_q, max_seqlen_k, p_dropout, softmax_scale,
+                               zero_tensors, is_causal, window_size_left, window_size_right, softcap,
+                               return_softmax, gen_, sink);
+}
+
+static std::vector<at::Tensor>
+mha_fwd_kvcache_impl(at::Tensor& q, const at::Tensor& kcache, const at::Tensor& vcache,
                 c10::optional<const at::Tensor>& k_, c10::optional<const at::Tensor>& v_,
                 c10::optional<const at::Tensor>& seqlens_k_,
                 c10::optional<const at::Tensor>& rotary_cos_,
@@ -356,7 +447,8 @@ mha_fwd_kvcache(at::Tensor& q, const at::Tensor& kcache, const at::Tensor& vcach
                 c10::optional<at::Tensor>& out_, const float softmax_scale, bool is_causal,
                 int window_size_left, int window_size_right, const float softcap,
                 bool is_rotary_interleaved, int num_splits,
-                c10::optional<const at::Tensor>& cache_leftpad_) {
+                c10::optional<const at::Tensor>& cache_leftpad_,
+                const c10::optional<at::Tensor>& sink_) {
     check_qkv_dtype(q, kcache, vcache);
     const bool append = k_.has_value();
     const bool local_or_causal = is_causal || window_size_left >= 0 || window_size_right >= 0;
@@ -500,20 +592,95 @@ mha_fwd_kvcache(at::Tensor& q, const at::Tensor& kcache, const at::Tensor& vcach
         TORCH_CHECK(!rotary_cos_.has_value(),
                     "If rotary cos/sin are provided, new key / value to be appended to KV cache must also be provided");
     }
-    fmha_page_kvcache_fwd_ex(q_attn.data_ptr(), kc.data_ptr(), vc.data_ptr(), out.data_ptr(),
-                             softmax_lse.data_ptr(), block_table.data_ptr(),
-                             (int)block_table.stride(0),
-                             seqlens.defined() ? seqlens.data_ptr() : nullptr, seqlen_q, seqlen_k,
-                             batch_size, num_heads, num_heads_k, head_size, page_block_size,
-                             softmax_scale, window_size_left, window_size_right, softcap,
-                             alibi.defined() ? alibi.data_ptr() : nullptr, (int)alibi_bs,
-                             num_splits, 0, 1.f, 1.f,
-                             leftpad.defined() ? leftpad.data_ptr() : nullptr,
-                             q.dtype() == torch::kFloat16, cur_stream());
-    raise_if_failed("fwd_kvcache");
+    if (const float* sink = sink_for_c(sink_, q, num_heads)) {
+        fmha_page_kvcache_fwd_sink(q_attn.data_ptr(), kc.data_ptr(), vc.data_ptr(), out.data_ptr(),
+                                   softmax_lse.data_ptr(), block_table.data_ptr(),
+                                   (int)block_table.stride(0),
+                                   seqlens.defined() ? seqlens.data_ptr() : nullptr, seqlen_q, seqlen_k,
+                                   batch_size, num_heads, num_heads_k, head_size, page_block_size,
+                                   softmax_scale, window_size_left, window_size_right, softcap,
+                                   alibi.defined() ? alibi.data_ptr() : nullptr, (int)alibi_bs,
+                                   num_splits, 0, 1.f, 1.f,
+                                   leftpad.defined() ? leftpad.data_ptr() : nullptr,
+                                   q.dtype() == torch::kFloat16, cur_stream(), sink);
+        raise_if_failed("fwd_kvcache_sink");
+    } else {
+        fmha_page_kvcache_fwd_ex(q_attn.data_ptr(), kc.data_ptr(), vc.data_ptr(), out.data_ptr(),
+                                 softmax_lse.data_ptr(), block_table.data_ptr(),
+                                 (int)block_table.stride(0),
+                                 seqlens.defined() ? seqlens.data_ptr() : nullptr, seqlen_q, seqlen_k,
+                                 batch_size, num_heads, num_heads_k, head_size, page_block_size,
+                                 softmax_scale, window_size_left, window_size_right, softcap,
+                                 alibi.defined() ? alibi.data_ptr() : nullptr, (int)alibi_bs,
+                                 num_splits, 0, 1.f, 1.f,
+                                 leftpad.defined() ? leftpad.data_ptr() : nullptr,
+                                 q.dtype() == torch::kFloat16, cur_stream());
+        raise_if_failed("fwd_kvcache");
+    }
     if (head_size_og % 8 != 0) out = out.index({"...", torch::indexing::Slice(torch::indexing::None, head_size_og)});
     if (out_.has_value() && !out_.value().is_same(out)) out_.value().copy_(out), out = out_.value();
     return {out, softmax_lse};
+}
+
+std::vector<at::Tensor>
+mha_fwd_kvcache(at::Tensor& q, const at::Tensor& kcache, const at::Tensor& vcache,
+                c10::optional<const at::Tensor>& k_, c10::optional<const at::Tensor>& v_,
+                c10::optional<const at::Tensor>& seqlens_k_,
+                c10::optional<const at::Tensor>& rotary_cos_,
+                c10::optional<const at::Tensor>& rotary_sin_,
+                c10::optional<const at::Tensor>& cache_batch_idx_,
+                c10::optional<at::Tensor>& block_table_, c10::optional<at::Tensor>& alibi_slopes_,
+                c10::optional<at::Tensor>& out_, const float softmax_scale, bool is_causal,
+                int window_size_left, int window_size_right, const float softcap,
+                bool is_rotary_interleaved, int num_splits,
+                c10::optional<const at::Tensor>& cache_leftpad_) {
+    return mha_fwd_kvcache_impl(q, kcache, vcache, k_, v_, seqlens_k_, rotary_cos_, rotary_sin_,
+                                cache_batch_idx_, block_table_, alibi_slopes_, out_, softmax_scale,
+                                is_causal, window_size_left, window_size_right, softcap,
+                                is_rotary_interleaved, num_splits, cache_leftpad_, c10::nullopt);
+}
+
+// `fwd_kvcache` plus a trailing sink: fmha_page_kvcache_fwd_sink
+std::vector<at::Tensor>
+mha_fwd_kvcache_sink(at::Tensor& q, const at::Tensor& kcache, const at::Tensor& vcache,
+                     c10::optional<const at::Tensor>& k_, c10::optional<const at::Tensor>& v_,
+                     c10::optional<const at::Tensor>& seqlens_k_,
+                     c10::optional<const at::Tensor>& rotary_cos_,
+                     c10::optional<const at::Tensor>& rotary_sin_,
+                     c10::optional<const at::Tensor>& cache_batch_idx_,
+                     c10::optional<at::Tensor>& block_table_, c10::optional<at::Tensor>& alibi_slopes_,
+                     c10::optional<at::Tensor>& out_, const float softmax_scale, bool is_causal,
+                     int window_size_left, int window_size_right, const float softcap,
+                     bool is_rotary_interleaved, int num_splits,
+                     c10::optional<const at::Tensor>& cache_leftpad_, const at::Tensor& sink) {
+    return mha_fwd_kvcache_impl(q, kcache, vcache, k_, v_, seqlens_k_, rotary_cos_, rotary_sin_,
+                                cache_batch_idx_, block_table_, alibi_slopes_, out_, softmax_scale,
+                                is_causal, window_size_left, window_size_right, softcap,
+                                is_rotary_interleaved, num_splits, cache_leftpad_, sink);
+}
+
+// Gradient of the sink from a backward's saved softmax_lse and its softmax_d: dense
+// [batch, heads, seqlen_q] or (varlen) packed [heads, total_q]; returns dsink fp32 [heads].
+at::Tensor
+mha_sink_bwd(const at::Tensor& softmax_lse, const at::Tensor& softmax_d, const at::Tensor& sink,
+             const bool varlen) {
+    CHECK_DEVICE(softmax_lse); CHECK_DEVICE(softmax_d); CHECK_DEVICE(sink);
+    TORCH_CHECK(softmax_lse.dtype() == torch::kFloat32 && softmax_d.dtype() == torch::kFloat32 &&
+                sink.dtype() == torch::kFloat32, "softmax_lse, softmax_d and sink must be fp32");
+    TORCH_CHECK(softmax_lse.dim() == (varlen ? 2 : 3), "softmax_lse must be (batch, heads, seqlen_q), or (heads, total_q) with varlen");
+    TORCH_CHECK(softmax_d.sizes() == softmax_lse.sizes(), "softmax_d must have softmax_lse's shape");
+    CHECK_CONTIGUOUS(softmax_lse); CHECK_CONTIGUOUS(softmax_d); CHECK_CONTIGUOUS(sink);
+    const int batch = varlen ? 1 : softmax_lse.size(0);
+    const int heads = softmax_lse.size(varlen ? 0 : 1), rows = softmax_lse.size(varlen ? 1 : 2);
+    TORCH_CHECK(sink.dim() == 1 && sink.size(0) == heads, "sink must have shape (num_heads)");
+    const c10::DeviceGuard device_guard(softmax_lse.device());
+    auto dsink = torch::zeros({heads}, sink.options());
+    if (batch > 0 && rows > 0) {
+        fmha_bwd_sink(softmax_lse.data_ptr<float>(), softmax_d.data_ptr<float>(), sink.data_ptr<float>(),
+                      dsink.data_ptr<float>(), batch, heads, rows, (int64_t)heads * rows, rows, cur_stream());
+        raise_if_failed("sink_bwd");
+    }
+    return dsink;
 }
 
 // Gradient outputs (export.cpp:1037-1060): a caller-given tensor must match q/k/v in dtype,
@@ -672,11 +839,12 @@ mha_varlen_bwd(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k,
 // Paged decode over an fp8 (OCP e4m3fn) K/V cache with per-tensor dequant scales — an
 // extension the reference lacks.  kcache/vcache: float8_e4m3fn (or uint8 bytes)
 // [num_blocks, page, hk, d]; returns {out, softmax_lse}.
-std::vector<at::Tensor>
-mha_fwd_kvcache_fp8(at::Tensor& q, const at::Tensor& kcache, const at::Tensor& vcache,
+static std::vector<at::Tensor>
+mha_fwd_kvcache_fp8_impl(at::Tensor& q, const at::Tensor& kcache, const at::Tensor& vcache,
                     const at::Tensor& seqlens_k, const at::Tensor& block_table, const float k_scale,
                     const float v_scale, const float softmax_scale, bool is_causal,
-                    int window_size_left, int window_size_right, int num_splits) {
+                    int window_size_left, int window_size_right, int num_splits,
+                    const c10::optional<at::Tensor>& sink_) {
     auto dt = q.dtype();
     TORCH_CHECK(dt == torch::kFloat16 || dt == torch::kBFloat16, "q must be fp16 or bf16");
     TORCH_CHECK(kcache.element_size() == 1 && vcache.element_size() == 1, "fp8 K/V cache expected");
@@ -700,6 +868,16 @@ mha_fwd_kvcache_fp8(at::Tensor& q, const at::Tensor& kcache, const at::Tensor& v
     auto out = torch::empty_like(qc);
     auto lse = torch::empty({batch_size, num_heads, seqlen_q}, q.options().dtype(at::kFloat));
     auto bt = block_table.contiguous();
+    if (const float* sink = sink_for_c(sink_, q, num_heads)) {
+        fmha_page_kvcache_fwd_sink(qc.data_ptr(), kcache.data_ptr(), vcache.data_ptr(), out.data_ptr(),
+                                   lse.data_ptr(), bt.data_ptr(), (int)bt.stride(0), seqlens_k.data_ptr(),
+                                   seqlen_q, seqlen_k, batch_size, num_heads, num_heads_k, d, page,
+                                   softmax_scale, window_size_left, window_size_right, 0.f, nullptr, 0,
+                                   num_splits, 1, k_scale, v_scale, nullptr, dt == torch::kFloat16,
+                                   cur_stream(), sink);
+        raise_if_failed("fwd_kvcache_fp8_sink");
+        return {out, lse};
+    }
     fmha_page_kvcache_fwd_ex(qc.data_ptr(), kcache.data_ptr(), vcache.data_ptr(), out.data_ptr(),
                              lse.data_ptr(), bt.data_ptr(), (int)bt.stride(0), seqlens_k.data_ptr(),
                              seqlen_q, seqlen_k, batch_size, num_heads, num_heads_k, d, page,
@@ -708,6 +886,28 @@ mha_fwd_kvcache_fp8(at::Tensor& q, const at::Tensor& kcache, const at::Tensor& v
                              cur_stream());
     raise_if_failed("fwd_kvcache_fp8");
     return {out, lse};
+}
+
+std::vector<at::Tensor>
+mha_fwd_kvcache_fp8(at::Tensor& q, const at::Tensor& kcache, const at::Tensor& vcache,
+                    const at::Tensor& seqlens_k, const at::Tensor& block_table, const float k_scale,
+                    const float v_scale, const float softmax_scale, bool is_causal,
+                    int window_size_left, int window_size_right, int num_splits) {
+    return mha_fwd_kvcache_fp8_impl(q, kcache, vcache, seqlens_k, block_table, k_scale, v_scale,
+                                    softmax_scale, is_causal, window_size_left, window_size_right,
+                                    num_splits, c10::nullopt);
+}
+
+// `fwd_kvcache_fp8` plus a trailing sink
+std::vector<at::Tensor>
+mha_fwd_kvcache_fp8_sink(at::Tensor& q, const at::Tensor& kcache, const at::Tensor& vcache,
+                         const at::Tensor& seqlens_k, const at::Tensor& block_table, const float k_scale,
+                         const float v_scale, const float softmax_scale, bool is_causal,
+                         int window_size_left, int window_size_right, int num_splits,
+                         const at::Tensor& sink) {
+    return mha_fwd_kvcache_fp8_impl(q, kcache, vcache, seqlens_k, block_table, k_scale, v_scale,
+                                    softmax_scale, is_causal, window_size_left, window_size_right,
+                                    num_splits, sink);
 }
 
 // fp8 e4m3fn Q/K/V forward (extension): q [b, sq, h, 128], k/v [b, sk, hk, 128] as
@@ -1031,6 +1231,11 @@ PYBIND11_MODULE(paged_attn, m) {
           py::arg("softmax_scale"), py::arg("is_causal"), py::arg("window_size_left"),
           py::arg("window_size_right"), py::arg("softcap"), py::arg("is_rotary_interleaved"),
           py::arg("num_splits"), py::arg("cache_leftpad") = py::none());
+    m.def("fwd_sink", &mha_fwd_sink, "Forward pass with a per-head attention sink");
+    m.def("varlen_fwd_sink", &mha_varlen_fwd_sink, "Forward pass (variable length) with an attention sink");
+    m.def("fwd_kvcache_sink", &mha_fwd_kvcache_sink, "Forward pass with KV-cache and an attention sink");
+    m.def("fwd_kvcache_fp8_sink", &mha_fwd_kvcache_fp8_sink, "Paged decode over an fp8 K/V cache with an attention sink");
+    m.def("sink_bwd", &mha_sink_bwd, "Gradient of the attention sink from softmax_lse and softmax_d");
     m.def("bwd", &mha_bwd, "Backward pass");
     m.def("varlen_bwd", &mha_varlen_bwd, "Backward pass (variable length)");
     m.def("fwd_kvcache_fp8", &mha_fwd_kvcache_fp8, "Paged decode over an fp8 e4m3fn K/V cache");

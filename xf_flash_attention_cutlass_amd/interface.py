@@ -18,6 +18,54 @@ def _maybe_contiguous(x):
     return x.contiguous() if x is not None and x.stride(-1) != 1 else x
 
 
+def _sink_f32(sink, q):
+    """The sink as the ops take it: fp32 [h], contiguous, on q's device."""
+    if sink.dim() != 1 or sink.shape[0] != q.shape[-2]:
+        raise ValueError(f"sink must have shape (num_heads,) = ({q.shape[-2]},), got {tuple(sink.shape)}")
+    if not sink.is_floating_point():
+        raise TypeError("sink must be a floating-point tensor")
+    return sink.detach().to(device=q.device, dtype=torch.float32).contiguous()
+
+
+class _FlashAttnSinkFunc(torch.autograd.Function):
+    """_FlashAttnFunc with a per-head sink logit: `fwd_sink`, the unchanged `bwd` (given the sink
+    forward's out and lse it is already the sink softmax's backward) and `sink_bwd` for dsink."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, sink, softmax_scale, causal, window_size, softcap, deterministic):
+        q, k, v = (_maybe_contiguous(x) for x in (q, k, v))
+        s32 = _sink_f32(sink, q)
+        out, q_p, k_p, v_p, out_p, lse, _, rng = paged_attn.fwd_sink(
+            q, k, v, None, None, 0.0, softmax_scale, causal, window_size[0], window_size[1],
+            softcap, False, None, s32)
+        ctx.save_for_backward(q_p, k_p, v_p, out_p, lse, rng, s32)
+        ctx.args = (softmax_scale, causal, window_size, softcap, deterministic, q.shape[-1],
+                    sink.dtype)
+        return out, lse
+
+    @staticmethod
+    def backward(ctx, dout, *_):
+        q, k, v, out, lse, rng, s32 = ctx.saved_tensors
+        scale, causal, window, softcap, deterministic, d_og, sink_dtype = ctx.args
+        dq, dk, dv, softmax_d = paged_attn.bwd(_maybe_contiguous(dout), q, k, v, out, lse, None,
+                                               None, None, None, 0.0, scale, causal, window[0],
+                                               window[1], softcap, deterministic, None, rng)
+        dsink = None
+        if ctx.needs_input_grad[3]:
+            dsink = paged_attn.sink_bwd(lse, softmax_d, s32, False).to(sink_dtype)
+        dq, dk, dv = dq[..., :d_og], dk[..., :d_og], dv[..., :d_og]
+        return dq, dk, dv, dsink, None, None, None, None, None
+
+
+def _check_sink_args(q, dropout_p, alibi_slopes):
+    if q.dtype == torch.float8_e4m3fn:
+        raise NotImplementedError("fp8 q/k/v: an attention sink is not supported")
+    if alibi_slopes is not None:
+        raise NotImplementedError("an attention sink does not support ALiBi")
+    if dropout_p != 0.0:
+        raise NotImplementedError("an attention sink does not support dropout")
+
+
 class _FlashAttnFunc(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, dropout_p, softmax_scale, causal, window_size, softcap,
@@ -45,13 +93,24 @@ class _FlashAttnFunc(torch.autograd.Function):
 def flash_attn_func(q, k, v, dropout_p=0.0, causal=False, window_size=(-1, -1), softcap=0.0,
                     alibi_slopes=None, deterministic=False, return_attn_probs=False, *,
                     softmax_scale=None, q_descale=None, k_descale=None, v_descale=None,
-                    out_dtype=torch.bfloat16):
+                    out_dtype=torch.bfloat16, sink=None):
     """q [b, sq, h, d], k/v [b, sk, hk, d] -> out [b, sq, h, d] (test.py:41-72).
 
     Extension: float8_e4m3fn q/k/v (with per-tensor descales, value = stored x descale) run the
-    fp8-MFMA forward (forward only, d = 128, no ALiBi / softcap / dropout); out is `out_dtype`."""
+    fp8-MFMA forward (forward only, d = 128, no ALiBi / softcap / dropout); out is `out_dtype`.
+
+    sink: a per-head logit [h] (any float dtype; gpt-oss's learned sinks) that joins each row's
+    softmax denominator and carries no value, in the units of the scaled scores; its gradient is
+    returned in sink's dtype.  Not with ALiBi, dropout or fp8 q/k/v; with return_attn_probs the
+    third result is None."""
     if softmax_scale is None:
         softmax_scale = q.shape[-1] ** (-0.5)
+    if sink is not None:
+        _check_sink_args(q, dropout_p, alibi_slopes)
+        out, lse = _FlashAttnSinkFunc.apply(q, k, v, sink, softmax_scale, causal,
+                                            tuple(int(w) for w in window_size), softcap,
+                                            deterministic)
+        return out if not return_attn_probs else (out, lse, None)
     if q.dtype == torch.float8_e4m3fn:
         # the fp8 forward has no dropout / softcap / ALiBi: refuse instead of dropping them
         if dropout_p != 0.0 or softcap != 0.0 or alibi_slopes is not None:
@@ -154,11 +213,11 @@ def flash_attn_fp8_func(q, k, v, q_descale=None, k_descale=None, v_descale=None,
 
 def flash_attn_kvpacked_func(q, kv, dropout_p=0.0, softmax_scale=None, causal=False,
                              window_size=(-1, -1), softcap=0.0, alibi_slopes=None,
-                             deterministic=False, return_softmax=False):
+                             deterministic=False, return_softmax=False, *, sink=None):
     """kv [b, sk, 2, hk, d] (test.py:74-100)."""
     return flash_attn_func(q, kv[:, :, 0], kv[:, :, 1], dropout_p, causal, window_size, softcap,
                            alibi_slopes, deterministic, return_softmax,
-                           softmax_scale=softmax_scale)
+                           softmax_scale=softmax_scale, sink=sink)
 
 
 class _FlashAttnVarlenFunc(torch.autograd.Function):
@@ -188,6 +247,40 @@ class _FlashAttnVarlenFunc(torch.autograd.Function):
                                               window[1], softcap, deterministic, None, rng)
         dq, dk, dv = dq[..., :d_og], dk[..., :d_og], dv[..., :d_og]
         return (dq, dk, dv) + (None,) * 13
+
+
+class _FlashAttnVarlenSinkFunc(torch.autograd.Function):
+    """_FlashAttnVarlenFunc with a per-head sink logit (as _FlashAttnSinkFunc)."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, sink, cu_q, cu_k, max_q, max_k, softmax_scale, causal, window_size,
+                softcap, deterministic, block_table):
+        q, k, v = (_maybe_contiguous(x) for x in (q, k, v))
+        s32 = _sink_f32(sink, q)
+        out, q_p, k_p, v_p, out_p, lse, _, rng = paged_attn.varlen_fwd_sink(
+            q, k, v, None, cu_q, cu_k, None, block_table, None, max_q, max_k, 0.0, softmax_scale,
+            False, causal, window_size[0], window_size[1], softcap, False, None, s32)
+        ctx.save_for_backward(q_p, k_p, v_p, out_p, lse, cu_q, cu_k, rng, s32)
+        ctx.args = (max_q, max_k, softmax_scale, causal, window_size, softcap, deterministic,
+                    q.shape[-1], block_table is not None, sink.dtype)
+        return out, lse
+
+    @staticmethod
+    def backward(ctx, dout, *_):
+        q, k, v, out, lse, cu_q, cu_k, rng, s32 = ctx.saved_tensors
+        (max_q, max_k, scale, causal, window, softcap, deterministic, d_og, paged,
+         sink_dtype) = ctx.args
+        if paged:
+            raise RuntimeError("backward through a paged K/V cache is not supported")
+        dq, dk, dv, softmax_d = paged_attn.varlen_bwd(
+            _maybe_contiguous(dout), q, k, v, out, lse, None, None, None, cu_q, cu_k, None, max_q,
+            max_k, 0.0, scale, False, causal, window[0], window[1], softcap, deterministic, None,
+            rng)
+        dsink = None
+        if ctx.needs_input_grad[3]:
+            dsink = paged_attn.sink_bwd(lse, softmax_d, s32, True).to(sink_dtype)
+        dq, dk, dv = dq[..., :d_og], dk[..., :d_og], dv[..., :d_og]
+        return (dq, dk, dv, dsink) + (None,) * 10
 
 
 def flash_attn_varlen_fp8_func(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k,
@@ -236,13 +329,22 @@ def flash_attn_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, ma
                            window_size=(-1, -1), softcap=0.0, alibi_slopes=None,
                            deterministic=False, return_attn_probs=False, block_table=None, *,
                            q_descale=None, k_descale=None, v_descale=None,
-                           out_dtype=torch.bfloat16):
+                           out_dtype=torch.bfloat16, sink=None):
     """Packed q [total_q, h, d], k/v [total_k, hk, d], cu_seqlens int32 (test.py:102-149).
 
     Extension: float8_e4m3fn q/k/v (with per-tensor descales) run the fp8-MFMA varlen forward
-    (forward only, d = 128, no ALiBi / softcap / dropout / block_table); out is `out_dtype`."""
+    (forward only, d = 128, no ALiBi / softcap / dropout / block_table); out is `out_dtype`.
+
+    sink: as `flash_attn_func`."""
     if softmax_scale is None:
         softmax_scale = q.shape[-1] ** (-0.5)
+    if sink is not None:
+        _check_sink_args(q, dropout_p, alibi_slopes)
+        out, lse = _FlashAttnVarlenSinkFunc.apply(
+            q, k, v, sink, cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), int(max_seqlen_k),
+            softmax_scale, causal, tuple(int(w) for w in window_size), softcap, deterministic,
+            block_table)
+        return out if not return_attn_probs else (out, lse, None)
     if q.dtype == torch.float8_e4m3fn:
         # refuse what the fp8 forward lacks instead of dropping it
         if dropout_p != 0.0 or softcap != 0.0 or alibi_slopes is not None or block_table is not None:
@@ -266,12 +368,12 @@ def flash_attn_varlen_kvpacked_func(q, kv, cu_seqlens_q, cu_seqlens_k, max_seqle
                                     max_seqlen_k, dropout_p=0.0, softmax_scale=None,
                                     causal=False, window_size=(-1, -1), softcap=0.0,
                                     alibi_slopes=None, deterministic=False,
-                                    return_attn_probs=False):
+                                    return_attn_probs=False, *, sink=None):
     """kv [total_k, 2, hk, d] (test.py:151-187)."""
     return flash_attn_varlen_func(q, kv[:, 0], kv[:, 1], cu_seqlens_q, cu_seqlens_k,
                                   max_seqlen_q, max_seqlen_k, dropout_p, softmax_scale, causal,
                                   window_size, softcap, alibi_slopes, deterministic,
-                                  return_attn_probs)
+                                  return_attn_probs, sink=sink)
 
 
 def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None,
@@ -282,7 +384,7 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
                             block_table: Optional[torch.Tensor] = None, softmax_scale=None,
                             causal=False, window_size=(-1, -1), softcap=0.0,
                             rotary_interleaved=True, alibi_slopes=None, num_splits=0,
-                            return_softmax_lse=False, k_scale=1.0, v_scale=1.0):
+                            return_softmax_lse=False, k_scale=1.0, v_scale=1.0, *, sink=None):
     """Decode / chunked prefill against a (paged) KV cache (test.py:189-245).  With k/v the new
     rows are first written into the cache in place at cache_seqlens (rotary_cos/sin: rotary
     embedding on k and q, interleaved = GPT-J pairs), then attended over.
@@ -292,7 +394,10 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
     fp16, q's dtype) the new rows are quantised into it first: K after its rotary in fp32, times
     1 / k_scale, clamped to +-448 and rounded once to e4m3; V times 1 / v_scale likewise
     (k_scale, v_scale positive floats); rotary_cos/sin and rotary_interleaved as for a bf16 cache.
-    ALiBi and softcap are not supported with an fp8 cache."""
+    ALiBi and softcap are not supported with an fp8 cache.
+
+    sink: a per-head logit [h] (any float dtype) in each row's softmax denominator, as
+    `flash_attn_func` (forward only here); bf16 / fp16 and fp8 caches alike, not with ALiBi."""
     assert k_cache.stride(-1) == 1, "k_cache must have contiguous last dimension"
     assert v_cache.stride(-1) == 1, "v_cache must have contiguous last dimension"
     if cache_leftpad is not None and (block_table is not None or k_cache.dtype == torch.float8_e4m3fn):
@@ -301,6 +406,9 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
     q, k, v = (_maybe_contiguous(x) for x in (q, k, v))
     if softmax_scale is None:
         softmax_scale = q.shape[-1] ** (-0.5)
+    if sink is not None:
+        _check_sink_args(q, 0.0, alibi_slopes)
+        sink = _sink_f32(sink, q)
     if k_cache.dtype == torch.float8_e4m3fn:
         if block_table is None or cache_seqlens is None or alibi_slopes is not None or softcap > 0:
             raise NotImplementedError("fp8 K/V cache: paged decode with block_table and "
@@ -320,11 +428,13 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
                 q, k_cache.view(torch.uint8), v_cache.view(torch.uint8), k, v,
                 _maybe_contiguous(cache_seqlens), block_table, rotary_cos, rotary_sin,
                 float(k_scale), float(v_scale), rotary_interleaved, per_token)
-        out, lse = paged_attn.fwd_kvcache_fp8(q, k_cache.view(torch.uint8),
-                                              v_cache.view(torch.uint8), cache_seqlens,
-                                              block_table, float(k_scale), float(v_scale),
-                                              softmax_scale, causal, int(window_size[0]),
-                                              int(window_size[1]), num_splits)
+        args = (q, k_cache.view(torch.uint8), v_cache.view(torch.uint8), cache_seqlens,
+                block_table, float(k_scale), float(v_scale), softmax_scale, causal,
+                int(window_size[0]), int(window_size[1]), num_splits)
+        if sink is not None:
+            out, lse = paged_attn.fwd_kvcache_fp8_sink(*args, sink)
+        else:
+            out, lse = paged_attn.fwd_kvcache_fp8(*args)
         return (out, lse) if return_softmax_lse else out
     if cache_seqlens is not None and isinstance(cache_seqlens, int):
         cache_seqlens = torch.full((q.shape[0],), cache_seqlens, dtype=torch.int32,
@@ -332,9 +442,12 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
         cache_seqlens = _maybe_contiguous(cache_seqlens)
     cache_batch_idx = _maybe_contiguous(cache_batch_idx)
     block_table = _maybe_contiguous(block_table)
-    out, lse = paged_attn.fwd_kvcache(q, k_cache, v_cache, k, v, cache_seqlens, rotary_cos,
-                                      rotary_sin, cache_batch_idx, block_table, alibi_slopes,
-                                      None, softmax_scale, causal, int(window_size[0]),
-                                      int(window_size[1]), softcap, rotary_interleaved,
-                                      num_splits, _maybe_contiguous(cache_leftpad))
+    args = (q, k_cache, v_cache, k, v, cache_seqlens, rotary_cos, rotary_sin, cache_batch_idx,
+            block_table, alibi_slopes, None, softmax_scale, causal, int(window_size[0]),
+            int(window_size[1]), softcap, rotary_interleaved, num_splits,
+            _maybe_contiguous(cache_leftpad))
+    if sink is not None:
+        out, lse = paged_attn.fwd_kvcache_sink(*args, sink)
+    else:
+        out, lse = paged_attn.fwd_kvcache(*args)
     return (out, lse) if return_softmax_lse else out
