@@ -13,12 +13,17 @@
 // transposed-view swap (:526-532); a [H]-shaped ALiBi vector is expanded rather than read
 // out of bounds; dropout runs (Philox keep bits, rng_state = {seed, offset} as export.cpp
 // returns it) instead of being silently ignored.
+//
+// Layout: the helpers (one per family of checks), then one function per op.  An op and its
+// _sink twin are one function that takes the optional sink first; without_sink / with_sink
+// bind the two names to it.
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 #include <c10/core/DeviceGuard.h>
 #include <c10/hip/HIPStream.h>
 #include <ATen/hip/HIPGeneratorImpl.h>
 
+#include <array>
 #include <limits>
 
 #include "paged_attn.h"
@@ -30,6 +35,9 @@
 
 namespace {
 
+using OptTensor = c10::optional<at::Tensor>;
+using OptConstTensor = c10::optional<const at::Tensor>;
+
 void raise_if_failed(const char* op) {
     if (fmha_last_status() != 0) TORCH_CHECK(false, op, ": ", fmha_last_error());
 }
@@ -38,9 +46,17 @@ hipStream_t cur_stream() { return c10::hip::getCurrentHIPStream().stream(); }
 
 int round8(int x) { return (x + 7) / 8 * 8; }
 
+void* ptr_or_null(const at::Tensor& t) { return t.defined() ? t.data_ptr() : nullptr; }
+
 at::Tensor pad_last(const at::Tensor& t, int d_og) {
     if (d_og % 8 == 0) return t;
     return torch::nn::functional::pad(t, torch::nn::functional::PadFuncOptions({0, 8 - d_og % 8}));
+}
+
+// ... and back: the first d_og columns of a tensor padded to a multiple of 8
+at::Tensor unpad_last(const at::Tensor& t, int d_og) {
+    if (d_og % 8 == 0) return t;
+    return t.index({"...", torch::indexing::Slice(torch::indexing::None, d_og)});
 }
 
 // The kernels move 16-byte chunks (b128 buffer loads, LDS-DMA, 16-byte row stores): every base
@@ -59,6 +75,18 @@ at::Tensor dense(const at::Tensor& t) {
     return c;
 }
 
+// ---- rank and shape reading: the rank first (sizes()[i] past it is an unchecked read)
+constexpr const char* kDense = "(batch, seqlen, heads, head_size)";
+constexpr const char* kPacked = "(total, heads, head_size)";
+
+template <int N>
+std::array<int, N> dims(const at::Tensor& t, const char* name, const char* layout) {
+    TORCH_CHECK(t.dim() == N, name, " must be ", layout);
+    std::array<int, N> s;
+    for (int i = 0; i < N; ++i) s[i] = t.size(i);
+    return s;
+}
+
 void check_qkv_dtype(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v) {
     auto dt = q.dtype();
     TORCH_CHECK(dt == torch::kFloat16 || dt == torch::kBFloat16,
@@ -71,9 +99,144 @@ void check_qkv_dtype(const at::Tensor& q, const at::Tensor& k, const at::Tensor&
     TORCH_CHECK(v.stride(-1) == 1, "Input tensor must have contiguous last dimension");
 }
 
+// ---- batch, heads and head size (`pass`: "forward" / "backward") ...
+void check_heads(int batch_size, int num_heads, int num_heads_k, int head_size, const char* pass) {
+    TORCH_CHECK(batch_size > 0, "batch size must be positive");
+    TORCH_CHECK(head_size <= 256, "FlashAttention ", pass, " only supports head dimension at most 256");
+    TORCH_CHECK(num_heads % num_heads_k == 0, "Number of heads in key/value must divide number of heads in query");
+}
+
+// ... and dropout / softcap / return_softmax
+void check_dropout(float p_dropout, float softcap, bool return_softmax) {
+    TORCH_CHECK(p_dropout >= 0.f && p_dropout < 1.f, "p_dropout must be in [0, 1)");
+    if (softcap > 0.f) { TORCH_CHECK(p_dropout == 0.f, "Softcapping does not support dropout for now"); }
+    TORCH_CHECK(!return_softmax || p_dropout > 0.f, "return_softmax is only supported when p_dropout > 0.0");
+}
+
+// ---- window and causal: causal closes the right window, except for a single query row (which
+// sees every key either way; `single_row` is the op's own rule for it); a window that reaches
+// past seqlen_k is open.  `fwd` clips before it applies causal (the reference's order,
+// export.cpp:497-503), every other op after: with seqlen_k == 0 the first leaves causal's
+// right = 0, the second opens it.
+void normalize_window(bool is_causal, bool single_row, int seqlen_k, bool clip_first, int& left, int& right) {
+    auto clip = [&] {
+        if (left >= seqlen_k) left = -1;
+        if (right >= seqlen_k) right = -1;
+    };
+    if (clip_first) clip();
+    if (is_causal && !single_row) right = 0;
+    if (!clip_first) clip();
+}
+
+// ---- cu_seqlens: int32 [batch + 1] on the device, contiguous; returns batch
+int check_cu_seqlens(const at::Tensor& cu, const char* name) {
+    TORCH_CHECK(cu.dtype() == torch::kInt32, name, " must have dtype int32");
+    TORCH_CHECK(cu.is_cuda(), name, " must be on CUDA");
+    TORCH_CHECK(cu.is_contiguous(), name, " must be contiguous");
+    TORCH_CHECK(cu.dim() == 1 && cu.numel() >= 2, name, " must have shape (batch_size + 1)");
+    return cu.numel() - 1;
+}
+int check_cu_seqlens(const at::Tensor& cu_seqlens_q, const at::Tensor& cu_seqlens_k) {
+    const int batch_size = check_cu_seqlens(cu_seqlens_q, "cu_seqlens_q");
+    TORCH_CHECK(check_cu_seqlens(cu_seqlens_k, "cu_seqlens_k") == batch_size,
+                "cu_seqlens_k must have shape (batch_size + 1)");
+    return batch_size;
+}
+
+// ---- an int32 [batch] tensor on the device, contiguous: seqused_k, seqlens_k, cache_leftpad
+// (leftpad_k), cache_batch_idx; batch_int32 takes an optional one (undefined when absent)
+void check_batch_int32(const at::Tensor& t, int batch_size, const char* name) {
+    TORCH_CHECK(t.dtype() == torch::kInt32, name, " must have dtype int32");
+    TORCH_CHECK(t.is_cuda(), name, " must be on CUDA");
+    TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+    TORCH_CHECK(t.dim() == 1 && t.size(0) == batch_size, name, " must have shape (batch_size)");
+}
+template <typename T>
+at::Tensor batch_int32(const c10::optional<T>& t_, int batch_size, const char* name) {
+    if (!t_.has_value()) return at::Tensor();
+    check_batch_int32(t_.value(), batch_size, name);
+    return t_.value();
+}
+
+// ---- block_table: int32 [batch, max_num_blocks_per_seq] on the device, rows contiguous
+void check_block_table(const at::Tensor& block_table, int batch_size) {
+    CHECK_DEVICE(block_table);
+    TORCH_CHECK(block_table.dtype() == torch::kInt32, "block_table must have dtype torch.int32");
+    TORCH_CHECK(block_table.stride(-1) == 1, "block_table must have contiguous last dimension");
+    CHECK_SHAPE(block_table, batch_size, block_table.size(1));
+}
+
+// ---- rotary cos / sin [seqlen_ro >= seqlen_k, rotary_dim / 2], q's dtype, contiguous (absent: dim 0)
+struct Rotary { at::Tensor cos, sin; int dim = 0; };
+template <typename T>
+Rotary check_rotary(const c10::optional<T>& cos_, const c10::optional<T>& sin_, const at::Tensor& q,
+                    int head_size, int64_t seqlen_k) {
+    Rotary r;
+    if (!cos_.has_value()) return r;
+    TORCH_CHECK(sin_.has_value(), "If rotary cos is provided, rotary sin must also be provided");
+    const at::Tensor &cos = cos_.value(), &sin = sin_.value();
+    CHECK_DEVICE(cos); CHECK_DEVICE(sin); CHECK_CONTIGUOUS(cos); CHECK_CONTIGUOUS(sin);
+    r.dim = cos.size(1) * 2;
+    TORCH_CHECK(r.dim <= head_size, "rotary_dim must be <= headdim");
+    TORCH_CHECK(r.dim % 16 == 0, "Only rotary dimensions divisible by 16 are currently supported");
+    TORCH_CHECK(cos.size(0) >= seqlen_k, "cos/sin seqlen must be at least the seqlen of KV cache");
+    CHECK_SHAPE(sin, cos.size(0), r.dim / 2);
+    TORCH_CHECK(cos.scalar_type() == q.scalar_type() && sin.scalar_type() == q.scalar_type(),
+                "rotary_cos/sin must have the same dtype as query");
+    r.cos = cos; r.sin = sin;
+    return r;
+}
+
+// ---- `out`: the caller's, checked against `shape` (the unpadded one) and `opts`' dtype, when the
+// kernel can write it directly: head size a multiple of 8, 16-byte aligned, and contiguous unless
+// `strided_ok`.  Otherwise `refuse_indirect` refuses it, or a contiguous temporary of the padded
+// shape is computed into and finish_out copies back; the same temporary when no `out` is given.
+at::Tensor take_out(const OptTensor& out_, const at::TensorOptions& opts, std::vector<int64_t> shape,
+                    bool strided_ok, bool refuse_indirect) {
+    if (out_.has_value()) {
+        const at::Tensor& out = out_.value();
+        TORCH_CHECK(out.dtype() == opts.dtype(), "Output must have the same dtype as inputs");
+        CHECK_DEVICE(out);
+        TORCH_CHECK(out.stride(-1) == 1, "Output tensor must have contiguous last dimension");
+        TORCH_CHECK(out.sizes() == at::IntArrayRef(shape), "out must have shape ", at::IntArrayRef(shape));
+        const bool direct = shape.back() % 8 == 0 && aligned16(out) && (strided_ok || out.is_contiguous());
+        if (direct) return out;
+        TORCH_CHECK(!refuse_indirect, "out must be contiguous (and 16-byte aligned)");
+    }
+    shape.back() = round8(shape.back());
+    return torch::empty(shape, opts);
+}
+
+// the op's first result: the padding columns off, and in the caller's `out` when one was given
+at::Tensor finish_out(const OptTensor& out_, const at::Tensor& computed, int head_size_og) {
+    at::Tensor out = unpad_last(computed, head_size_og);
+    if (!out_.has_value() || out_.value().is_same(out)) return out;
+    out_.value().copy_(out);
+    return out_.value();
+}
+
+// ---- gradients (export.cpp:1037-1060): a caller-given tensor must match q/k/v in dtype, device
+// and shape; a non-contiguous one is computed into a contiguous temporary and copied back.
+// finish_grad returns the caller's view of the result: in its tensor, the padding columns off.
+at::Tensor take_grad(const OptTensor& t, const at::Tensor& like) {
+    if (t.has_value()) {
+        const at::Tensor& x = t.value();
+        TORCH_CHECK(x.dtype() == like.dtype(), "gradient must have the same dtype as its input");
+        CHECK_DEVICE(x);
+        TORCH_CHECK(x.sizes() == like.sizes(), "gradient has the wrong shape");
+        if (x.is_contiguous() && aligned16(x)) return x;
+    }
+    return torch::empty_like(like, like.options().memory_format(at::MemoryFormat::Contiguous));
+}
+at::Tensor finish_grad(const OptTensor& t, const at::Tensor& g, int head_size_og) {
+    if (t.has_value() && !t.value().is_same(g)) t.value().copy_(g);
+    return unpad_last(t.has_value() ? t.value() : g, head_size_og);
+}
+
 // ALiBi slopes as the C ABI wants them: fp32, [b, h] when batch > 1 (paged_attn.cpp:375).
-at::Tensor alibi_for_c(c10::optional<at::Tensor>& a, int b, int h, int64_t* bstride) {
-    if (!a.has_value()) { *bstride = 0; return at::Tensor(); }
+struct Alibi { at::Tensor slopes; int batch_stride = 0; };
+Alibi alibi_for_c(const OptTensor& a, int b, int h) {
+    if (!a.has_value()) return {};
     auto s = a.value();
     TORCH_CHECK(s.dtype() == torch::kFloat32, "ALiBi slopes must have dtype fp32");
     CHECK_DEVICE(s);
@@ -81,9 +244,7 @@ at::Tensor alibi_for_c(c10::optional<at::Tensor>& a, int b, int h, int64_t* bstr
     TORCH_CHECK(s.sizes() == torch::IntArrayRef({h}) || s.sizes() == torch::IntArrayRef({b, h}),
                 "ALiBi slopes must have shape (num_heads) or (batch_size, num_heads)");
     if (s.dim() == 1) s = s.unsqueeze(0).expand({b, h});
-    s = s.contiguous();
-    *bstride = b > 1 ? h : 0;
-    return s;
+    return {s.contiguous(), b > 1 ? h : 0};
 }
 
 // Dropout: the key from torch's HIP generator (ATen/hip/HIPGeneratorImpl.h, whose generator
@@ -118,7 +279,7 @@ at::Tensor dropout_rng(float p_dropout, c10::optional<at::Generator>& gen_, int6
 
 // The backward's key: a device rng_state (the forward's) is read on the device (capturable);
 // a host one (a caller's own {seed, offset}) is passed by value.
-void dropout_rng_restore(float p_dropout, c10::optional<at::Tensor>& rng_state) {
+void dropout_rng_restore(float p_dropout, const OptTensor& rng_state) {
     if (p_dropout <= 0.f) return;
     TORCH_CHECK(rng_state.has_value(), "backward with dropout needs the forward's rng_state");
     const at::Tensor& r0 = rng_state.value();
@@ -142,7 +303,7 @@ struct RngDisarm {
 };
 
 // The sink of the _sink ops: fp32 [num_heads], contiguous, on q's device (null when absent).
-const float* sink_for_c(const c10::optional<at::Tensor>& sink_, const at::Tensor& q, int num_heads) {
+const float* sink_for_c(const OptTensor& sink_, const at::Tensor& q, int num_heads) {
     if (!sink_.has_value()) return nullptr;
     const at::Tensor& s = sink_.value();
     TORCH_CHECK(s.dtype() == torch::kFloat32, "sink must have dtype fp32");
@@ -158,205 +319,112 @@ at::Tensor sdmask_buffer(bool want, const at::TensorOptions& opts, int b, int h,
     return torch::empty({b, h, r128(sq), r128(sk)}, opts);
 }
 
+// An op and its _sink twin are one function taking the optional sink first: the base name binds
+// it without a sink (the reference's argument list; one argument more is a TypeError), the
+// _sink name with a trailing, required sink tensor.
+template <typename R, typename... A>
+auto without_sink(R (*f)(const OptTensor&, A...)) {
+    return [f](A... a) { return f(c10::nullopt, std::forward<A>(a)...); };
+}
+template <typename R, typename... A>
+auto with_sink(R (*f)(const OptTensor&, A...)) {
+    return [f](A... a, const at::Tensor& sink) { return f(sink, std::forward<A>(a)...); };
+}
+
 }  // namespace
 
-static std::vector<at::Tensor>
-mha_fwd_impl(at::Tensor& q, const at::Tensor& k, const at::Tensor& v, c10::optional<at::Tensor>& out_,
-        c10::optional<at::Tensor>& alibi_slopes_, const float p_dropout, const float softmax_scale,
-        bool is_causal, int window_size_left, int window_size_right, const float softcap,
-        const bool return_softmax, c10::optional<at::Generator> gen_,
-        const c10::optional<at::Tensor>& sink_) {
+// `fwd`, and `fwd_sink` with a trailing sink (fp32 [num_heads])
+std::vector<at::Tensor>
+mha_fwd(const OptTensor& sink_, at::Tensor& q, const at::Tensor& k, const at::Tensor& v, OptTensor& out_,
+        OptTensor& alibi_slopes_, const float p_dropout, const float softmax_scale, bool is_causal,
+        int window_size_left, int window_size_right, const float softcap, const bool return_softmax,
+        c10::optional<at::Generator> gen_) {
     check_qkv_dtype(q, k, v);
-    const auto sizes = q.sizes();
-    TORCH_CHECK(q.dim() == 4, "q must be (batch, seqlen, heads, head_size)");
-    const int batch_size = sizes[0];
-    const int seqlen_q = sizes[1];
-    const int num_heads = sizes[2];
-    const int head_size_og = sizes[3];
+    const auto [batch_size, seqlen_q, num_heads, head_size_og] = dims<4>(q, "q", kDense);
     const int seqlen_k = k.size(1);
     const int num_heads_k = k.size(2);
-    TORCH_CHECK(batch_size > 0, "batch size must be postive");
-    TORCH_CHECK(head_size_og <= 256, "FlashAttention forward only supports head dimension at most 256");
-    TORCH_CHECK(num_heads % num_heads_k == 0, "Number of heads in key/value must divide number of heads in query");
-    TORCH_CHECK(p_dropout >= 0.f && p_dropout < 1.f, "p_dropout must be in [0, 1)");
-    if (softcap > 0.f) { TORCH_CHECK(p_dropout == 0.f, "Softcapping does not support dropout for now"); }
-    TORCH_CHECK(!return_softmax || p_dropout > 0.f, "return_softmax is only supported when p_dropout > 0.0");
-    if (window_size_left >= seqlen_k) window_size_left = -1;
-    if (window_size_right >= seqlen_k) window_size_right = -1;
-    if (seqlen_q == 1 && !alibi_slopes_.has_value()) is_causal = false;
-    if (is_causal) window_size_right = 0;
-    CHECK_SHAPE(q, batch_size, seqlen_q, num_heads, head_size_og);
+    check_heads(batch_size, num_heads, num_heads_k, head_size_og, "forward");
+    check_dropout(p_dropout, softcap, return_softmax);
+    normalize_window(is_causal, seqlen_q == 1 && !alibi_slopes_.has_value(), seqlen_k, /*clip_first=*/true,
+                     window_size_left, window_size_right);
     CHECK_SHAPE(k, batch_size, seqlen_k, num_heads_k, head_size_og);
     CHECK_SHAPE(v, batch_size, seqlen_k, num_heads_k, head_size_og);
 
     // d % 8 == 0 and 16-byte aligned: strided views (head / batch slices, kvpacked kv[:, :, 0])
-    // run in place through fmha_fwd_strided; otherwise the reference's padding to a multiple of
-    // 8 (export.cpp:539-547) into aligned contiguous copies
+    // run in place; otherwise the reference's padding to a multiple of 8 (export.cpp:539-547)
+    // into aligned contiguous copies.  Either way each tensor goes by its own strides.
     const bool strided = head_size_og % 8 == 0 && aligned16(q) && aligned16(k) && aligned16(v);
     at::Tensor q_padded = strided ? q : dense(pad_last(q, head_size_og));
     at::Tensor k_padded = strided ? k : dense(pad_last(k, head_size_og));
     at::Tensor v_padded = strided ? v : dense(pad_last(v, head_size_og));
-    at::Tensor out;
-    if (out_.has_value()) {
-        out = out_.value();
-        TORCH_CHECK(out.dtype() == q.dtype(), "Output must have the same dtype as inputs");
-        CHECK_DEVICE(out);
-        TORCH_CHECK(out.stride(-1) == 1, "Output tensor must have contiguous last dimension");
-        CHECK_SHAPE(out, batch_size, seqlen_q, num_heads, head_size_og);
-        if (head_size_og % 8 != 0 || !aligned16(out) || (!strided && !out.is_contiguous()))
-            out = torch::empty_like(q_padded, at::MemoryFormat::Contiguous);
-    } else {
-        out = torch::empty_like(q_padded, at::MemoryFormat::Contiguous);
-    }
-    const int head_size = round8(head_size_og);
+    // (an aligned non-contiguous `out` is written in place when the inputs run in place)
+    at::Tensor out_padded = take_out(out_, q.options(), {batch_size, seqlen_q, num_heads, head_size_og},
+                                     /*strided_ok=*/strided, /*refuse_indirect=*/false);
     const c10::DeviceGuard device_guard(q.device());
     auto opts = q.options();
     auto softmax_lse = torch::empty({batch_size, num_heads, seqlen_q}, opts.dtype(at::kFloat));
     at::Tensor p = sdmask_buffer(return_softmax, opts, batch_size, num_heads, seqlen_q, seqlen_k);
     auto rng_state = dropout_rng(p_dropout, gen_, (int64_t)batch_size * num_heads * 32, q.device());
     RngDisarm rng_disarm;
-    int64_t alibi_bs = 0;
-    at::Tensor alibi = alibi_for_c(alibi_slopes_, batch_size, num_heads, &alibi_bs);
-
+    const Alibi alibi = alibi_for_c(alibi_slopes_, batch_size, num_heads);
     const float* sink = sink_for_c(sink_, q, num_heads);
-    if (seqlen_k > 0 && sink) {
-        // (the padded copies by their own strides where the views cannot run in place)
-        const at::Tensor &qs = strided ? q : q_padded, &ks = strided ? k : k_padded, &vs = strided ? v : v_padded;
-        const int64_t st[12] = {qs.stride(0), qs.stride(1), qs.stride(2), ks.stride(0), ks.stride(1),
-                                ks.stride(2), vs.stride(0), vs.stride(1), vs.stride(2), out.stride(0),
-                                out.stride(1), out.stride(2)};
-        fmha_fwd_sink(qs.data_ptr(), ks.data_ptr(), vs.data_ptr(), out.data_ptr(),
-                      alibi.defined() ? alibi.data_ptr() : nullptr, softmax_lse.data_ptr(),
-                      seqlen_q, seqlen_k, batch_size, num_heads, num_heads_k, head_size, st,
-                      softmax_scale, window_size_left, window_size_right, softcap,
-                      q.dtype() == torch::kFloat16, 0, cur_stream(), p_dropout,
-                      p.defined() ? p.data_ptr() : nullptr, sink);
-        raise_if_failed("fwd_sink");
-    } else if (seqlen_k > 0 && strided) {
-        const int64_t st[12] = {q.stride(0), q.stride(1), q.stride(2), k.stride(0), k.stride(1),
-                                k.stride(2), v.stride(0), v.stride(1), v.stride(2), out.stride(0),
-                                out.stride(1), out.stride(2)};
-        fmha_fwd_strided(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(),
-                         alibi.defined() ? alibi.data_ptr() : nullptr, softmax_lse.data_ptr(),
-                         seqlen_q, seqlen_k, batch_size, num_heads, num_heads_k, head_size, st,
-                         softmax_scale, window_size_left, window_size_right, softcap,
-                         q.dtype() == torch::kFloat16, 0, cur_stream(), p_dropout,
-                         p.defined() ? p.data_ptr() : nullptr);
-        raise_if_failed("fwd");
-    } else if (seqlen_k > 0) {
-        fmha_fwd(q_padded.data_ptr(), k_padded.data_ptr(), v_padded.data_ptr(), out.data_ptr(),
-                 alibi.defined() ? alibi.data_ptr() : nullptr, seqlen_q, seqlen_k, batch_size,
-                 num_heads, num_heads_k, head_size, p_dropout, cur_stream(), nullptr, softmax_scale,
-                 p.defined() ? p.data_ptr() : nullptr, softmax_lse.data_ptr(), window_size_left,
-                 window_size_right, softcap, return_softmax, q.dtype() == torch::kFloat16, 0);
+    if (seqlen_k > 0) {
+        const at::Tensor* t[4] = {&q_padded, &k_padded, &v_padded, &out_padded};
+        int64_t st[12];
+        for (int i = 0; i < 12; ++i) st[i] = t[i / 3]->stride(i % 3);
+        fmha_fwd_sink(q_padded.data_ptr(), k_padded.data_ptr(), v_padded.data_ptr(), out_padded.data_ptr(),
+                      ptr_or_null(alibi.slopes), softmax_lse.data_ptr(), seqlen_q, seqlen_k, batch_size,
+                      num_heads, num_heads_k, round8(head_size_og), st, softmax_scale, window_size_left,
+                      window_size_right, softcap, q.dtype() == torch::kFloat16, 0, cur_stream(), p_dropout,
+                      ptr_or_null(p), sink);
         raise_if_failed("fwd");
     } else {
-        out.zero_();
+        out_padded.zero_();
         softmax_lse.fill_(std::numeric_limits<float>::infinity());
     }
-    at::Tensor out_padded = out;
-    if (head_size_og % 8 != 0) out = out.index({"...", torch::indexing::Slice(torch::indexing::None, head_size_og)});
-    if (out_.has_value() && !out_.value().is_same(out)) out_.value().copy_(out), out = out_.value();
-    return {out, q_padded, k_padded, v_padded, out_padded, softmax_lse, p, rng_state};
+    return {finish_out(out_, out_padded, head_size_og), q_padded, k_padded, v_padded, out_padded, softmax_lse,
+            p, rng_state};
 }
 
+// `varlen_fwd`, and `varlen_fwd_sink` with a trailing sink
 std::vector<at::Tensor>
-mha_fwd(at::Tensor& q, const at::Tensor& k, const at::Tensor& v, c10::optional<at::Tensor>& out_,
-        c10::optional<at::Tensor>& alibi_slopes_, const float p_dropout, const float softmax_scale,
-        bool is_causal, int window_size_left, int window_size_right, const float softcap,
-        const bool return_softmax, c10::optional<at::Generator> gen_) {
-    return mha_fwd_impl(q, k, v, out_, alibi_slopes_, p_dropout, softmax_scale, is_causal,
-                        window_size_left, window_size_right, softcap, return_softmax, gen_, c10::nullopt);
-}
-
-// `fwd` plus a trailing sink (fp32 [num_heads]): fmha_fwd_sink
-std::vector<at::Tensor>
-mha_fwd_sink(at::Tensor& q, const at::Tensor& k, const at::Tensor& v, c10::optional<at::Tensor>& out_,
-             c10::optional<at::Tensor>& alibi_slopes_, const float p_dropout, const float softmax_scale,
-             bool is_causal, int window_size_left, int window_size_right, const float softcap,
-             const bool return_softmax, c10::optional<at::Generator> gen_, const at::Tensor& sink) {
-    return mha_fwd_impl(q, k, v, out_, alibi_slopes_, p_dropout, softmax_scale, is_causal,
-                        window_size_left, window_size_right, softcap, return_softmax, gen_, sink);
-}
-
-static std::vector<at::Tensor>
-mha_varlen_fwd_impl(at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
-               c10::optional<at::Tensor>& out_, const at::Tensor& cu_seqlens_q,
-               const at::Tensor& cu_seqlens_k, c10::optional<at::Tensor>& seqused_k,
-               c10::optional<at::Tensor>& block_table_, c10::optional<at::Tensor>& alibi_slopes_,
-               int max_seqlen_q, const int max_seqlen_k, const float p_dropout,
-               const float softmax_scale, const bool zero_tensors, bool is_causal,
-               int window_size_left, int window_size_right, const float softcap,
-               const bool return_softmax, c10::optional<at::Generator> gen_,
-               const c10::optional<at::Tensor>& sink_) {
+mha_varlen_fwd(const OptTensor& sink_, at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+               OptTensor& out_, const at::Tensor& cu_seqlens_q, const at::Tensor& cu_seqlens_k,
+               OptTensor& seqused_k, OptTensor& block_table_, OptTensor& alibi_slopes_, int max_seqlen_q,
+               const int max_seqlen_k, const float p_dropout, const float softmax_scale,
+               const bool zero_tensors, bool is_causal, int window_size_left, int window_size_right,
+               const float softcap, const bool return_softmax, c10::optional<at::Generator> gen_) {
     check_qkv_dtype(q, k, v);
-    TORCH_CHECK(cu_seqlens_q.dtype() == torch::kInt32, "cu_seqlens_q must have dtype int32");
-    TORCH_CHECK(cu_seqlens_k.dtype() == torch::kInt32, "cu_seqlens_k must have dtype int32");
-    CHECK_DEVICE(cu_seqlens_q); CHECK_DEVICE(cu_seqlens_k);
-    CHECK_CONTIGUOUS(cu_seqlens_q); CHECK_CONTIGUOUS(cu_seqlens_k);
+    const int batch_size = check_cu_seqlens(cu_seqlens_q, cu_seqlens_k);
+    const auto [total_q, num_heads, head_size_og] = dims<3>(q, "q", kPacked);
     at::Tensor block_table;
     const bool paged_KV = block_table_.has_value();
     if (paged_KV) {
         block_table = block_table_.value();
-        CHECK_DEVICE(block_table);
-        TORCH_CHECK(block_table.dtype() == torch::kInt32, "block_table must have dtype torch.int32");
-        TORCH_CHECK(block_table.stride(-1) == 1, "block_table must have contiguous last dimension");
+        check_block_table(block_table, batch_size);
     }
-    const auto sizes = q.sizes();
-    const int batch_size = cu_seqlens_q.numel() - 1;
-    const int num_heads = sizes[1];
-    const int head_size_og = sizes[2];
     const int num_heads_k = paged_KV ? k.size(2) : k.size(1);
-    const int total_q = sizes[0];
-    TORCH_CHECK(batch_size > 0, "batch size must be positive");
-    TORCH_CHECK(head_size_og <= 256, "FlashAttention forward only supports head dimension at most 256");
-    TORCH_CHECK(num_heads % num_heads_k == 0, "Number of heads in key/value must divide number of heads in query");
-    TORCH_CHECK(p_dropout >= 0.f && p_dropout < 1.f, "p_dropout must be in [0, 1)");
-    if (softcap > 0.f) { TORCH_CHECK(p_dropout == 0.f, "Softcapping does not support dropout for now"); }
-    TORCH_CHECK(!return_softmax || p_dropout > 0.f, "return_softmax is only supported when p_dropout > 0.0");
+    check_heads(batch_size, num_heads, num_heads_k, head_size_og, "forward");
+    check_dropout(p_dropout, softcap, return_softmax);
     TORCH_CHECK(p_dropout == 0.f || !paged_KV, "dropout over a paged K/V cache is not supported");
-    const int max_num_blocks_per_seq = !paged_KV ? 0 : block_table.size(1);
-    const int num_blocks = !paged_KV ? 0 : k.size(0);
     const int page_block_size = !paged_KV ? 1 : k.size(1);
-    if (max_seqlen_q == 1 && !alibi_slopes_.has_value()) is_causal = false;
-    if (is_causal) window_size_right = 0;
-    if (window_size_left >= max_seqlen_k) window_size_left = -1;
-    if (window_size_right >= max_seqlen_k) window_size_right = -1;
-    CHECK_SHAPE(q, total_q, num_heads, head_size_og);
+    normalize_window(is_causal, max_seqlen_q == 1 && !alibi_slopes_.has_value(), max_seqlen_k,
+                     /*clip_first=*/false, window_size_left, window_size_right);
     if (!paged_KV) {
         const int total_k = k.size(0);
         CHECK_SHAPE(k, total_k, num_heads_k, head_size_og);
         CHECK_SHAPE(v, total_k, num_heads_k, head_size_og);
     } else {
+        const int num_blocks = k.size(0);
         CHECK_SHAPE(k, num_blocks, page_block_size, num_heads_k, head_size_og);
         CHECK_SHAPE(v, num_blocks, page_block_size, num_heads_k, head_size_og);
-        CHECK_SHAPE(block_table, batch_size, max_num_blocks_per_seq);
     }
-    CHECK_SHAPE(cu_seqlens_q, batch_size + 1);
-    CHECK_SHAPE(cu_seqlens_k, batch_size + 1);
-    at::Tensor seqused;
-    if (seqused_k.has_value()) {
-        seqused = seqused_k.value();
-        TORCH_CHECK(seqused.dtype() == torch::kInt32, "seqused_k must have dtype int32");
-        TORCH_CHECK(seqused.is_cuda(), "seqused_k must be on CUDA device");
-        TORCH_CHECK(seqused.is_contiguous(), "seqused_k must be contiguous");
-        CHECK_SHAPE(seqused, batch_size);
-    }
+    at::Tensor seqused = batch_int32(seqused_k, batch_size, "seqused_k");
     at::Tensor q_padded = dense(pad_last(q, head_size_og));
     at::Tensor k_padded = dense(pad_last(k, head_size_og));
     at::Tensor v_padded = dense(pad_last(v, head_size_og));
-    at::Tensor out;
-    if (out_.has_value()) {
-        out = out_.value();
-        TORCH_CHECK(out.dtype() == q.dtype(), "Output must have the same dtype as inputs");
-        CHECK_DEVICE(out);
-        TORCH_CHECK(out.stride(-1) == 1, "Output tensor must have contiguous last dimension");
-        CHECK_SHAPE(out, sizes[0], sizes[1], head_size_og);
-        if (head_size_og % 8 != 0 || !out.is_contiguous() || !aligned16(out)) out = torch::empty_like(q_padded);
-    } else {
-        out = torch::empty_like(q_padded);
-    }
-    const int head_size = round8(head_size_og);
+    at::Tensor out_padded = take_out(out_, q.options(), {total_q, num_heads, head_size_og},
+                                     /*strided_ok=*/false, /*refuse_indirect=*/false);
     const c10::DeviceGuard device_guard(q.device());
     auto opts = q.options();
     auto softmax_lse = torch::empty({num_heads, total_q}, opts.dtype(at::kFloat));
@@ -364,184 +432,88 @@ mha_varlen_fwd_impl(at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
     auto rng_state = dropout_rng(p_dropout, gen_, (int64_t)batch_size * num_heads * 32, q.device());
     RngDisarm rng_disarm;
     if (zero_tensors) {
-        out.zero_();
+        out_padded.zero_();
         softmax_lse.fill_(-std::numeric_limits<float>::infinity());
     }
-    int64_t alibi_bs = 0;
-    at::Tensor alibi = alibi_for_c(alibi_slopes_, batch_size, num_heads, &alibi_bs);
+    const Alibi alibi = alibi_for_c(alibi_slopes_, batch_size, num_heads);
     const float* sink = sink_for_c(sink_, q, num_heads);
-    if (max_seqlen_k > 0 && sink) {
+    if (max_seqlen_k > 0) {
         fmha_varlen_fwd_sink(q_padded.data_ptr(), k_padded.data_ptr(), v_padded.data_ptr(),
-                             out.data_ptr(), softmax_lse.data_ptr(), cu_seqlens_q.data_ptr(),
-                             cu_seqlens_k.data_ptr(), seqused.defined() ? seqused.data_ptr() : nullptr,
-                             paged_KV ? block_table.data_ptr() : nullptr,
+                             out_padded.data_ptr(), softmax_lse.data_ptr(), cu_seqlens_q.data_ptr(),
+                             cu_seqlens_k.data_ptr(), ptr_or_null(seqused), ptr_or_null(block_table),
                              paged_KV ? (int)block_table.stride(0) : 0, page_block_size,
-                             alibi.defined() ? alibi.data_ptr() : nullptr, (int)alibi_bs,
-                             max_seqlen_q, max_seqlen_k, total_q, batch_size, num_heads, num_heads_k,
-                             head_size, softmax_scale, window_size_left, window_size_right, softcap,
-                             q.dtype() == torch::kFloat16, cur_stream(), p_dropout,
-                             p.defined() ? p.data_ptr() : nullptr, sink);
-        raise_if_failed("varlen_fwd_sink");
-    } else if (max_seqlen_k > 0) {
-        fmha_varlen_fwd_ex(q_padded.data_ptr(), k_padded.data_ptr(), v_padded.data_ptr(),
-                           out.data_ptr(), softmax_lse.data_ptr(), cu_seqlens_q.data_ptr(),
-                           cu_seqlens_k.data_ptr(), seqused.defined() ? seqused.data_ptr() : nullptr,
-                           paged_KV ? block_table.data_ptr() : nullptr,
-                           paged_KV ? (int)block_table.stride(0) : 0, page_block_size,
-                           alibi.defined() ? alibi.data_ptr() : nullptr, (int)alibi_bs,
-                           max_seqlen_q, max_seqlen_k, total_q, batch_size, num_heads, num_heads_k,
-                           head_size, softmax_scale, window_size_left, window_size_right, softcap,
-                           q.dtype() == torch::kFloat16, cur_stream(), p_dropout,
-                           p.defined() ? p.data_ptr() : nullptr);
+                             ptr_or_null(alibi.slopes), alibi.batch_stride, max_seqlen_q, max_seqlen_k,
+                             total_q, batch_size, num_heads, num_heads_k, round8(head_size_og), softmax_scale,
+                             window_size_left, window_size_right, softcap, q.dtype() == torch::kFloat16,
+                             cur_stream(), p_dropout, ptr_or_null(p), sink);
         raise_if_failed("varlen_fwd");
     } else {
-        out.zero_();
+        out_padded.zero_();
         softmax_lse.fill_(std::numeric_limits<float>::infinity());
     }
-    at::Tensor out_padded = out;
-    if (head_size_og % 8 != 0) out = out.index({"...", torch::indexing::Slice(torch::indexing::None, head_size_og)});
-    if (out_.has_value() && !out_.value().is_same(out)) out_.value().copy_(out), out = out_.value();
-    return {out, q_padded, k_padded, v_padded, out_padded, softmax_lse, p, rng_state};
+    return {finish_out(out_, out_padded, head_size_og), q_padded, k_padded, v_padded, out_padded, softmax_lse,
+            p, rng_state};
 }
 
+// `fwd_kvcache`, and `fwd_kvcache_sink` with a trailing sink
 std::vector<at::Tensor>
-mha_varlen_fwd(at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
-               c10::optional<at::Tensor>& out_, const at::Tensor& cu_seqlens_q,
-               const at::Tensor& cu_seqlens_k, c10::optional<at::Tensor>& seqused_k,
-               c10::optional<at::Tensor>& block_table_, c10::optional<at::Tensor>& alibi_slopes_,
-               int max_seqlen_q, const int max_seqlen_k, const float p_dropout,
-               const float softmax_scale, const bool zero_tensors, bool is_causal,
-               int window_size_left, int window_size_right, const float softcap,
-               const bool return_softmax, c10::optional<at::Generator> gen_) {
-    return mha_varlen_fwd_impl(q, k, v, out_, cu_seqlens_q, cu_seqlens_k, seqused_k, block_table_,
-                               alibi_slopes_, max_seqlen_q, max_seqlen_k, p_dropout, softmax_scale,
-                               zero_tensors, is_causal, window_size_left, window_size_right, softcap,
-                               return_softmax, gen_, c10::nullopt);
-}
-
-// `varlen_fwd` plus a trailing sink: fmha_varlen_fwd_sink
-std::vector<at::Tensor>
-mha_varlen_fwd_sink(at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
-                    c10::optional<at::Tensor>& out_, const at::Tensor& cu_seqlens_q,
-                    const at::Tensor& cu_seqlens_k, c10::optional<at::Tensor>& seqused_k,
-                    c10::optional<at::Tensor>& block_table_, c10::optional<at::Tensor>& alibi_slopes_,
-                    int max_seqlen_q, const int max_seqlen_k, const float p_dropout,
-                    const float softmax_scale, const bool zero_tensors, bool is_causal,
-                    int window_size_left, int window_size_right, const float softcap,
-                    const bool return_softmax, c10::optional<at::Generator> gen_,
-                    const at::Tensor& sink) {
-    return mha_varlen_fwd_impl(q, k, v, out_, cu_seqlens_q, cu_seqlens_k, seqused_k, block_table_,
-                               alibi_slopes_, max_seqlen_q, max_seqlen_k, p_dropout, softmax_scale,
-                               zero_tensors, is_causal, window_size_left, window_size_right, softcap,
-                               return_softmax, gen_, sink);
-}
-
-static std::vector<at::Tensor>
-mha_fwd_kvcache_impl(at::Tensor& q, const at::Tensor& kcache, const at::Tensor& vcache,
-                c10::optional<const at::Tensor>& k_, c10::optional<const at::Tensor>& v_,
-                c10::optional<const at::Tensor>& seqlens_k_,
-                c10::optional<const at::Tensor>& rotary_cos_,
-                c10::optional<const at::Tensor>& rotary_sin_,
-                c10::optional<const at::Tensor>& cache_batch_idx_,
-                c10::optional<at::Tensor>& block_table_, c10::optional<at::Tensor>& alibi_slopes_,
-                c10::optional<at::Tensor>& out_, const float softmax_scale, bool is_causal,
-                int window_size_left, int window_size_right, const float softcap,
-                bool is_rotary_interleaved, int num_splits,
-                c10::optional<const at::Tensor>& cache_leftpad_,
-                const c10::optional<at::Tensor>& sink_) {
+mha_fwd_kvcache(const OptTensor& sink_, at::Tensor& q, const at::Tensor& kcache, const at::Tensor& vcache,
+                OptConstTensor& k_, OptConstTensor& v_, OptConstTensor& seqlens_k_,
+                OptConstTensor& rotary_cos_, OptConstTensor& rotary_sin_, OptConstTensor& cache_batch_idx_,
+                OptTensor& block_table_, OptTensor& alibi_slopes_, OptTensor& out_, const float softmax_scale,
+                bool is_causal, int window_size_left, int window_size_right, const float softcap,
+                bool is_rotary_interleaved, int num_splits, OptConstTensor& cache_leftpad_) {
     check_qkv_dtype(q, kcache, vcache);
     const bool append = k_.has_value();
     const bool local_or_causal = is_causal || window_size_left >= 0 || window_size_right >= 0;
+    const auto [batch_size, seqlen_q, num_heads, head_size_og] = dims<4>(q, "q", kDense);
     at::Tensor block_table;
     const bool paged_KV = block_table_.has_value();
     if (paged_KV) {
         block_table = block_table_.value();
-        CHECK_DEVICE(block_table);
-        TORCH_CHECK(block_table.dtype() == torch::kInt32, "block_table must have dtype torch.int32");
-        TORCH_CHECK(block_table.stride(-1) == 1, "block_table must have contiguous last dimension");
+        check_block_table(block_table, batch_size);
     }
-    const auto sizes = q.sizes();
-    const int batch_size = sizes[0];
-    const int seqlen_q = sizes[1];
-    const int num_heads = sizes[2];
-    const int head_size_og = sizes[3];
     const int max_num_blocks_per_seq = !paged_KV ? 1 : block_table.size(1);
-    const int num_blocks = !paged_KV ? kcache.size(0) : kcache.size(0);
-    const int page_block_size = !paged_KV ? kcache.size(1) : kcache.size(1);
+    const int num_blocks = kcache.size(0);      // (a dense cache: its batch, one "page" per sequence)
+    const int page_block_size = kcache.size(1);
     const int seqlen_k = max_num_blocks_per_seq * page_block_size;
     const int num_heads_k = kcache.size(2);
-    TORCH_CHECK(batch_size > 0, "batch size must be positive");
-    TORCH_CHECK(head_size_og <= 256, "FlashAttention forward only supports head dimension at most 256");
-    TORCH_CHECK(num_heads % num_heads_k == 0, "Number of heads in key/value must divide number of heads in query");
-    if (seqlen_q == 1 && !alibi_slopes_.has_value()) is_causal = false;
-    if (is_causal) window_size_right = 0;
-    if (window_size_left >= seqlen_k) window_size_left = -1;
-    if (window_size_right >= seqlen_k) window_size_right = -1;
-    CHECK_SHAPE(q, batch_size, seqlen_q, num_heads, head_size_og);
+    check_heads(batch_size, num_heads, num_heads_k, head_size_og, "forward");
+    normalize_window(is_causal, seqlen_q == 1 && !alibi_slopes_.has_value(), seqlen_k, /*clip_first=*/false,
+                     window_size_left, window_size_right);
+    CHECK_SHAPE(kcache, num_blocks, page_block_size, num_heads_k, head_size_og);
+    CHECK_SHAPE(vcache, num_blocks, page_block_size, num_heads_k, head_size_og);
     if (!paged_KV) {
-        // Dense cache [batch_cache, seqlen_k, hk, d]: one "page" per sequence (the reference's
-        // non-paged branch dereferences an undefined block_table, export.cpp:1711); the page of
-        // batch b is cache_batch_idx[b] when given, else b.
-        const int bc = kcache.size(0);
-        CHECK_SHAPE(kcache, bc, page_block_size, num_heads_k, head_size_og);
-        CHECK_SHAPE(vcache, bc, page_block_size, num_heads_k, head_size_og);
+        // Dense cache [batch_cache, seqlen_k, hk, d] (the reference's non-paged branch dereferences
+        // an undefined block_table, export.cpp:1711); the page of batch b is cache_batch_idx[b]
+        // when given, else b.
         if (cache_batch_idx_.has_value()) {
-            auto idx = cache_batch_idx_.value();
-            CHECK_DEVICE(idx); CHECK_CONTIGUOUS(idx);
-            TORCH_CHECK(idx.scalar_type() == torch::kInt32, "cache_batch_idx must have dtype int32");
-            CHECK_SHAPE(idx, batch_size);
-            block_table = idx.view({batch_size, 1});
+            block_table = batch_int32(cache_batch_idx_, batch_size, "cache_batch_idx").view({batch_size, 1});
         } else {
-            TORCH_CHECK(bc == batch_size, "k_cache batch must equal q batch without cache_batch_idx");
+            TORCH_CHECK(num_blocks == batch_size, "k_cache batch must equal q batch without cache_batch_idx");
             block_table = torch::arange(batch_size, q.options().dtype(torch::kInt32)).view({batch_size, 1});
         }
     } else {
         TORCH_CHECK(!cache_batch_idx_.has_value(),
                     "cache_batch_idx cannot be combined with a paged KV cache");
-        CHECK_SHAPE(kcache, num_blocks, page_block_size, num_heads_k, head_size_og);
-        CHECK_SHAPE(vcache, num_blocks, page_block_size, num_heads_k, head_size_og);
-        CHECK_SHAPE(block_table, batch_size, max_num_blocks_per_seq);
     }
     at::Tensor q_padded = dense(pad_last(q, head_size_og));
     at::Tensor kc = dense(pad_last(kcache, head_size_og));
     at::Tensor vc = dense(pad_last(vcache, head_size_og));
-    at::Tensor out;
-    if (out_.has_value()) {
-        out = out_.value();
-        TORCH_CHECK(out.dtype() == q.dtype(), "Output must have the same dtype as inputs");
-        CHECK_DEVICE(out);
-        TORCH_CHECK(out.stride(-1) == 1, "Output tensor must have contiguous last dimension");
-        CHECK_SHAPE(out, batch_size, seqlen_q, num_heads, head_size_og);
-        if (head_size_og % 8 != 0 || !out.is_contiguous() || !aligned16(out)) out = torch::empty_like(q_padded);
-    } else {
-        out = torch::empty_like(q_padded);
-    }
+    at::Tensor out = take_out(out_, q.options(), {batch_size, seqlen_q, num_heads, head_size_og},
+                              /*strided_ok=*/false, /*refuse_indirect=*/false);
     const int head_size = round8(head_size_og);
     const c10::DeviceGuard device_guard(q.device());
-    auto opts = q.options();
-    auto softmax_lse = torch::empty({batch_size, num_heads, seqlen_q}, opts.dtype(at::kFloat));
-    at::Tensor seqlens;
-    if (seqlens_k_.has_value()) {
-        seqlens = seqlens_k_.value();
-        TORCH_CHECK(seqlens.dtype() == torch::kInt32, "seqlens_k must have dtype int32");
-        CHECK_DEVICE(seqlens);
-        CHECK_CONTIGUOUS(seqlens);
-        CHECK_SHAPE(seqlens, batch_size);
-    }
+    auto softmax_lse = torch::empty({batch_size, num_heads, seqlen_q}, q.options().dtype(at::kFloat));
+    at::Tensor seqlens = batch_int32(seqlens_k_, batch_size, "seqlens_k");
     // cache_leftpad (flash-attn's leftpad_k, commented out at export.cpp:1443,1627-1634): batch b's
     // sequence is cache rows [leftpad[b], seqlens_k[b]); non-paged caches only, as there
-    at::Tensor leftpad;
-    if (cache_leftpad_.has_value()) {
-        leftpad = cache_leftpad_.value();
-        TORCH_CHECK(!paged_KV, "We don't support Paged KV and leftpad_k running at the same time yet");
-        TORCH_CHECK(leftpad.dtype() == torch::kInt32, "leftpad_k must have dtype int32");
-        CHECK_DEVICE(leftpad);
-        CHECK_CONTIGUOUS(leftpad);
-        CHECK_SHAPE(leftpad, batch_size);
-        TORCH_CHECK(seqlens.defined(), "cache_leftpad needs seqlens_k");
-    }
-    int64_t alibi_bs = 0;
-    at::Tensor alibi = alibi_for_c(alibi_slopes_, batch_size, num_heads, &alibi_bs);
+    TORCH_CHECK(!cache_leftpad_.has_value() || !paged_KV,
+                "We don't support Paged KV and leftpad_k running at the same time yet");
+    at::Tensor leftpad = batch_int32(cache_leftpad_, batch_size, "leftpad_k");
+    TORCH_CHECK(!leftpad.defined() || seqlens.defined(), "cache_leftpad needs seqlens_k");
+    const Alibi alibi = alibi_for_c(alibi_slopes_, batch_size, num_heads);
+    const float* sink = sink_for_c(sink_, q, num_heads);
     at::Tensor q_attn = q_padded;
     if (append) {
         // write the new rows into the cache in place (+ rotary on k and q), then attend over the
@@ -559,32 +531,15 @@ mha_fwd_kvcache_impl(at::Tensor& q, const at::Tensor& kcache, const at::Tensor& 
         TORCH_CHECK(seqlen_q <= seqlen_k, "If key is supplied, it must have seqlen <= the seqlen of the KV cache");
         TORCH_CHECK(head_size_og % 8 == 0 && kcache.is_contiguous() && vcache.is_contiguous(),
                     "appending needs contiguous caches with head_size a multiple of 8 (updated in place)");
-        int rotary_dim = 0;
-        at::Tensor cos, sin, q_rot;
-        if (rotary_cos_.has_value()) {
-            TORCH_CHECK(rotary_sin_.has_value(), "If rotary cos is provided, rotary sin must also be provided");
-            cos = rotary_cos_.value();
-            sin = rotary_sin_.value();
-            CHECK_DEVICE(cos); CHECK_DEVICE(sin); CHECK_CONTIGUOUS(cos); CHECK_CONTIGUOUS(sin);
-            rotary_dim = cos.size(1) * 2;
-            TORCH_CHECK(rotary_dim <= head_size_og, "rotary_dim must be <= headdim");
-            TORCH_CHECK(rotary_dim % 16 == 0, "Only rotary dimensions divisible by 16 are currently supported");
-            TORCH_CHECK(cos.size(0) >= seqlen_k, "cos/sin seqlen must be at least the seqlen of KV cache");
-            CHECK_SHAPE(sin, cos.size(0), rotary_dim / 2);
-            TORCH_CHECK(cos.scalar_type() == q.scalar_type() && sin.scalar_type() == q.scalar_type(),
-                        "rotary_cos/sin must have the same dtype as query");
-            q_rot = torch::empty_like(q_padded);
-        }
+        const Rotary rotary = check_rotary(rotary_cos_, rotary_sin_, q, head_size_og, seqlen_k);
+        at::Tensor q_rot = rotary.cos.defined() ? torch::empty_like(q_padded) : at::Tensor();
         auto seqlens_new = torch::empty_like(seqlens);
-        fmha_kvcache_append(q_padded.data_ptr(), q_rot.defined() ? q_rot.data_ptr() : nullptr,
-                            kc.data_ptr(), vc.data_ptr(), kn.data_ptr(), vn.data_ptr(), seqlen_new,
-                            block_table.data_ptr(), (int)block_table.stride(0), page_block_size,
-                            seqlens.data_ptr(), seqlens_new.data_ptr(),
-                            cos.defined() ? cos.data_ptr() : nullptr,
-                            sin.defined() ? sin.data_ptr() : nullptr, rotary_dim,
-                            is_rotary_interleaved, local_or_causal, batch_size, seqlen_q,
-                            num_heads, num_heads_k, head_size, q.dtype() == torch::kFloat16,
-                            cur_stream());
+        fmha_kvcache_append(q_padded.data_ptr(), ptr_or_null(q_rot), kc.data_ptr(), vc.data_ptr(),
+                            kn.data_ptr(), vn.data_ptr(), seqlen_new, block_table.data_ptr(),
+                            (int)block_table.stride(0), page_block_size, seqlens.data_ptr(),
+                            seqlens_new.data_ptr(), ptr_or_null(rotary.cos), ptr_or_null(rotary.sin),
+                            rotary.dim, is_rotary_interleaved, local_or_causal, batch_size, seqlen_q,
+                            num_heads, num_heads_k, head_size, q.dtype() == torch::kFloat16, cur_stream());
         raise_if_failed("fwd_kvcache (append)");
         seqlens = seqlens_new;
         if (q_rot.defined()) q_attn = q_rot;
@@ -592,71 +547,14 @@ mha_fwd_kvcache_impl(at::Tensor& q, const at::Tensor& kcache, const at::Tensor& 
         TORCH_CHECK(!rotary_cos_.has_value(),
                     "If rotary cos/sin are provided, new key / value to be appended to KV cache must also be provided");
     }
-    if (const float* sink = sink_for_c(sink_, q, num_heads)) {
-        fmha_page_kvcache_fwd_sink(q_attn.data_ptr(), kc.data_ptr(), vc.data_ptr(), out.data_ptr(),
-                                   softmax_lse.data_ptr(), block_table.data_ptr(),
-                                   (int)block_table.stride(0),
-                                   seqlens.defined() ? seqlens.data_ptr() : nullptr, seqlen_q, seqlen_k,
-                                   batch_size, num_heads, num_heads_k, head_size, page_block_size,
-                                   softmax_scale, window_size_left, window_size_right, softcap,
-                                   alibi.defined() ? alibi.data_ptr() : nullptr, (int)alibi_bs,
-                                   num_splits, 0, 1.f, 1.f,
-                                   leftpad.defined() ? leftpad.data_ptr() : nullptr,
-                                   q.dtype() == torch::kFloat16, cur_stream(), sink);
-        raise_if_failed("fwd_kvcache_sink");
-    } else {
-        fmha_page_kvcache_fwd_ex(q_attn.data_ptr(), kc.data_ptr(), vc.data_ptr(), out.data_ptr(),
-                                 softmax_lse.data_ptr(), block_table.data_ptr(),
-                                 (int)block_table.stride(0),
-                                 seqlens.defined() ? seqlens.data_ptr() : nullptr, seqlen_q, seqlen_k,
-                                 batch_size, num_heads, num_heads_k, head_size, page_block_size,
-                                 softmax_scale, window_size_left, window_size_right, softcap,
-                                 alibi.defined() ? alibi.data_ptr() : nullptr, (int)alibi_bs,
-                                 num_splits, 0, 1.f, 1.f,
-                                 leftpad.defined() ? leftpad.data_ptr() : nullptr,
-                                 q.dtype() == torch::kFloat16, cur_stream());
-        raise_if_failed("fwd_kvcache");
-    }
-    if (head_size_og % 8 != 0) out = out.index({"...", torch::indexing::Slice(torch::indexing::None, head_size_og)});
-    if (out_.has_value() && !out_.value().is_same(out)) out_.value().copy_(out), out = out_.value();
-    return {out, softmax_lse};
-}
-
-std::vector<at::Tensor>
-mha_fwd_kvcache(at::Tensor& q, const at::Tensor& kcache, const at::Tensor& vcache,
-                c10::optional<const at::Tensor>& k_, c10::optional<const at::Tensor>& v_,
-                c10::optional<const at::Tensor>& seqlens_k_,
-                c10::optional<const at::Tensor>& rotary_cos_,
-                c10::optional<const at::Tensor>& rotary_sin_,
-                c10::optional<const at::Tensor>& cache_batch_idx_,
-                c10::optional<at::Tensor>& block_table_, c10::optional<at::Tensor>& alibi_slopes_,
-                c10::optional<at::Tensor>& out_, const float softmax_scale, bool is_causal,
-                int window_size_left, int window_size_right, const float softcap,
-                bool is_rotary_interleaved, int num_splits,
-                c10::optional<const at::Tensor>& cache_leftpad_) {
-    return mha_fwd_kvcache_impl(q, kcache, vcache, k_, v_, seqlens_k_, rotary_cos_, rotary_sin_,
-                                cache_batch_idx_, block_table_, alibi_slopes_, out_, softmax_scale,
-                                is_causal, window_size_left, window_size_right, softcap,
-                                is_rotary_interleaved, num_splits, cache_leftpad_, c10::nullopt);
-}
-
-// `fwd_kvcache` plus a trailing sink: fmha_page_kvcache_fwd_sink
-std::vector<at::Tensor>
-mha_fwd_kvcache_sink(at::Tensor& q, const at::Tensor& kcache, const at::Tensor& vcache,
-                     c10::optional<const at::Tensor>& k_, c10::optional<const at::Tensor>& v_,
-                     c10::optional<const at::Tensor>& seqlens_k_,
-                     c10::optional<const at::Tensor>& rotary_cos_,
-                     c10::optional<const at::Tensor>& rotary_sin_,
-                     c10::optional<const at::Tensor>& cache_batch_idx_,
-                     c10::optional<at::Tensor>& block_table_, c10::optional<at::Tensor>& alibi_slopes_,
-                     c10::optional<at::Tensor>& out_, const float softmax_scale, bool is_causal,
-                     int window_size_left, int window_size_right, const float softcap,
-                     bool is_rotary_interleaved, int num_splits,
-                     c10::optional<const at::Tensor>& cache_leftpad_, const at::Tensor& sink) {
-    return mha_fwd_kvcache_impl(q, kcache, vcache, k_, v_, seqlens_k_, rotary_cos_, rotary_sin_,
-                                cache_batch_idx_, block_table_, alibi_slopes_, out_, softmax_scale,
-                                is_causal, window_size_left, window_size_right, softcap,
-                                is_rotary_interleaved, num_splits, cache_leftpad_, sink);
+    fmha_page_kvcache_fwd_sink(q_attn.data_ptr(), kc.data_ptr(), vc.data_ptr(), out.data_ptr(),
+                               softmax_lse.data_ptr(), block_table.data_ptr(), (int)block_table.stride(0),
+                               ptr_or_null(seqlens), seqlen_q, seqlen_k, batch_size, num_heads, num_heads_k,
+                               head_size, page_block_size, softmax_scale, window_size_left, window_size_right,
+                               softcap, ptr_or_null(alibi.slopes), alibi.batch_stride, num_splits, 0, 1.f, 1.f,
+                               ptr_or_null(leftpad), q.dtype() == torch::kFloat16, cur_stream(), sink);
+    raise_if_failed("fwd_kvcache");
+    return {finish_out(out_, out, head_size_og), softmax_lse};
 }
 
 // Gradient of the sink from a backward's saved softmax_lse and its softmax_d: dense
@@ -683,68 +581,53 @@ mha_sink_bwd(const at::Tensor& softmax_lse, const at::Tensor& softmax_d, const a
     return dsink;
 }
 
-// Gradient outputs (export.cpp:1037-1060): a caller-given tensor must match q/k/v in dtype,
-// device and shape; a non-contiguous one is computed into a contiguous temporary and copied
-// back by grad_writeback.
-static at::Tensor grad_out(c10::optional<at::Tensor>& t, const at::Tensor& like) {
-    if (t.has_value()) {
-        const at::Tensor& x = t.value();
-        TORCH_CHECK(x.dtype() == like.dtype(), "gradient must have the same dtype as its input");
-        CHECK_DEVICE(x);
-        TORCH_CHECK(x.sizes() == like.sizes(), "gradient has the wrong shape");
-        if (x.is_contiguous() && aligned16(x)) return x;
-    }
-    return torch::empty_like(like, like.options().memory_format(at::MemoryFormat::Contiguous));
+namespace {
+
+// what `bwd` and `varlen_bwd` check alike before their shapes: q / k / v are the forward's padded
+// tensors (head_size), dout the caller's (head_size_og)
+void check_bwd_args(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, float p_dropout,
+                    float softcap, const OptTensor& rng_state) {
+    check_qkv_dtype(q, k, v);
+    check_dropout(p_dropout, softcap, /*return_softmax=*/false);
+    dropout_rng_restore(p_dropout, rng_state);
 }
-static void grad_writeback(c10::optional<at::Tensor>& t, at::Tensor& g) {
-    if (t.has_value() && !t.value().is_same(g)) { t.value().copy_(g); g = t.value(); }
+void check_bwd_heads(int batch_size, int num_heads, int num_heads_k, int head_size, int head_size_og) {
+    TORCH_CHECK(head_size % 8 == 0, "head_size should be a multiple of 8");
+    check_heads(batch_size, num_heads, num_heads_k, head_size, "backward");
+    TORCH_CHECK(head_size == round8(head_size_og), "head_size must be head_size_og rounded to a multiple of 8");
 }
+
+}  // namespace
 
 std::vector<at::Tensor>
 mha_bwd(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
-        const at::Tensor& out, const at::Tensor& softmax_lse, c10::optional<at::Tensor>& dq_,
-        c10::optional<at::Tensor>& dk_, c10::optional<at::Tensor>& dv_,
-        c10::optional<at::Tensor>& alibi_slopes_, const float p_dropout,
-        const float softmax_scale, const bool is_causal, int window_size_left,
-        int window_size_right, const float softcap, const bool deterministic,
-        c10::optional<at::Generator> /*gen_*/, c10::optional<at::Tensor>& rng_state) {
-    check_qkv_dtype(q, k, v);
-    if (is_causal) window_size_right = 0;
+        const at::Tensor& out, const at::Tensor& softmax_lse, OptTensor& dq_, OptTensor& dk_, OptTensor& dv_,
+        OptTensor& alibi_slopes_, const float p_dropout, const float softmax_scale, const bool is_causal,
+        int window_size_left, int window_size_right, const float softcap, const bool deterministic,
+        c10::optional<at::Generator> /*gen_*/, OptTensor& rng_state) {
     TORCH_CHECK(out.dtype() == q.dtype(), "query and out must have the same dtype");
     TORCH_CHECK(dout.dtype() == q.dtype(), "query and dout must have the same dtype");
     CHECK_DEVICE(out); CHECK_DEVICE(dout); CHECK_DEVICE(softmax_lse);
-    TORCH_CHECK(p_dropout >= 0.f && p_dropout < 1.f, "p_dropout must be in [0, 1)");
-    if (softcap > 0.f) { TORCH_CHECK(p_dropout == 0.f, "Softcapping does not support dropout for now"); }
-    dropout_rng_restore(p_dropout, rng_state);
+    check_bwd_args(q, k, v, p_dropout, softcap, rng_state);
     RngDisarm rng_disarm;
-    const auto sizes = q.sizes();
-    const int batch_size = sizes[0];
-    const int seqlen_q = sizes[1];
-    const int num_heads = sizes[2];
+    const auto [batch_size, seqlen_q, num_heads, head_size] = dims<4>(q, "q", kDense);
     const int head_size_og = dout.size(3);
-    const int head_size = sizes[3];
     const int seqlen_k = k.size(1);
     const int num_heads_k = k.size(2);
-    TORCH_CHECK(batch_size > 0, "batch size must be positive");
-    TORCH_CHECK(head_size % 8 == 0, "head_size should be a multiple of 8");
-    TORCH_CHECK(head_size <= 256, "FlashAttention backward only supports head dimension at most 256");
-    TORCH_CHECK(num_heads % num_heads_k == 0, "Number of heads in key/value must divide number of heads in query");
-    TORCH_CHECK(head_size == round8(head_size_og), "head_size must be head_size_og rounded to a multiple of 8");
-    if (window_size_left >= seqlen_k) window_size_left = -1;
-    if (window_size_right >= seqlen_k) window_size_right = -1;
-    CHECK_SHAPE(q, batch_size, seqlen_q, num_heads, head_size);
+    check_bwd_heads(batch_size, num_heads, num_heads_k, head_size, head_size_og);
+    normalize_window(is_causal, /*single_row=*/false, seqlen_k, /*clip_first=*/false, window_size_left,
+                     window_size_right);
     CHECK_SHAPE(k, batch_size, seqlen_k, num_heads_k, head_size);
     CHECK_SHAPE(v, batch_size, seqlen_k, num_heads_k, head_size);
     CHECK_SHAPE(out, batch_size, seqlen_q, num_heads, head_size);
     CHECK_SHAPE(dout, batch_size, seqlen_q, num_heads, head_size_og);
     CHECK_SHAPE(softmax_lse, batch_size, num_heads, seqlen_q);
-    at::Tensor dq = grad_out(dq_, q), dk = grad_out(dk_, k), dv = grad_out(dv_, v);
+    at::Tensor dq = take_grad(dq_, q), dk = take_grad(dk_, k), dv = take_grad(dv_, v);
     at::Tensor dout_padded = dense(pad_last(dout, head_size_og));
     const c10::DeviceGuard device_guard(q.device());
     auto opts = q.options();
     auto softmax_d = torch::empty({batch_size, num_heads, seqlen_q}, opts.dtype(at::kFloat));
-    int64_t alibi_bs = 0;
-    at::Tensor alibi = alibi_for_c(alibi_slopes_, batch_size, num_heads, &alibi_bs);
+    const Alibi alibi = alibi_for_c(alibi_slopes_, batch_size, num_heads);
     auto qc = dense(q), kc = dense(k), vc = dense(v), oc = dense(out);
     auto lse = softmax_lse.contiguous();
     const size_t ws = fmha_bwd_workspace_size(seqlen_q, seqlen_k, batch_size, num_heads, num_heads_k,
@@ -752,166 +635,102 @@ mha_bwd(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k, const 
     at::Tensor workspace = torch::empty({(int64_t)ws}, opts.dtype(torch::kUInt8));
     if (seqlen_q > 0) {
         fmha_bwd(dout_padded.data_ptr(), qc.data_ptr(), kc.data_ptr(), vc.data_ptr(), oc.data_ptr(),
-                 lse.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(),
-                 alibi.defined() ? alibi.data_ptr() : nullptr, softmax_d.data_ptr(), seqlen_q,
-                 seqlen_k, batch_size, num_heads, num_heads_k, head_size, p_dropout, softmax_scale,
-                 window_size_left, window_size_right, softcap, deterministic,
+                 lse.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), ptr_or_null(alibi.slopes),
+                 softmax_d.data_ptr(), seqlen_q, seqlen_k, batch_size, num_heads, num_heads_k, head_size,
+                 p_dropout, softmax_scale, window_size_left, window_size_right, softcap, deterministic,
                  q.dtype() == torch::kFloat16, cur_stream(), workspace.data_ptr(), ws);
         raise_if_failed("bwd");
     } else {
         dk.zero_(); dv.zero_(); softmax_d.zero_();
     }
-    grad_writeback(dq_, dq); grad_writeback(dk_, dk); grad_writeback(dv_, dv);
-    if (head_size_og % 8 != 0) {
-        using torch::indexing::Slice; using torch::indexing::None;
-        dq = dq.index({"...", Slice(None, head_size_og)});
-        dk = dk.index({"...", Slice(None, head_size_og)});
-        dv = dv.index({"...", Slice(None, head_size_og)});
-    }
-    return {dq, dk, dv, softmax_d};
+    return {finish_grad(dq_, dq, head_size_og), finish_grad(dk_, dk, head_size_og),
+            finish_grad(dv_, dv, head_size_og), softmax_d};
 }
 
 std::vector<at::Tensor>
-mha_varlen_bwd(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k,
-               const at::Tensor& v, const at::Tensor& out, const at::Tensor& softmax_lse,
-               c10::optional<at::Tensor>& dq_, c10::optional<at::Tensor>& dk_,
-               c10::optional<at::Tensor>& dv_, const at::Tensor& cu_seqlens_q,
-               const at::Tensor& cu_seqlens_k, c10::optional<at::Tensor>& alibi_slopes_,
-               const int max_seqlen_q, const int max_seqlen_k, const float p_dropout,
-               const float softmax_scale, const bool zero_tensors, const bool is_causal,
-               int window_size_left, int window_size_right, const float softcap,
-               const bool deterministic, c10::optional<at::Generator> /*gen_*/,
-               c10::optional<at::Tensor>& rng_state) {
-    check_qkv_dtype(q, k, v);
-    if (is_causal) window_size_right = 0;
-    TORCH_CHECK(p_dropout >= 0.f && p_dropout < 1.f, "p_dropout must be in [0, 1)");
-    if (softcap > 0.f) { TORCH_CHECK(p_dropout == 0.f, "Softcapping does not support dropout for now"); }
-    dropout_rng_restore(p_dropout, rng_state);
+mha_varlen_bwd(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+               const at::Tensor& out, const at::Tensor& softmax_lse, OptTensor& dq_, OptTensor& dk_,
+               OptTensor& dv_, const at::Tensor& cu_seqlens_q, const at::Tensor& cu_seqlens_k,
+               OptTensor& alibi_slopes_, const int max_seqlen_q, const int max_seqlen_k, const float p_dropout,
+               const float softmax_scale, const bool /*zero_tensors*/, const bool is_causal,
+               int window_size_left, int window_size_right, const float softcap, const bool deterministic,
+               c10::optional<at::Generator> /*gen_*/, OptTensor& rng_state) {
+    check_bwd_args(q, k, v, p_dropout, softcap, rng_state);
     RngDisarm rng_disarm;
-    TORCH_CHECK(cu_seqlens_q.dtype() == torch::kInt32, "cu_seqlens_q must have dtype int32");
-    TORCH_CHECK(cu_seqlens_k.dtype() == torch::kInt32, "cu_seqlens_k must have dtype int32");
-    const int batch_size = cu_seqlens_q.numel() - 1;
+    const int batch_size = check_cu_seqlens(cu_seqlens_q, cu_seqlens_k);
     const int total_q = q.size(0), num_heads = q.size(1), head_size = q.size(2);
     const int total_k = k.size(0), num_heads_k = k.size(1);
     const int head_size_og = dout.size(2);
-    TORCH_CHECK(head_size % 8 == 0, "head_size should be a multiple of 8");
-    TORCH_CHECK(head_size <= 256, "FlashAttention backward only supports head dimension at most 256");
-    TORCH_CHECK(num_heads % num_heads_k == 0, "Number of heads in key/value must divide number of heads in query");
-    if (window_size_left >= max_seqlen_k) window_size_left = -1;
-    if (window_size_right >= max_seqlen_k) window_size_right = -1;
+    check_bwd_heads(batch_size, num_heads, num_heads_k, head_size, head_size_og);
+    normalize_window(is_causal, /*single_row=*/false, max_seqlen_k, /*clip_first=*/false, window_size_left,
+                     window_size_right);
     CHECK_SHAPE(softmax_lse, num_heads, total_q);
     CHECK_SHAPE(k, total_k, num_heads_k, head_size);
     CHECK_SHAPE(v, total_k, num_heads_k, head_size);
     CHECK_SHAPE(out, total_q, num_heads, head_size);
     CHECK_SHAPE(dout, total_q, num_heads, head_size_og);
-    at::Tensor dq = grad_out(dq_, q), dk = grad_out(dk_, k), dv = grad_out(dv_, v);
+    at::Tensor dq = take_grad(dq_, q), dk = take_grad(dk_, k), dv = take_grad(dv_, v);
     at::Tensor dout_padded = dense(pad_last(dout, head_size_og));
     const c10::DeviceGuard device_guard(q.device());
     auto opts = q.options();
     auto softmax_d = torch::empty({num_heads, total_q}, opts.dtype(at::kFloat));
-    int64_t alibi_bs = 0;
-    at::Tensor alibi = alibi_for_c(alibi_slopes_, batch_size, num_heads, &alibi_bs);
+    const Alibi alibi = alibi_for_c(alibi_slopes_, batch_size, num_heads);
     auto qc = dense(q), kc = dense(k), vc = dense(v), oc = dense(out);
     auto lse = softmax_lse.contiguous();
     const size_t ws = fmha_varlen_bwd_workspace_size(total_q, max_seqlen_k, batch_size, num_heads,
                                                      num_heads_k, head_size, deterministic);
     at::Tensor workspace = torch::empty({(int64_t)ws}, opts.dtype(torch::kUInt8));
-    fmha_varlen_bwd(dout_padded.data_ptr(), qc.data_ptr(), kc.data_ptr(), vc.data_ptr(),
-                    oc.data_ptr(), lse.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(),
-                    cu_seqlens_q.data_ptr(), cu_seqlens_k.data_ptr(),
-                    alibi.defined() ? alibi.data_ptr() : nullptr, (int)alibi_bs, max_seqlen_q,
+    fmha_varlen_bwd(dout_padded.data_ptr(), qc.data_ptr(), kc.data_ptr(), vc.data_ptr(), oc.data_ptr(),
+                    lse.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), cu_seqlens_q.data_ptr(),
+                    cu_seqlens_k.data_ptr(), ptr_or_null(alibi.slopes), alibi.batch_stride, max_seqlen_q,
                     max_seqlen_k, total_q, total_k, batch_size, num_heads, num_heads_k, head_size,
                     softmax_scale, window_size_left, window_size_right, softcap, deterministic,
                     q.dtype() == torch::kFloat16, cur_stream(), workspace.data_ptr(), ws,
                     softmax_d.data_ptr(), p_dropout);
     raise_if_failed("varlen_bwd");
-    (void)zero_tensors;
-    grad_writeback(dq_, dq); grad_writeback(dk_, dk); grad_writeback(dv_, dv);
-    if (head_size_og % 8 != 0) {
-        using torch::indexing::Slice; using torch::indexing::None;
-        dq = dq.index({"...", Slice(None, head_size_og)});
-        dk = dk.index({"...", Slice(None, head_size_og)});
-        dv = dv.index({"...", Slice(None, head_size_og)});
-    }
-    return {dq, dk, dv, softmax_d};
+    return {finish_grad(dq_, dq, head_size_og), finish_grad(dk_, dk, head_size_og),
+            finish_grad(dv_, dv, head_size_og), softmax_d};
 }
 
 // Paged decode over an fp8 (OCP e4m3fn) K/V cache with per-tensor dequant scales — an
 // extension the reference lacks.  kcache/vcache: float8_e4m3fn (or uint8 bytes)
-// [num_blocks, page, hk, d]; returns {out, softmax_lse}.
-static std::vector<at::Tensor>
-mha_fwd_kvcache_fp8_impl(at::Tensor& q, const at::Tensor& kcache, const at::Tensor& vcache,
+// [num_blocks, page, hk, d]; returns {out, softmax_lse}.  `fwd_kvcache_fp8`, and
+// `fwd_kvcache_fp8_sink` with a trailing sink.
+std::vector<at::Tensor>
+mha_fwd_kvcache_fp8(const OptTensor& sink_, at::Tensor& q, const at::Tensor& kcache, const at::Tensor& vcache,
                     const at::Tensor& seqlens_k, const at::Tensor& block_table, const float k_scale,
-                    const float v_scale, const float softmax_scale, bool is_causal,
-                    int window_size_left, int window_size_right, int num_splits,
-                    const c10::optional<at::Tensor>& sink_) {
+                    const float v_scale, const float softmax_scale, bool is_causal, int window_size_left,
+                    int window_size_right, int num_splits) {
     auto dt = q.dtype();
     TORCH_CHECK(dt == torch::kFloat16 || dt == torch::kBFloat16, "q must be fp16 or bf16");
     TORCH_CHECK(kcache.element_size() == 1 && vcache.element_size() == 1, "fp8 K/V cache expected");
-    CHECK_DEVICE(q); CHECK_DEVICE(kcache); CHECK_DEVICE(vcache); CHECK_DEVICE(block_table); CHECK_DEVICE(seqlens_k);
+    CHECK_DEVICE(q); CHECK_DEVICE(kcache); CHECK_DEVICE(vcache);
     CHECK_CONTIGUOUS(kcache); CHECK_CONTIGUOUS(vcache);
-    TORCH_CHECK(block_table.dtype() == torch::kInt32 && seqlens_k.dtype() == torch::kInt32,
-                "block_table / seqlens_k must be int32");
     const int batch_size = q.size(0), seqlen_q = q.size(1), num_heads = q.size(2), d = q.size(3);
     const int page = kcache.size(1), num_heads_k = kcache.size(2);
     TORCH_CHECK(kcache.size(3) == d && d % 8 == 0 && d <= 256, "head_size must be a multiple of 8 and <= 256");
-    TORCH_CHECK(num_heads % num_heads_k == 0, "Number of heads in key/value must divide number of heads in query");
-    CHECK_SHAPE(block_table, batch_size, block_table.size(1));
-    CHECK_SHAPE(seqlens_k, batch_size);
-    const int seqlen_k = block_table.size(1) * page;
-    if (seqlen_q == 1) is_causal = false;
-    if (is_causal) window_size_right = 0;
-    if (window_size_left >= seqlen_k) window_size_left = -1;
-    if (window_size_right >= seqlen_k) window_size_right = -1;
+    check_heads(batch_size, num_heads, num_heads_k, d, "forward");
+    auto bt = block_table.contiguous();      // (so any strides are taken)
+    check_block_table(bt, batch_size);
+    check_batch_int32(seqlens_k, batch_size, "seqlens_k");
+    const int seqlen_k = bt.size(1) * page;
+    normalize_window(is_causal, seqlen_q == 1, seqlen_k, /*clip_first=*/false, window_size_left, window_size_right);
     const c10::DeviceGuard device_guard(q.device());
     auto qc = dense(q);
     auto out = torch::empty_like(qc);
     auto lse = torch::empty({batch_size, num_heads, seqlen_q}, q.options().dtype(at::kFloat));
-    auto bt = block_table.contiguous();
-    if (const float* sink = sink_for_c(sink_, q, num_heads)) {
-        fmha_page_kvcache_fwd_sink(qc.data_ptr(), kcache.data_ptr(), vcache.data_ptr(), out.data_ptr(),
-                                   lse.data_ptr(), bt.data_ptr(), (int)bt.stride(0), seqlens_k.data_ptr(),
-                                   seqlen_q, seqlen_k, batch_size, num_heads, num_heads_k, d, page,
-                                   softmax_scale, window_size_left, window_size_right, 0.f, nullptr, 0,
-                                   num_splits, 1, k_scale, v_scale, nullptr, dt == torch::kFloat16,
-                                   cur_stream(), sink);
-        raise_if_failed("fwd_kvcache_fp8_sink");
-        return {out, lse};
-    }
-    fmha_page_kvcache_fwd_ex(qc.data_ptr(), kcache.data_ptr(), vcache.data_ptr(), out.data_ptr(),
-                             lse.data_ptr(), bt.data_ptr(), (int)bt.stride(0), seqlens_k.data_ptr(),
-                             seqlen_q, seqlen_k, batch_size, num_heads, num_heads_k, d, page,
-                             softmax_scale, window_size_left, window_size_right, 0.f, nullptr, 0,
-                             num_splits, 1, k_scale, v_scale, nullptr, dt == torch::kFloat16,
-                             cur_stream());
+    fmha_page_kvcache_fwd_sink(qc.data_ptr(), kcache.data_ptr(), vcache.data_ptr(), out.data_ptr(),
+                               lse.data_ptr(), bt.data_ptr(), (int)bt.stride(0), seqlens_k.data_ptr(),
+                               seqlen_q, seqlen_k, batch_size, num_heads, num_heads_k, d, page,
+                               softmax_scale, window_size_left, window_size_right, 0.f, nullptr, 0,
+                               num_splits, 1, k_scale, v_scale, nullptr, dt == torch::kFloat16,
+                               cur_stream(), sink_for_c(sink_, q, num_heads));
     raise_if_failed("fwd_kvcache_fp8");
     return {out, lse};
 }
 
-std::vector<at::Tensor>
-mha_fwd_kvcache_fp8(at::Tensor& q, const at::Tensor& kcache, const at::Tensor& vcache,
-                    const at::Tensor& seqlens_k, const at::Tensor& block_table, const float k_scale,
-                    const float v_scale, const float softmax_scale, bool is_causal,
-                    int window_size_left, int window_size_right, int num_splits) {
-    return mha_fwd_kvcache_fp8_impl(q, kcache, vcache, seqlens_k, block_table, k_scale, v_scale,
-                                    softmax_scale, is_causal, window_size_left, window_size_right,
-                                    num_splits, c10::nullopt);
-}
+namespace {
 
-// `fwd_kvcache_fp8` plus a trailing sink
-std::vector<at::Tensor>
-mha_fwd_kvcache_fp8_sink(at::Tensor& q, const at::Tensor& kcache, const at::Tensor& vcache,
-                         const at::Tensor& seqlens_k, const at::Tensor& block_table, const float k_scale,
-                         const float v_scale, const float softmax_scale, bool is_causal,
-                         int window_size_left, int window_size_right, int num_splits,
-                         const at::Tensor& sink) {
-    return mha_fwd_kvcache_fp8_impl(q, kcache, vcache, seqlens_k, block_table, k_scale, v_scale,
-                                    softmax_scale, is_causal, window_size_left, window_size_right,
-                                    num_splits, sink);
-}
-
-// fp8 e4m3fn Q/K/V forward (extension): q [b, sq, h, 128], k/v [b, sk, hk, 128] as
-// float8_e4m3fn (or uint8 bytes) with per-tensor descales; returns {out (out_dtype), lse}.
 // Device descales of the _ex ops: fp32 CUDA tensors of one element or of shape [batch, heads_k]
 // (FA3's layout), brought to one stride pair for the three of them - (0, 0) when all have one
 // element, else [batch, heads_k] contiguous (a one-element tensor expanded on the device: no
@@ -937,49 +756,89 @@ DeviceDescales device_descales(const at::Tensor& qd, const at::Tensor& kd, const
     return {out[0], out[1], out[2], per_head ? num_heads_k : 0, per_head ? 1 : 0};
 }
 
+// what the four fp8 q/k/v forwards check alike: byte-sized contiguous q, k, v of rank N on the device
+template <int N>
+void check_fp8_qkv(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, const char* what,
+                   const char* layout) {
+    TORCH_CHECK(q.element_size() == 1 && k.element_size() == 1 && v.element_size() == 1,
+                what, ": q, k and v must be float8_e4m3fn (or uint8 bytes)");
+    CHECK_DEVICE(q); CHECK_DEVICE(k); CHECK_DEVICE(v);
+    CHECK_CONTIGUOUS(q); CHECK_CONTIGUOUS(k); CHECK_CONTIGUOUS(v);
+    TORCH_CHECK(q.dim() == N && k.dim() == N && v.dim() == N, "q, k, v must be ", layout);
+}
+
+// ... and their `out`: its dtype is out_fp16's choice, not the inputs', and one the kernel cannot
+// write directly is refused
+at::Tensor take_fp8_out(const OptTensor& out_, const at::Tensor& q, bool out_fp16, std::vector<int64_t> shape) {
+    const auto odt = out_fp16 ? torch::kFloat16 : torch::kBFloat16;
+    TORCH_CHECK(!out_.has_value() || out_.value().dtype() == odt, "out has the wrong dtype");
+    return take_out(out_, q.options().dtype(odt), std::move(shape), /*strided_ok=*/false, /*refuse_indirect=*/true);
+}
+
+// fp8 e4m3fn Q/K/V forward (extension): q [b, sq, h, 128], k/v [b, sk, hk, 128] as
+// float8_e4m3fn (or uint8 bytes) with per-tensor descales; returns {out (out_dtype), lse}.
 // `launch(out, lse, window_left, window_right)` calls the C entry (by-value or device descales)
 template <typename F>
 std::vector<at::Tensor>
 fwd_fp8_impl(const char* op, const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
-             c10::optional<at::Tensor>& out_, bool is_causal, int window_size_left,
-             int window_size_right, const bool out_fp16, F&& launch) {
-    TORCH_CHECK(q.element_size() == 1 && k.element_size() == 1 && v.element_size() == 1,
-                "fp8 forward: q, k and v must be float8_e4m3fn (or uint8 bytes)");
-    CHECK_DEVICE(q); CHECK_DEVICE(k); CHECK_DEVICE(v);
-    CHECK_CONTIGUOUS(q); CHECK_CONTIGUOUS(k); CHECK_CONTIGUOUS(v);
-    TORCH_CHECK(q.dim() == 4 && k.dim() == 4 && v.dim() == 4, "q, k, v must be [b, s, h, d]");
+             OptTensor& out_, bool is_causal, int window_size_left, int window_size_right,
+             const bool out_fp16, F&& launch) {
+    check_fp8_qkv<4>(q, k, v, "fp8 forward", "[b, s, h, d]");
     const int batch_size = q.size(0), seqlen_q = q.size(1), num_heads = q.size(2), d = q.size(3);
     const int seqlen_k = k.size(1), num_heads_k = k.size(2);
     TORCH_CHECK(d == 128, "fp8 forward supports head_size 128");
     CHECK_SHAPE(k, batch_size, seqlen_k, num_heads_k, d);
     CHECK_SHAPE(v, batch_size, seqlen_k, num_heads_k, d);
-    TORCH_CHECK(num_heads % num_heads_k == 0, "Number of heads in key/value must divide number of heads in query");
-    if (seqlen_q == 1) is_causal = false;
-    if (is_causal) window_size_right = 0;
-    if (window_size_left >= seqlen_k) window_size_left = -1;
-    if (window_size_right >= seqlen_k) window_size_right = -1;
+    check_heads(batch_size, num_heads, num_heads_k, d, "forward");
+    normalize_window(is_causal, seqlen_q == 1, seqlen_k, /*clip_first=*/false, window_size_left, window_size_right);
     const c10::DeviceGuard device_guard(q.device());
-    const auto odt = out_fp16 ? torch::kFloat16 : torch::kBFloat16;
-    at::Tensor out;
-    if (out_.has_value()) {
-        out = out_.value();
-        TORCH_CHECK(out.dtype() == odt, "out has the wrong dtype");
-        CHECK_DEVICE(out); CHECK_CONTIGUOUS(out);
-        CHECK_SHAPE(out, batch_size, seqlen_q, num_heads, d);
-    } else {
-        out = torch::empty({batch_size, seqlen_q, num_heads, d}, q.options().dtype(odt));
-    }
+    at::Tensor out = take_fp8_out(out_, q, out_fp16, {batch_size, seqlen_q, num_heads, d});
     auto lse = torch::empty({batch_size, num_heads, seqlen_q}, q.options().dtype(at::kFloat));
     launch(out, lse, window_size_left, window_size_right);
     raise_if_failed(op);
     return {out, lse};
 }
 
+// fp8 e4m3fn forward over packed sequences (extension): q [total_q, h, 128], k/v
+// [total_k, hk, 128], cu_seqlens int32 [b + 1], optional seqused_k int32 [b]; returns
+// {out [total_q, h, 128] (out dtype), lse [h, total_q]}.
+// `launch(out, lse, seqused pointer, window_left, window_right)` calls the C entry
+template <typename F>
 std::vector<at::Tensor>
-mha_fwd_fp8(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
-            c10::optional<at::Tensor>& out_, const float q_scale, const float k_scale,
-            const float v_scale, const float softmax_scale, bool is_causal, int window_size_left,
-            int window_size_right, const bool out_fp16) {
+varlen_fwd_fp8_impl(const char* op, const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+                    OptTensor& out_, const at::Tensor& cu_seqlens_q, const at::Tensor& cu_seqlens_k,
+                    OptTensor& seqused_k, int max_seqlen_q, const int max_seqlen_k, bool is_causal,
+                    int window_size_left, int window_size_right, const bool out_fp16, F&& launch) {
+    check_fp8_qkv<3>(q, k, v, "fp8 varlen forward", "[total, h, d]");
+    const int batch_size = check_cu_seqlens(cu_seqlens_q, cu_seqlens_k);
+    TORCH_CHECK(cu_seqlens_q.device() == q.device() && cu_seqlens_k.device() == q.device(),
+                "cu_seqlens must be on q's device");
+    const int total_q = q.size(0), num_heads = q.size(1), d = q.size(2);
+    const int total_k = k.size(0), num_heads_k = k.size(1);
+    TORCH_CHECK(d == 128, "fp8 forward supports head_size 128");
+    CHECK_SHAPE(k, total_k, num_heads_k, d);
+    CHECK_SHAPE(v, total_k, num_heads_k, d);
+    check_heads(batch_size, num_heads, num_heads_k, d, "forward");
+    TORCH_CHECK(max_seqlen_q > 0 && max_seqlen_k > 0, "max_seqlen_q and max_seqlen_k must be positive");
+    at::Tensor seqused = batch_int32(seqused_k, batch_size, "seqused_k");
+    TORCH_CHECK(!seqused.defined() || seqused.device() == q.device(), "seqused_k must be on q's device");
+    normalize_window(is_causal, max_seqlen_q == 1, max_seqlen_k, /*clip_first=*/false, window_size_left,
+                     window_size_right);
+    const c10::DeviceGuard device_guard(q.device());
+    at::Tensor out = take_fp8_out(out_, q, out_fp16, {total_q, num_heads, d});
+    auto lse = torch::empty({num_heads, total_q}, q.options().dtype(at::kFloat));
+    if (total_q == 0) return {out, lse};
+    launch(out, lse, ptr_or_null(seqused), window_size_left, window_size_right);
+    raise_if_failed(op);
+    return {out, lse};
+}
+
+}  // namespace
+
+std::vector<at::Tensor>
+mha_fwd_fp8(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, OptTensor& out_,
+            const float q_scale, const float k_scale, const float v_scale, const float softmax_scale,
+            bool is_causal, int window_size_left, int window_size_right, const bool out_fp16) {
     return fwd_fp8_impl("fwd_fp8", q, k, v, out_, is_causal, window_size_left, window_size_right, out_fp16,
                         [&](at::Tensor& out, at::Tensor& lse, int wl, int wr) {
         fmha_fwd_fp8(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), lse.data_ptr(), q_scale,
@@ -990,10 +849,10 @@ mha_fwd_fp8(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
 
 // ... with the descales as device tensors (one element or [batch, heads_k]): no host read
 std::vector<at::Tensor>
-mha_fwd_fp8_ex(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
-               c10::optional<at::Tensor>& out_, const at::Tensor& q_descale,
-               const at::Tensor& k_descale, const at::Tensor& v_descale, const float softmax_scale,
-               bool is_causal, int window_size_left, int window_size_right, const bool out_fp16) {
+mha_fwd_fp8_ex(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, OptTensor& out_,
+               const at::Tensor& q_descale, const at::Tensor& k_descale, const at::Tensor& v_descale,
+               const float softmax_scale, bool is_causal, int window_size_left, int window_size_right,
+               const bool out_fp16) {
     TORCH_CHECK(q.dim() == 4 && k.dim() == 4, "q, k, v must be [b, s, h, d]");
     const DeviceDescales ds = device_descales(q_descale, k_descale, v_descale, q, q.size(0), k.size(2));
     return fwd_fp8_impl("fwd_fp8_ex", q, k, v, out_, is_causal, window_size_left, window_size_right, out_fp16,
@@ -1005,76 +864,12 @@ mha_fwd_fp8_ex(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
     });
 }
 
-// fp8 e4m3fn forward over packed sequences (extension): q [total_q, h, 128], k/v
-// [total_k, hk, 128], cu_seqlens int32 [b + 1], optional seqused_k int32 [b]; returns
-// {out [total_q, h, 128] (out dtype), lse [h, total_q]}.
-// `launch(out, lse, seqused pointer, window_left, window_right)` calls the C entry
-template <typename F>
 std::vector<at::Tensor>
-varlen_fwd_fp8_impl(const char* op, const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
-                    c10::optional<at::Tensor>& out_, const at::Tensor& cu_seqlens_q,
-                    const at::Tensor& cu_seqlens_k, c10::optional<at::Tensor>& seqused_k,
-                    int max_seqlen_q, const int max_seqlen_k, bool is_causal, int window_size_left,
-                    int window_size_right, const bool out_fp16, F&& launch) {
-    TORCH_CHECK(q.element_size() == 1 && k.element_size() == 1 && v.element_size() == 1,
-                "fp8 varlen forward: q, k and v must be float8_e4m3fn (or uint8 bytes)");
-    CHECK_DEVICE(q); CHECK_DEVICE(k); CHECK_DEVICE(v);
-    CHECK_CONTIGUOUS(q); CHECK_CONTIGUOUS(k); CHECK_CONTIGUOUS(v);
-    TORCH_CHECK(q.dim() == 3 && k.dim() == 3 && v.dim() == 3, "q, k, v must be [total, h, d]");
-    TORCH_CHECK(cu_seqlens_q.dtype() == torch::kInt32, "cu_seqlens_q must have dtype int32");
-    TORCH_CHECK(cu_seqlens_k.dtype() == torch::kInt32, "cu_seqlens_k must have dtype int32");
-    CHECK_DEVICE(cu_seqlens_q); CHECK_DEVICE(cu_seqlens_k);
-    CHECK_CONTIGUOUS(cu_seqlens_q); CHECK_CONTIGUOUS(cu_seqlens_k);
-    TORCH_CHECK(cu_seqlens_q.device() == q.device() && cu_seqlens_k.device() == q.device(),
-                "cu_seqlens must be on q's device");
-    const int total_q = q.size(0), num_heads = q.size(1), d = q.size(2);
-    const int total_k = k.size(0), num_heads_k = k.size(1);
-    const int batch_size = cu_seqlens_q.numel() - 1;
-    TORCH_CHECK(batch_size > 0, "batch size must be positive");
-    TORCH_CHECK(d == 128, "fp8 forward supports head_size 128");
-    CHECK_SHAPE(k, total_k, num_heads_k, d);
-    CHECK_SHAPE(v, total_k, num_heads_k, d);
-    CHECK_SHAPE(cu_seqlens_q, batch_size + 1);
-    CHECK_SHAPE(cu_seqlens_k, batch_size + 1);
-    TORCH_CHECK(num_heads % num_heads_k == 0, "Number of heads in key/value must divide number of heads in query");
-    TORCH_CHECK(max_seqlen_q > 0 && max_seqlen_k > 0, "max_seqlen_q and max_seqlen_k must be positive");
-    at::Tensor seqused;
-    if (seqused_k.has_value()) {
-        seqused = seqused_k.value();
-        TORCH_CHECK(seqused.dtype() == torch::kInt32, "seqused_k must have dtype int32");
-        TORCH_CHECK(seqused.is_cuda() && seqused.device() == q.device(), "seqused_k must be on q's device");
-        TORCH_CHECK(seqused.is_contiguous(), "seqused_k must be contiguous");
-        CHECK_SHAPE(seqused, batch_size);
-    }
-    if (max_seqlen_q == 1) is_causal = false;
-    if (is_causal) window_size_right = 0;
-    if (window_size_left >= max_seqlen_k) window_size_left = -1;
-    if (window_size_right >= max_seqlen_k) window_size_right = -1;
-    const c10::DeviceGuard device_guard(q.device());
-    const auto odt = out_fp16 ? torch::kFloat16 : torch::kBFloat16;
-    at::Tensor out;
-    if (out_.has_value()) {
-        out = out_.value();
-        TORCH_CHECK(out.dtype() == odt, "out has the wrong dtype");
-        CHECK_DEVICE(out); CHECK_CONTIGUOUS(out);
-        CHECK_SHAPE(out, total_q, num_heads, d);
-    } else {
-        out = torch::empty({total_q, num_heads, d}, q.options().dtype(odt));
-    }
-    auto lse = torch::empty({num_heads, total_q}, q.options().dtype(at::kFloat));
-    if (total_q == 0) return {out, lse};
-    launch(out, lse, seqused.defined() ? seqused.data_ptr() : nullptr, window_size_left, window_size_right);
-    raise_if_failed(op);
-    return {out, lse};
-}
-
-std::vector<at::Tensor>
-mha_varlen_fwd_fp8(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
-                   c10::optional<at::Tensor>& out_, const at::Tensor& cu_seqlens_q,
-                   const at::Tensor& cu_seqlens_k, c10::optional<at::Tensor>& seqused_k,
-                   int max_seqlen_q, const int max_seqlen_k, const float q_scale,
-                   const float k_scale, const float v_scale, const float softmax_scale,
-                   bool is_causal, int window_size_left, int window_size_right, const bool out_fp16) {
+mha_varlen_fwd_fp8(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, OptTensor& out_,
+                   const at::Tensor& cu_seqlens_q, const at::Tensor& cu_seqlens_k, OptTensor& seqused_k,
+                   int max_seqlen_q, const int max_seqlen_k, const float q_scale, const float k_scale,
+                   const float v_scale, const float softmax_scale, bool is_causal, int window_size_left,
+                   int window_size_right, const bool out_fp16) {
     return varlen_fwd_fp8_impl("varlen_fwd_fp8", q, k, v, out_, cu_seqlens_q, cu_seqlens_k, seqused_k,
                                max_seqlen_q, max_seqlen_k, is_causal, window_size_left,
                                window_size_right, out_fp16,
@@ -1088,9 +883,8 @@ mha_varlen_fwd_fp8(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v
 
 // ... with the descales as device tensors (one element or [sequences, heads_k]): no host read
 std::vector<at::Tensor>
-mha_varlen_fwd_fp8_ex(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
-                      c10::optional<at::Tensor>& out_, const at::Tensor& cu_seqlens_q,
-                      const at::Tensor& cu_seqlens_k, c10::optional<at::Tensor>& seqused_k,
+mha_varlen_fwd_fp8_ex(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, OptTensor& out_,
+                      const at::Tensor& cu_seqlens_q, const at::Tensor& cu_seqlens_k, OptTensor& seqused_k,
                       int max_seqlen_q, const int max_seqlen_k, const at::Tensor& q_descale,
                       const at::Tensor& k_descale, const at::Tensor& v_descale, const float softmax_scale,
                       bool is_causal, int window_size_left, int window_size_right, const bool out_fp16) {
@@ -1116,8 +910,7 @@ mha_varlen_fwd_fp8_ex(const at::Tensor& q, const at::Tensor& k, const at::Tensor
 // 1 one per (batch or sequence, group of `group` heads).  Returns {x8 (float8_e4m3fn,
 // contiguous), descale fp32 [1] or [b, h / group]}.
 std::vector<at::Tensor>
-mha_quantize_fp8(const at::Tensor& x, int granularity, int group,
-                 c10::optional<at::Tensor>& cu_seqlens_, int max_seqlen) {
+mha_quantize_fp8(const at::Tensor& x, int granularity, int group, OptTensor& cu_seqlens_, int max_seqlen) {
     auto dt = x.dtype();
     TORCH_CHECK(dt == torch::kFloat16 || dt == torch::kBFloat16, "quantize_fp8: x must be fp16 or bf16");
     CHECK_DEVICE(x);
@@ -1131,11 +924,8 @@ mha_quantize_fp8(const at::Tensor& x, int granularity, int group,
     int64_t st[3];
     if (packed) {
         cu = cu_seqlens_.value();
-        TORCH_CHECK(cu.dtype() == torch::kInt32, "cu_seqlens must have dtype int32");
-        TORCH_CHECK(cu.is_cuda() && cu.device() == x.device(), "cu_seqlens must be on x's device");
-        CHECK_CONTIGUOUS(cu);
-        TORCH_CHECK(cu.dim() == 1 && cu.numel() >= 2, "cu_seqlens must be [batch + 1]");
-        batch_size = cu.numel() - 1;
+        batch_size = check_cu_seqlens(cu, "cu_seqlens");
+        TORCH_CHECK(cu.device() == x.device(), "cu_seqlens must be on x's device");
         seqlen = max_seqlen > 0 ? max_seqlen : (int)xs.size(0);
         num_heads = xs.size(1); d = xs.size(2);
         st[0] = 0; st[1] = xs.stride(0); st[2] = xs.stride(1);
@@ -1148,9 +938,8 @@ mha_quantize_fp8(const at::Tensor& x, int granularity, int group,
     auto descale = granularity ? torch::empty({batch_size, num_heads / group}, x.options().dtype(at::kFloat))
                                : torch::empty({1}, x.options().dtype(at::kFloat));
     if (xs.numel() == 0) { descale.fill_(1.f); return {x8, descale}; }
-    fmha_quantize_fp8(xs.data_ptr(), x8.data_ptr(), descale.data_ptr<float>(),
-                      cu.defined() ? cu.data_ptr() : nullptr, batch_size, seqlen, num_heads, group, d,
-                      st, granularity, dt == torch::kFloat16, cur_stream());
+    fmha_quantize_fp8(xs.data_ptr(), x8.data_ptr(), descale.data_ptr<float>(), ptr_or_null(cu), batch_size,
+                      seqlen, num_heads, group, d, st, granularity, dt == torch::kFloat16, cur_stream());
     raise_if_failed("quantize_fp8");
     return {x8, descale};
 }
@@ -1159,86 +948,68 @@ mha_quantize_fp8(const at::Tensor& x, int granularity, int group,
 // (fmha_kvcache_append_fp8): the write step of fwd_kvcache for an fp8 cache.  Returns
 // {seqlens_out, q_out (rotary; else q itself)}.
 std::vector<at::Tensor>
-mha_kvcache_append_fp8(const at::Tensor& q, at::Tensor& kcache, at::Tensor& vcache,
-                       const at::Tensor& kn, const at::Tensor& vn, const at::Tensor& seqlens_k,
-                       const at::Tensor& block_table, c10::optional<at::Tensor>& rotary_cos_,
-                       c10::optional<at::Tensor>& rotary_sin_, const float k_scale,
+mha_kvcache_append_fp8(const at::Tensor& q, at::Tensor& kcache, at::Tensor& vcache, const at::Tensor& kn,
+                       const at::Tensor& vn, const at::Tensor& seqlens_k, const at::Tensor& block_table,
+                       OptTensor& rotary_cos_, OptTensor& rotary_sin_, const float k_scale,
                        const float v_scale, bool is_rotary_interleaved, bool q_rotary_per_token) {
     auto dt = q.dtype();
     TORCH_CHECK(dt == torch::kFloat16 || dt == torch::kBFloat16, "q must be fp16 or bf16");
     TORCH_CHECK(kn.dtype() == dt && vn.dtype() == dt, "new key / value must have the same dtype as query");
     TORCH_CHECK(kcache.element_size() == 1 && vcache.element_size() == 1, "fp8 K/V cache expected");
     CHECK_DEVICE(q); CHECK_DEVICE(kcache); CHECK_DEVICE(vcache); CHECK_DEVICE(kn); CHECK_DEVICE(vn);
-    CHECK_DEVICE(block_table); CHECK_DEVICE(seqlens_k);
-    CHECK_CONTIGUOUS(kcache); CHECK_CONTIGUOUS(vcache); CHECK_CONTIGUOUS(seqlens_k);
-    TORCH_CHECK(block_table.dtype() == torch::kInt32 && seqlens_k.dtype() == torch::kInt32,
-                "block_table / seqlens_k must be int32");
+    CHECK_CONTIGUOUS(kcache); CHECK_CONTIGUOUS(vcache);
     TORCH_CHECK(q.dim() == 4 && kn.dim() == 4 && kcache.dim() == 4 && block_table.dim() == 2,
                 "q, k, v, caches must be 4-D and block_table 2-D");
     const int batch_size = q.size(0), seqlen_q = q.size(1), num_heads = q.size(2), d = q.size(3);
     const int page = kcache.size(1), num_heads_k = kcache.size(2), seqlen_new = kn.size(1);
     TORCH_CHECK(kcache.size(3) == d && d % 8 == 0 && d <= 256, "head_size must be a multiple of 8 and <= 256");
-    TORCH_CHECK(num_heads % num_heads_k == 0, "Number of heads in key/value must divide number of heads in query");
+    check_heads(batch_size, num_heads, num_heads_k, d, "forward");
     TORCH_CHECK(vcache.sizes() == kcache.sizes(), "k_cache and v_cache must have the same shape");
     CHECK_SHAPE(kn, batch_size, seqlen_new, num_heads_k, d);
     CHECK_SHAPE(vn, batch_size, seqlen_new, num_heads_k, d);
-    CHECK_SHAPE(block_table, batch_size, block_table.size(1));
-    CHECK_SHAPE(seqlens_k, batch_size);
+    auto bt = block_table.contiguous();      // (so any strides are taken)
+    check_block_table(bt, batch_size);
+    check_batch_int32(seqlens_k, batch_size, "seqlens_k");
     TORCH_CHECK(k_scale > 0.f && v_scale > 0.f, "fp8 cache descales must be positive");
     const c10::DeviceGuard device_guard(q.device());
     auto qc = dense(q);
     auto knc = dense(kn), vnc = dense(vn);
-    auto bt = block_table.contiguous();
-    int rotary_dim = 0;
-    at::Tensor cos, sin, q_rot;
-    if (rotary_cos_.has_value()) {
-        TORCH_CHECK(rotary_sin_.has_value(), "If rotary cos is provided, rotary sin must also be provided");
-        cos = rotary_cos_.value();
-        sin = rotary_sin_.value();
-        CHECK_DEVICE(cos); CHECK_DEVICE(sin); CHECK_CONTIGUOUS(cos); CHECK_CONTIGUOUS(sin);
-        TORCH_CHECK(cos.dim() == 2, "rotary_cos must be [seqlen_ro, rotary_dim / 2]");
-        rotary_dim = cos.size(1) * 2;
-        TORCH_CHECK(rotary_dim <= d, "rotary_dim must be <= headdim");
-        TORCH_CHECK(rotary_dim % 16 == 0, "Only rotary dimensions divisible by 16 are currently supported");
-        TORCH_CHECK(cos.size(0) >= (int64_t)bt.size(1) * page, "cos/sin seqlen must be at least the seqlen of KV cache");
-        CHECK_SHAPE(sin, cos.size(0), rotary_dim / 2);
-        TORCH_CHECK(cos.scalar_type() == q.scalar_type() && sin.scalar_type() == q.scalar_type(),
-                    "rotary_cos/sin must have the same dtype as query");
-        q_rot = torch::empty_like(qc);
-    }
+    TORCH_CHECK(!rotary_cos_.has_value() || rotary_cos_.value().dim() == 2,
+                "rotary_cos must be [seqlen_ro, rotary_dim / 2]");
+    const Rotary rotary = check_rotary(rotary_cos_, rotary_sin_, q, d, (int64_t)bt.size(1) * page);
+    at::Tensor q_rot = rotary.cos.defined() ? torch::empty_like(qc) : at::Tensor();
     auto seqlens_new = torch::empty_like(seqlens_k);
-    fmha_kvcache_append_fp8(qc.data_ptr(), q_rot.defined() ? q_rot.data_ptr() : nullptr,
-                            kcache.data_ptr(), vcache.data_ptr(), knc.data_ptr(), vnc.data_ptr(),
-                            seqlen_new, bt.data_ptr(), (int)bt.stride(0), page, seqlens_k.data_ptr(),
-                            seqlens_new.data_ptr(), cos.defined() ? cos.data_ptr() : nullptr,
-                            sin.defined() ? sin.data_ptr() : nullptr, rotary_dim, is_rotary_interleaved,
-                            q_rotary_per_token, batch_size, seqlen_q, num_heads, num_heads_k, d,
-                            dt == torch::kFloat16, cur_stream(), k_scale, v_scale);
+    fmha_kvcache_append_fp8(qc.data_ptr(), ptr_or_null(q_rot), kcache.data_ptr(), vcache.data_ptr(),
+                            knc.data_ptr(), vnc.data_ptr(), seqlen_new, bt.data_ptr(), (int)bt.stride(0), page,
+                            seqlens_k.data_ptr(), seqlens_new.data_ptr(), ptr_or_null(rotary.cos),
+                            ptr_or_null(rotary.sin), rotary.dim, is_rotary_interleaved, q_rotary_per_token,
+                            batch_size, seqlen_q, num_heads, num_heads_k, d, dt == torch::kFloat16,
+                            cur_stream(), k_scale, v_scale);
     raise_if_failed("kvcache_append_fp8");
     return {seqlens_new, q_rot.defined() ? q_rot : qc};
 }
 
 PYBIND11_MODULE(paged_attn, m) {
     m.doc() = "FlashAttention for MI355X (gfx950): hand-written HIP kernels behind the paged_attn C ABI";
-    m.def("fwd", &mha_fwd, "Forward pass");
-    m.def("varlen_fwd", &mha_varlen_fwd, "Forward pass (variable length)");
+    m.def("fwd", without_sink(&mha_fwd), "Forward pass");
+    m.def("varlen_fwd", without_sink(&mha_varlen_fwd), "Forward pass (variable length)");
     // the reference's positional signature (export.cpp:1757) plus an optional trailing
     // cache_leftpad
-    m.def("fwd_kvcache", &mha_fwd_kvcache, "Forward pass, with KV-cache", py::arg("q"),
+    m.def("fwd_kvcache", without_sink(&mha_fwd_kvcache), "Forward pass, with KV-cache", py::arg("q"),
           py::arg("kcache"), py::arg("vcache"), py::arg("k"), py::arg("v"), py::arg("seqlens_k"),
           py::arg("rotary_cos"), py::arg("rotary_sin"), py::arg("cache_batch_idx"),
           py::arg("block_table"), py::arg("alibi_slopes"), py::arg("out"),
           py::arg("softmax_scale"), py::arg("is_causal"), py::arg("window_size_left"),
           py::arg("window_size_right"), py::arg("softcap"), py::arg("is_rotary_interleaved"),
           py::arg("num_splits"), py::arg("cache_leftpad") = py::none());
-    m.def("fwd_sink", &mha_fwd_sink, "Forward pass with a per-head attention sink");
-    m.def("varlen_fwd_sink", &mha_varlen_fwd_sink, "Forward pass (variable length) with an attention sink");
-    m.def("fwd_kvcache_sink", &mha_fwd_kvcache_sink, "Forward pass with KV-cache and an attention sink");
-    m.def("fwd_kvcache_fp8_sink", &mha_fwd_kvcache_fp8_sink, "Paged decode over an fp8 K/V cache with an attention sink");
+    m.def("fwd_sink", with_sink(&mha_fwd), "Forward pass with a per-head attention sink");
+    m.def("varlen_fwd_sink", with_sink(&mha_varlen_fwd), "Forward pass (variable length) with an attention sink");
+    m.def("fwd_kvcache_sink", with_sink(&mha_fwd_kvcache), "Forward pass with KV-cache and an attention sink");
+    m.def("fwd_kvcache_fp8_sink", with_sink(&mha_fwd_kvcache_fp8), "Paged decode over an fp8 K/V cache with an attention sink");
     m.def("sink_bwd", &mha_sink_bwd, "Gradient of the attention sink from softmax_lse and softmax_d");
     m.def("bwd", &mha_bwd, "Backward pass");
     m.def("varlen_bwd", &mha_varlen_bwd, "Backward pass (variable length)");
-    m.def("fwd_kvcache_fp8", &mha_fwd_kvcache_fp8, "Paged decode over an fp8 e4m3fn K/V cache");
+    m.def("fwd_kvcache_fp8", without_sink(&mha_fwd_kvcache_fp8), "Paged decode over an fp8 e4m3fn K/V cache");
     m.def("fwd_fp8", &mha_fwd_fp8, "Forward pass over fp8 e4m3fn q/k/v (fp8 MFMA)");
     m.def("varlen_fwd_fp8", &mha_varlen_fwd_fp8, "Forward pass over packed fp8 e4m3fn q/k/v (variable length)");
     m.def("quantize_fp8", &mha_quantize_fp8, "bf16 / fp16 -> fp8 e4m3fn with its descale(s)", py::arg("x"),

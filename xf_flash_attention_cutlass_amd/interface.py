@@ -27,36 +27,6 @@ def _sink_f32(sink, q):
     return sink.detach().to(device=q.device, dtype=torch.float32).contiguous()
 
 
-class _FlashAttnSinkFunc(torch.autograd.Function):
-    """_FlashAttnFunc with a per-head sink logit: `fwd_sink`, the unchanged `bwd` (given the sink
-    forward's out and lse it is already the sink softmax's backward) and `sink_bwd` for dsink."""
-
-    @staticmethod
-    def forward(ctx, q, k, v, sink, softmax_scale, causal, window_size, softcap, deterministic):
-        q, k, v = (_maybe_contiguous(x) for x in (q, k, v))
-        s32 = _sink_f32(sink, q)
-        out, q_p, k_p, v_p, out_p, lse, _, rng = paged_attn.fwd_sink(
-            q, k, v, None, None, 0.0, softmax_scale, causal, window_size[0], window_size[1],
-            softcap, False, None, s32)
-        ctx.save_for_backward(q_p, k_p, v_p, out_p, lse, rng, s32)
-        ctx.args = (softmax_scale, causal, window_size, softcap, deterministic, q.shape[-1],
-                    sink.dtype)
-        return out, lse
-
-    @staticmethod
-    def backward(ctx, dout, *_):
-        q, k, v, out, lse, rng, s32 = ctx.saved_tensors
-        scale, causal, window, softcap, deterministic, d_og, sink_dtype = ctx.args
-        dq, dk, dv, softmax_d = paged_attn.bwd(_maybe_contiguous(dout), q, k, v, out, lse, None,
-                                               None, None, None, 0.0, scale, causal, window[0],
-                                               window[1], softcap, deterministic, None, rng)
-        dsink = None
-        if ctx.needs_input_grad[3]:
-            dsink = paged_attn.sink_bwd(lse, softmax_d, s32, False).to(sink_dtype)
-        dq, dk, dv = dq[..., :d_og], dk[..., :d_og], dv[..., :d_og]
-        return dq, dk, dv, dsink, None, None, None, None, None
-
-
 def _check_sink_args(q, dropout_p, alibi_slopes):
     if q.dtype == torch.float8_e4m3fn:
         raise NotImplementedError("fp8 q/k/v: an attention sink is not supported")
@@ -66,28 +36,43 @@ def _check_sink_args(q, dropout_p, alibi_slopes):
         raise NotImplementedError("an attention sink does not support dropout")
 
 
+def _sink_grad(ctx, lse, softmax_d, s32, varlen):
+    """dsink in the sink's dtype when the sink wants a gradient (`sink_bwd`), else None"""
+    if s32 is None or not ctx.needs_input_grad[3]:
+        return None
+    return paged_attn.sink_bwd(lse, softmax_d, s32, varlen).to(ctx.sink_dtype)
+
+
 class _FlashAttnFunc(torch.autograd.Function):
+    """sink: a per-head logit tensor or None.  With one, `fwd_sink`, the unchanged `bwd` (given the
+    sink forward's out and lse it is already the sink softmax's backward) and `sink_bwd` for dsink."""
+
     @staticmethod
-    def forward(ctx, q, k, v, dropout_p, softmax_scale, causal, window_size, softcap,
+    def forward(ctx, q, k, v, sink, dropout_p, softmax_scale, causal, window_size, softcap,
                 alibi_slopes, deterministic, return_softmax):
         q, k, v = (_maybe_contiguous(x) for x in (q, k, v))
-        out, q_p, k_p, v_p, out_p, lse, s_dmask, rng = paged_attn.fwd(
-            q, k, v, None, alibi_slopes, dropout_p, softmax_scale, causal, window_size[0],
-            window_size[1], softcap, return_softmax and dropout_p > 0, None)
-        ctx.save_for_backward(q_p, k_p, v_p, out_p, lse, rng)
+        args = (q, k, v, None, alibi_slopes, dropout_p, softmax_scale, causal, window_size[0],
+                window_size[1], softcap, return_softmax and dropout_p > 0, None)
+        s32 = None if sink is None else _sink_f32(sink, q)
+        out, q_p, k_p, v_p, out_p, lse, s_dmask, rng = (
+            paged_attn.fwd(*args) if sink is None else paged_attn.fwd_sink(*args, s32))
+        ctx.save_for_backward(q_p, k_p, v_p, out_p, lse, rng, *(() if sink is None else (s32,)))
         ctx.args = (dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes,
                     deterministic, q.shape[-1])
+        ctx.sink_dtype = None if sink is None else sink.dtype
         return out, lse, s_dmask
 
     @staticmethod
     def backward(ctx, dout, *_):
-        q, k, v, out, lse, rng = ctx.saved_tensors
+        q, k, v, out, lse, rng, *s32 = ctx.saved_tensors
         dropout_p, scale, causal, window, softcap, alibi, deterministic, d_og = ctx.args
-        dq, dk, dv, _ = paged_attn.bwd(_maybe_contiguous(dout), q, k, v, out, lse, None, None,
-                                       None, alibi, dropout_p, scale, causal, window[0],
-                                       window[1], softcap, deterministic, None, rng)
+        dq, dk, dv, softmax_d = paged_attn.bwd(_maybe_contiguous(dout), q, k, v, out, lse, None,
+                                               None, None, alibi, dropout_p, scale, causal,
+                                               window[0], window[1], softcap, deterministic, None,
+                                               rng)
+        dsink = _sink_grad(ctx, lse, softmax_d, s32[0] if s32 else None, False)
         dq, dk, dv = dq[..., :d_og], dk[..., :d_og], dv[..., :d_og]
-        return dq, dk, dv, None, None, None, None, None, None, None, None
+        return (dq, dk, dv, dsink) + (None,) * 8
 
 
 def flash_attn_func(q, k, v, dropout_p=0.0, causal=False, window_size=(-1, -1), softcap=0.0,
@@ -107,10 +92,6 @@ def flash_attn_func(q, k, v, dropout_p=0.0, causal=False, window_size=(-1, -1), 
         softmax_scale = q.shape[-1] ** (-0.5)
     if sink is not None:
         _check_sink_args(q, dropout_p, alibi_slopes)
-        out, lse = _FlashAttnSinkFunc.apply(q, k, v, sink, softmax_scale, causal,
-                                            tuple(int(w) for w in window_size), softcap,
-                                            deterministic)
-        return out if not return_attn_probs else (out, lse, None)
     if q.dtype == torch.float8_e4m3fn:
         # the fp8 forward has no dropout / softcap / ALiBi: refuse instead of dropping them
         if dropout_p != 0.0 or softcap != 0.0 or alibi_slopes is not None:
@@ -120,7 +101,7 @@ def flash_attn_func(q, k, v, dropout_p=0.0, causal=False, window_size=(-1, -1), 
         out, lse = flash_attn_fp8_func(q, k, v, q_descale, k_descale, v_descale, softmax_scale,
                                        causal, window_size, out_dtype, return_lse=True)
         return out if not return_attn_probs else (out, lse, None)
-    out, lse, s_dmask = _FlashAttnFunc.apply(q, k, v, dropout_p, softmax_scale, causal,
+    out, lse, s_dmask = _FlashAttnFunc.apply(q, k, v, sink, dropout_p, softmax_scale, causal,
                                              tuple(int(w) for w in window_size), softcap,
                                              alibi_slopes, deterministic, return_attn_probs)
     return out if not return_attn_probs else (out, lse, s_dmask)
@@ -144,12 +125,6 @@ def quantize_fp8(x, granularity="tensor", group=1, cu_seqlens=None, *, max_seqle
     x8, descale = paged_attn.quantize_fp8(x, _GRANULARITY[granularity], int(group), cu_seqlens,
                                           0 if max_seqlen is None else int(max_seqlen))
     return x8, descale
-
-
-def _device_descales(*ds):
-    """True when any descale is a CUDA tensor: then all three go to the _ex entries as device
-    tensors (one element or [batch, heads_k]) and nothing is read on the host."""
-    return any(isinstance(x, torch.Tensor) and x.is_cuda for x in ds)
 
 
 def _as_device_descale(x, device):
@@ -176,6 +151,33 @@ def _quantize_qkv(q, k, v, quantize, descales, cu_q=None, cu_k=None, max_q=None,
     return q8, k8, v8, qd, kd, vd
 
 
+def _fp8_forward(op, q, k, v, packed, descales, softmax_scale, causal, window_size, out_dtype,
+                 quantize):
+    """What the two fp8 functions share: the refusals, the default scale, quantize= and the
+    descale dispatch.  `op`: "fwd_fp8" / "varlen_fwd_fp8"; `packed`: () or (cu_seqlens_q,
+    cu_seqlens_k, seqused_k, max_seqlen_q, max_seqlen_k), the op's arguments between `out` and
+    the descales.  When any descale is a CUDA tensor all three go to the op's _ex twin as device
+    tensors (one element or [batch, heads_k]) and nothing is read on the host; otherwise they are
+    passed by value.  Returns (out, lse)."""
+    if q.requires_grad or k.requires_grad or v.requires_grad:
+        raise NotImplementedError("the fp8 forward has no backward")
+    if out_dtype not in (torch.bfloat16, torch.float16):
+        raise ValueError("out_dtype must be bfloat16 or float16")
+    if softmax_scale is None:
+        softmax_scale = q.shape[-1] ** (-0.5)
+    if quantize is not None:
+        cu_q, cu_k, _, max_q, max_k = packed or (None,) * 5
+        q, k, v, *descales = _quantize_qkv(q, k, v, quantize, descales, cu_q, cu_k, max_q, max_k)
+    q, k, v = (_maybe_contiguous(x) for x in (q, k, v))
+    if any(isinstance(x, torch.Tensor) and x.is_cuda for x in descales):
+        op, descales = op + "_ex", [_as_device_descale(x, q.device) for x in descales]
+    else:
+        descales = [1.0 if x is None else float(x) for x in descales]
+    return getattr(paged_attn, op)(q, k, v, None, *packed, *descales, softmax_scale, causal,
+                                   int(window_size[0]), int(window_size[1]),
+                                   out_dtype == torch.float16)
+
+
 def flash_attn_fp8_func(q, k, v, q_descale=None, k_descale=None, v_descale=None,
                         softmax_scale=None, causal=False, window_size=(-1, -1),
                         out_dtype=torch.bfloat16, return_lse=False, *, quantize=None):
@@ -186,28 +188,8 @@ def flash_attn_fp8_func(q, k, v, q_descale=None, k_descale=None, v_descale=None,
     element or of shape [b, hk] (FA3's layout; q's per kv head) are read by the kernel, with no
     host sync.  quantize="tensor" | "head": q, k, v are bf16 / fp16 and are quantised first
     (`quantize_fp8`, three calls), all on the device."""
-    if q.requires_grad or k.requires_grad or v.requires_grad:
-        raise NotImplementedError("the fp8 forward has no backward")
-    if out_dtype not in (torch.bfloat16, torch.float16):
-        raise ValueError("out_dtype must be bfloat16 or float16")
-    if softmax_scale is None:
-        softmax_scale = q.shape[-1] ** (-0.5)
-    if quantize is not None:
-        q, k, v, q_descale, k_descale, v_descale = _quantize_qkv(
-            q, k, v, quantize, (q_descale, k_descale, v_descale))
-
-    def _f(x):
-        return 1.0 if x is None else float(x)
-    q, k, v = (_maybe_contiguous(x) for x in (q, k, v))
-    if _device_descales(q_descale, k_descale, v_descale):
-        qd, kd, vd = (_as_device_descale(x, q.device) for x in (q_descale, k_descale, v_descale))
-        out, lse = paged_attn.fwd_fp8_ex(q, k, v, None, qd, kd, vd, softmax_scale, causal,
-                                         int(window_size[0]), int(window_size[1]),
-                                         out_dtype == torch.float16)
-        return (out, lse) if return_lse else out
-    out, lse = paged_attn.fwd_fp8(q, k, v, None, _f(q_descale), _f(k_descale), _f(v_descale),
-                                  softmax_scale, causal, int(window_size[0]), int(window_size[1]),
-                                  out_dtype == torch.float16)
+    out, lse = _fp8_forward("fwd_fp8", q, k, v, (), (q_descale, k_descale, v_descale),
+                            softmax_scale, causal, window_size, out_dtype, quantize)
     return (out, lse) if return_lse else out
 
 
@@ -221,66 +203,39 @@ def flash_attn_kvpacked_func(q, kv, dropout_p=0.0, softmax_scale=None, causal=Fa
 
 
 class _FlashAttnVarlenFunc(torch.autograd.Function):
+    """sink: as _FlashAttnFunc (`varlen_fwd_sink`, the unchanged `varlen_bwd`, `sink_bwd`)."""
+
     @staticmethod
-    def forward(ctx, q, k, v, cu_q, cu_k, max_q, max_k, dropout_p, softmax_scale, causal,
+    def forward(ctx, q, k, v, sink, cu_q, cu_k, max_q, max_k, dropout_p, softmax_scale, causal,
                 window_size, softcap, alibi_slopes, deterministic, return_softmax, block_table):
         q, k, v = (_maybe_contiguous(x) for x in (q, k, v))
-        out, q_p, k_p, v_p, out_p, lse, s_dmask, rng = paged_attn.varlen_fwd(
-            q, k, v, None, cu_q, cu_k, None, block_table, alibi_slopes, max_q, max_k, dropout_p,
-            softmax_scale, False, causal, window_size[0], window_size[1], softcap,
-            return_softmax and dropout_p > 0, None)
-        ctx.save_for_backward(q_p, k_p, v_p, out_p, lse, cu_q, cu_k, rng)
+        args = (q, k, v, None, cu_q, cu_k, None, block_table, alibi_slopes, max_q, max_k, dropout_p,
+                softmax_scale, False, causal, window_size[0], window_size[1], softcap,
+                return_softmax and dropout_p > 0, None)
+        s32 = None if sink is None else _sink_f32(sink, q)
+        out, q_p, k_p, v_p, out_p, lse, s_dmask, rng = (
+            paged_attn.varlen_fwd(*args) if sink is None else paged_attn.varlen_fwd_sink(*args, s32))
+        ctx.save_for_backward(q_p, k_p, v_p, out_p, lse, cu_q, cu_k, rng,
+                              *(() if sink is None else (s32,)))
         ctx.args = (max_q, max_k, dropout_p, softmax_scale, causal, window_size, softcap,
                     alibi_slopes, deterministic, q.shape[-1], block_table is not None)
+        ctx.sink_dtype = None if sink is None else sink.dtype
         return out, lse, s_dmask
 
     @staticmethod
     def backward(ctx, dout, *_):
-        q, k, v, out, lse, cu_q, cu_k, rng = ctx.saved_tensors
+        q, k, v, out, lse, cu_q, cu_k, rng, *s32 = ctx.saved_tensors
         (max_q, max_k, dropout_p, scale, causal, window, softcap, alibi, deterministic, d_og,
          paged) = ctx.args
         if paged:
             raise RuntimeError("backward through a paged K/V cache is not supported")
-        dq, dk, dv, _ = paged_attn.varlen_bwd(_maybe_contiguous(dout), q, k, v, out, lse, None,
-                                              None, None, cu_q, cu_k, alibi, max_q, max_k,
-                                              dropout_p, scale, False, causal, window[0],
-                                              window[1], softcap, deterministic, None, rng)
-        dq, dk, dv = dq[..., :d_og], dk[..., :d_og], dv[..., :d_og]
-        return (dq, dk, dv) + (None,) * 13
-
-
-class _FlashAttnVarlenSinkFunc(torch.autograd.Function):
-    """_FlashAttnVarlenFunc with a per-head sink logit (as _FlashAttnSinkFunc)."""
-
-    @staticmethod
-    def forward(ctx, q, k, v, sink, cu_q, cu_k, max_q, max_k, softmax_scale, causal, window_size,
-                softcap, deterministic, block_table):
-        q, k, v = (_maybe_contiguous(x) for x in (q, k, v))
-        s32 = _sink_f32(sink, q)
-        out, q_p, k_p, v_p, out_p, lse, _, rng = paged_attn.varlen_fwd_sink(
-            q, k, v, None, cu_q, cu_k, None, block_table, None, max_q, max_k, 0.0, softmax_scale,
-            False, causal, window_size[0], window_size[1], softcap, False, None, s32)
-        ctx.save_for_backward(q_p, k_p, v_p, out_p, lse, cu_q, cu_k, rng, s32)
-        ctx.args = (max_q, max_k, softmax_scale, causal, window_size, softcap, deterministic,
-                    q.shape[-1], block_table is not None, sink.dtype)
-        return out, lse
-
-    @staticmethod
-    def backward(ctx, dout, *_):
-        q, k, v, out, lse, cu_q, cu_k, rng, s32 = ctx.saved_tensors
-        (max_q, max_k, scale, causal, window, softcap, deterministic, d_og, paged,
-         sink_dtype) = ctx.args
-        if paged:
-            raise RuntimeError("backward through a paged K/V cache is not supported")
         dq, dk, dv, softmax_d = paged_attn.varlen_bwd(
-            _maybe_contiguous(dout), q, k, v, out, lse, None, None, None, cu_q, cu_k, None, max_q,
-            max_k, 0.0, scale, False, causal, window[0], window[1], softcap, deterministic, None,
-            rng)
-        dsink = None
-        if ctx.needs_input_grad[3]:
-            dsink = paged_attn.sink_bwd(lse, softmax_d, s32, True).to(sink_dtype)
+            _maybe_contiguous(dout), q, k, v, out, lse, None, None, None, cu_q, cu_k, alibi, max_q,
+            max_k, dropout_p, scale, False, causal, window[0], window[1], softcap, deterministic,
+            None, rng)
+        dsink = _sink_grad(ctx, lse, softmax_d, s32[0] if s32 else None, True)
         dq, dk, dv = dq[..., :d_og], dk[..., :d_og], dv[..., :d_og]
-        return (dq, dk, dv, dsink) + (None,) * 10
+        return (dq, dk, dv, dsink) + (None,) * 13
 
 
 def flash_attn_varlen_fp8_func(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k,
@@ -294,33 +249,9 @@ def flash_attn_varlen_fp8_func(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q
 
     Descales and quantize= as `flash_attn_fp8_func`; a [b, hk] descale is indexed by (sequence,
     kv head)."""
-    if q.requires_grad or k.requires_grad or v.requires_grad:
-        raise NotImplementedError("the fp8 forward has no backward")
-    if out_dtype not in (torch.bfloat16, torch.float16):
-        raise ValueError("out_dtype must be bfloat16 or float16")
-    if softmax_scale is None:
-        softmax_scale = q.shape[-1] ** (-0.5)
-
-    if quantize is not None:
-        q, k, v, q_descale, k_descale, v_descale = _quantize_qkv(
-            q, k, v, quantize, (q_descale, k_descale, v_descale), cu_seqlens_q, cu_seqlens_k,
-            max_seqlen_q, max_seqlen_k)
-
-    def _f(x):
-        return 1.0 if x is None else float(x)
-    q, k, v = (_maybe_contiguous(x) for x in (q, k, v))
-    if _device_descales(q_descale, k_descale, v_descale):
-        qd, kd, vd = (_as_device_descale(x, q.device) for x in (q_descale, k_descale, v_descale))
-        out, lse = paged_attn.varlen_fwd_fp8_ex(q, k, v, None, cu_seqlens_q, cu_seqlens_k, seqused_k,
-                                                int(max_seqlen_q), int(max_seqlen_k), qd, kd, vd,
-                                                softmax_scale, causal, int(window_size[0]),
-                                                int(window_size[1]), out_dtype == torch.float16)
-        return (out, lse) if return_lse else out
-    out, lse = paged_attn.varlen_fwd_fp8(q, k, v, None, cu_seqlens_q, cu_seqlens_k, seqused_k,
-                                         int(max_seqlen_q), int(max_seqlen_k), _f(q_descale),
-                                         _f(k_descale), _f(v_descale), softmax_scale, causal,
-                                         int(window_size[0]), int(window_size[1]),
-                                         out_dtype == torch.float16)
+    packed = (cu_seqlens_q, cu_seqlens_k, seqused_k, int(max_seqlen_q), int(max_seqlen_k))
+    out, lse = _fp8_forward("varlen_fwd_fp8", q, k, v, packed, (q_descale, k_descale, v_descale),
+                            softmax_scale, causal, window_size, out_dtype, quantize)
     return (out, lse) if return_lse else out
 
 
@@ -340,11 +271,6 @@ def flash_attn_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, ma
         softmax_scale = q.shape[-1] ** (-0.5)
     if sink is not None:
         _check_sink_args(q, dropout_p, alibi_slopes)
-        out, lse = _FlashAttnVarlenSinkFunc.apply(
-            q, k, v, sink, cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), int(max_seqlen_k),
-            softmax_scale, causal, tuple(int(w) for w in window_size), softcap, deterministic,
-            block_table)
-        return out if not return_attn_probs else (out, lse, None)
     if q.dtype == torch.float8_e4m3fn:
         # refuse what the fp8 forward lacks instead of dropping it
         if dropout_p != 0.0 or softcap != 0.0 or alibi_slopes is not None or block_table is not None:
@@ -358,7 +284,7 @@ def flash_attn_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, ma
                                               return_lse=True)
         return out if not return_attn_probs else (out, lse, None)
     out, lse, s_dmask = _FlashAttnVarlenFunc.apply(
-        q, k, v, cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), int(max_seqlen_k), dropout_p,
+        q, k, v, sink, cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), int(max_seqlen_k), dropout_p,
         softmax_scale, causal, tuple(int(w) for w in window_size), softcap, alibi_slopes,
         deterministic, return_attn_probs, block_table)
     return out if not return_attn_probs else (out, lse, s_dmask)
@@ -409,6 +335,9 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
     if sink is not None:
         _check_sink_args(q, 0.0, alibi_slopes)
         sink = _sink_f32(sink, q)
+    if isinstance(cache_seqlens, int):
+        cache_seqlens = torch.full((q.shape[0],), cache_seqlens, dtype=torch.int32, device=q.device)
+    window = (int(window_size[0]), int(window_size[1]))
     if k_cache.dtype == torch.float8_e4m3fn:
         if block_table is None or cache_seqlens is None or alibi_slopes is not None or softcap > 0:
             raise NotImplementedError("fp8 K/V cache: paged decode with block_table and "
@@ -418,36 +347,24 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
         if k is None and (rotary_cos is not None or rotary_sin is not None):
             raise ValueError("If rotary cos/sin are provided, new key / value to be appended to "
                              "KV cache must also be provided")
-        if isinstance(cache_seqlens, int):
-            cache_seqlens = torch.full((q.shape[0],), cache_seqlens, dtype=torch.int32,
-                                       device=q.device)
         if k is not None:
             # append (+ rotary on k and q) into the fp8 cache, then attend over the grown lengths
-            per_token = bool(causal) or int(window_size[0]) >= 0 or int(window_size[1]) >= 0
+            per_token = bool(causal) or window[0] >= 0 or window[1] >= 0
             cache_seqlens, q = paged_attn.kvcache_append_fp8(
                 q, k_cache.view(torch.uint8), v_cache.view(torch.uint8), k, v,
                 _maybe_contiguous(cache_seqlens), block_table, rotary_cos, rotary_sin,
                 float(k_scale), float(v_scale), rotary_interleaved, per_token)
+        op = "fwd_kvcache_fp8"
         args = (q, k_cache.view(torch.uint8), v_cache.view(torch.uint8), cache_seqlens,
-                block_table, float(k_scale), float(v_scale), softmax_scale, causal,
-                int(window_size[0]), int(window_size[1]), num_splits)
-        if sink is not None:
-            out, lse = paged_attn.fwd_kvcache_fp8_sink(*args, sink)
-        else:
-            out, lse = paged_attn.fwd_kvcache_fp8(*args)
-        return (out, lse) if return_softmax_lse else out
-    if cache_seqlens is not None and isinstance(cache_seqlens, int):
-        cache_seqlens = torch.full((q.shape[0],), cache_seqlens, dtype=torch.int32,
-                                   device=k_cache.device)
-        cache_seqlens = _maybe_contiguous(cache_seqlens)
-    cache_batch_idx = _maybe_contiguous(cache_batch_idx)
-    block_table = _maybe_contiguous(block_table)
-    args = (q, k_cache, v_cache, k, v, cache_seqlens, rotary_cos, rotary_sin, cache_batch_idx,
-            block_table, alibi_slopes, None, softmax_scale, causal, int(window_size[0]),
-            int(window_size[1]), softcap, rotary_interleaved, num_splits,
-            _maybe_contiguous(cache_leftpad))
-    if sink is not None:
-        out, lse = paged_attn.fwd_kvcache_sink(*args, sink)
+                block_table, float(k_scale), float(v_scale), softmax_scale, causal, *window,
+                num_splits)
     else:
-        out, lse = paged_attn.fwd_kvcache(*args)
+        op = "fwd_kvcache"
+        args = (q, k_cache, v_cache, k, v, cache_seqlens, rotary_cos, rotary_sin,
+                _maybe_contiguous(cache_batch_idx), _maybe_contiguous(block_table), alibi_slopes,
+                None, softmax_scale, causal, *window, softcap, rotary_interleaved, num_splits,
+                _maybe_contiguous(cache_leftpad))
+    if sink is not None:
+        op, args = op + "_sink", args + (sink,)
+    out, lse = getattr(paged_attn, op)(*args)
     return (out, lse) if return_softmax_lse else out
