@@ -137,7 +137,9 @@ const char* fmha_version(void);
  * another thread launches is safe (that launch sees the old or the new value).  Returns 0, or
  * -1 for an unknown name / out-of-range value.  Knobs: fwd_waves (4 | 8 waves = 128 | 256
  * query rows per forward workgroup), fwd_prio (0/1), fwd_persistent (workgroups per CU, 0 =
- * one workgroup per item), fwd_slack (0..16), fwd_order (0/1), fwd_dyn (0..2), fwd_xcdq (0/1),
+ * one workgroup per item), fwd_slack (0..16; an fp16 launch runs with at most 15 and an fp8 one
+ * with at most 8, since P <= 2^slack must fit the type it is rounded to), fwd_order (0/1),
+ * fwd_dyn (0..2), fwd_xcdq (0/1),
  * fwd_pipe (0..2), fwd_decode (0/1), dec_wg_per_cu (1..16), dec_hmaj (0..2), dec_mr (16/32),
  * fwd_w4 (D = 128 forward where eligible — dense, varlen, or a paged cache whose page size is a
  * power of two >= 8: 4 auto, the default = 3 where no row has a right window and the cache is

@@ -23,8 +23,10 @@ from oracle import attention_ref as orc
 
 
 def attention_fp8_kernel_model(q8, k8, v8, q_scale, k_scale, v_scale, causal=False,
-                               window_size=(-1, -1), slack=8):
-    """fp32 [b, sq, h, d] output of the 4-wave fp8 kernel's arithmetic (see the module doc)."""
+                               window_size=(-1, -1), slack=8, clamp_slack=True):
+    """fp32 [b, sq, h, d] output of the 4-wave fp8 kernel's arithmetic (see the module doc).
+    clamp_slack=False: the threshold 2^slack as given, without the kernel's limit of 8 (P then
+    passes 448, the e4m3 maximum, once slack > 8: what an unclamped launch would compute)."""
     b, sq, h, d = q8.shape
     sk, hk = k8.shape[1], k8.shape[2]
     G = h // hk
@@ -34,7 +36,7 @@ def attention_fp8_kernel_model(q8, k8, v8, q_scale, k_scale, v_scale, causal=Fal
     masked = orc.local_mask(sq, sk, window_size) if (window_size[0] >= 0 or window_size[1] >= 0) \
         else torch.zeros(sq, sk, dtype=torch.bool)
     c = d ** -0.5 * math.log2(math.e)
-    thr = 2.0 ** min(slack, 8)
+    thr = 2.0 ** (min(slack, 8) if clamp_slack else slack)
     half = ((torch.arange(64) >> 2) & 1).bool()          # key 32 kt + 8 d + 4 hh + i: lane half hh
     out = torch.zeros(b, sq, h, d)
     ntile = (sk + 63) // 64

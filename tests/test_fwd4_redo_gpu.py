@@ -24,6 +24,8 @@ import torch
 
 from oracle import attention_ref as orc
 from tests import golden_util as gu
+from tests.softmax_stress_util import (_check, _growing, _option, _overflow_margin, _randn,  # noqa: F401
+                                       _rounding_bound)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -33,21 +35,6 @@ LSE_ATOL = 1e-3
 def _lib():
     from xf_flash_attention_cutlass_amd import capi
     return capi.lib()
-
-
-class _option:
-    """fmha_set_option for the duration of a block (process-wide knob, restored after)."""
-
-    def __init__(self, name, value):
-        self.name, self.value = name.encode(), value
-
-    def __enter__(self):
-        L = _lib()
-        self.old = L.fmha_get_option(self.name)
-        assert L.fmha_set_option(self.name, self.value) == 0
-
-    def __exit__(self, *exc):
-        assert _lib().fmha_set_option(self.name, self.old) == 0
 
 
 def _fwd(q, k, v, causal, window=(-1, -1)):
@@ -86,53 +73,6 @@ def _assert_fwd4(wr=0):
     kern = L.fmha_last_kernel().decode()
     want = expected_kernel(L.fmha_get_option(b"fwd_w4"), wr)
     assert kern.startswith(want + " "), kern
-
-
-def _check(o, lse, q, k, v, causal, what, rtol_lse=0.0, o_atol=None):
-    ref, _ = orc.attention_ref(q, k, v, causal=causal)
-    pt, _ = orc.attention_ref(q, k, v, causal=causal, upcast=False, reorder_ops=True)
-    assert torch.isfinite(o.float()).all(), f"{what}: non-finite output"
-    ok, err, bound = orc.parity_ok(o, ref, pt, 2.0)
-    assert ok, f"{what}: max|out-ref|={err:.3g} > bound {bound:.3g}"
-    if o_atol is not None:
-        assert err <= o_atol, f"{what}: max|out-ref|={err:.3g} > {o_atol}"
-    lref = orc.attention_lse_ref(q, k, causal=causal)
-    fin = torch.isfinite(lref)
-    assert torch.equal(torch.isinf(lse), ~fin), f"{what}: empty-row pattern differs"
-    tol = LSE_ATOL + rtol_lse * lref[fin].abs()
-    lerr = (lse[fin] - lref[fin]).abs()
-    assert (lerr <= tol).all(), f"{what}: max|lse-ref|={lerr.max().item():.3g}"
-
-
-def _randn(shape, seed, dtype):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn(*shape, generator=g).to(dtype)
-
-
-def _growing(k, amp):
-    """k rows scaled by 1 + amp * j / sk along the key axis (scores grow with the key)."""
-    sk = k.shape[1]
-    f = 1.0 + amp * torch.arange(sk, dtype=torch.float32) / sk
-    return (k.float() * f[None, :, None, None]).to(k.dtype)
-
-
-def _overflow_margin(q, k, causal):
-    """max over rows of (max later score - tile 0's max) in log2 units: > 128 means exp2
-    against tile 0's max overflows fp32, i.e. the kernel cannot be right without the redo."""
-    c = q.shape[-1] ** -0.5 * 1.4426950408889634
-    hk = k.shape[2]
-    g = q.shape[2] // hk
-    kk = k.float().repeat_interleave(g, dim=2)
-    s = torch.einsum("bqhd,bkhd->bhqk", q.float(), kk) * c
-    sq, sk = q.shape[1], k.shape[1]
-    if causal:
-        i = torch.arange(sq)[:, None]
-        j = torch.arange(sk)[None, :]
-        s = s.masked_fill(j > i + sk - sq, float("-inf"))
-    m0 = s[..., :64].amax(-1)
-    later = s[..., 64:].amax(-1)
-    d = later - m0
-    return d[torch.isfinite(d)].max().item()
 
 
 # ------------------------------------------------------------ fwd_slack = 0: redo everywhere --
@@ -228,15 +168,6 @@ def test_fwd4_growing_scores(dtype, causal, amp):
     o, lse = _fwd(q, k, v, causal)
     _check(o, lse, q, k, v, causal, f"growing amp{amp} c{causal} {dtype}", rtol_lse=1e-5,
            o_atol=_rounding_bound(q, k, v, causal))
-
-
-def _rounding_bound(q, k, v, causal):
-    """A priori bound on |O - O_ref| from the kernel's two roundings: P to the input dtype before
-    PV (half an ulp, u = 2^-8 bf16 / 2^-11 fp16, relative per weight: <= u max|v|) and O to the
-    output dtype (<= u |O|); 5 % slack for the fp32 sums."""
-    u = 2.0 ** -8 if q.dtype == torch.bfloat16 else 2.0 ** -11
-    ref, _ = orc.attention_ref(q, k, v, causal=causal)
-    return 1.05 * u * (v.float().abs().max().item() + ref.float().abs().max().item())
 
 
 def test_fwd4_growing_scores_varlen(xfa):

@@ -332,8 +332,11 @@ void run_sdmask(const FwdParams& p, void* s, bool bf16, hipStream_t st) {
 
 // The one place that reads the schedule knobs every forward launch shares.  p.fwd4 carries
 // either kernel-choice knob: fwd_w4 on the bf16 / fp16 forward, fp8_w4 on the fp8 one (their
-// launchers are separate, so the field never means both).
-void load_schedule(FwdParams& p, const std::atomic<int>& w4) {
+// launchers are separate, so the field never means both).  slack_max: the kernels keep
+// P = exp2(S c - m_sc) within 2^fwd_slack, and P is rounded to the type of the PV operand, so the
+// slack a launch runs with stops where that type does: 8 for e4m3 (256 < 448), 15 for fp16
+// (2^16 rounds to inf), the knob's own 16 for bf16.
+void load_schedule(FwdParams& p, const std::atomic<int>& w4, int slack_max) {
     Options& o = options();
     p.device = current_device();
     p.num_cus = num_cus(p.device);
@@ -341,7 +344,7 @@ void load_schedule(FwdParams& p, const std::atomic<int>& w4) {
     p.persist_per_cu = o.fwd_persistent.load();
     p.order = o.fwd_order.load();
     p.xcdq = o.fwd_xcdq.load();
-    p.max_slack = (float)o.fwd_slack.load();
+    p.max_slack = (float)std::min(o.fwd_slack.load(), slack_max);
 }
 // ... and takes the item-queue counter where fwd_dyn reaches `dyn_min`; `code`: the status of
 // a failed allocation
@@ -353,7 +356,7 @@ bool take_item_queue(FwdParams& p, hipStream_t st, int dyn_min, int code) {
 
 void run_fwd(FwdParams& p, bool bf16, hipStream_t st, int num_splits_req) {
     Options& o = options();
-    load_schedule(p, o.fwd_w4);
+    load_schedule(p, o.fwd_w4, bf16 ? 16 : 15);
     p.waves = o.fwd_waves.load();
     p.prio_hi = o.fwd_prio.load();
     p.pipe = o.fwd_pipe.load();
@@ -491,7 +494,7 @@ void run_fwd_fp8(FwdParams& p, const Fp8Descales& ds, int dyn_min,
     p.q_scale = ds.q; p.k_scale = ds.k; p.v_scale = ds.v;
     p.q_descale = ds.q_ptr; p.k_descale = ds.k_ptr; p.v_descale = ds.v_ptr;
     p.ds_batch = ds.batch_stride; p.ds_head = ds.head_stride;
-    load_schedule(p, options().fp8_w4);
+    load_schedule(p, options().fp8_w4, 8);
     p.num_splits = 1;
     if (!take_item_queue(p, st, dyn_min, 1)) return;
     g_last_splits = 1;
