@@ -127,7 +127,7 @@ void fmha_set_rng_state(uint64_t seed, uint64_t offset);
 void fmha_set_rng_state_device(const int64_t* seed_ptr, const int64_t* offset_ptr,
                                uint64_t offset_add, int64_t* rng_out);
 
-/* Library version / build identification, e.g. "xf-fmha-gfx950 2.7".  2.0 (round 3) changed
+/* Library version / build identification, e.g. "xf-fmha-gfx950 2.8".  2.0 (round 3) changed
  * argument lists of existing symbols; 2.1 exports those under _v2 names (see INTEGRATION.md
  * "ABI history"). */
 const char* fmha_version(void);
@@ -417,6 +417,43 @@ void fmha_page_kvcache_fwd_sink(void* q, void* kcache, void* vcache, void* o, vo
 void fmha_bwd_sink(const float* softmax_lse, const float* softmax_d, const float* sink, float* dsink,
                    int32_t batch, int32_t num_heads, int32_t rows, int64_t batch_stride,
                    int64_t head_stride, hipStream_t stream);
+
+/* ------------------------------------------------- merge of partial attention states (2.8) --- */
+
+/* Most parts one fmha_merge_states call takes. */
+#define FMHA_MERGE_MAX_PARTS 16
+
+/* Merge num_parts partial results (O_i, LSE_i) of the same queries, each computed over its own
+ * keys (a cached prefix and a new suffix; the K/V chunks of ring attention), into the (O, LSE) of
+ * one softmax over all of those keys (other libraries' merge_attn_states / merge_state).
+ * o_parts / lse_parts: HOST arrays of num_parts DEVICE pointers, 1 <= num_parts <=
+ * FMHA_MERGE_MAX_PARTS; the pointers are copied by value into the kernel's arguments: no device
+ * table, no copy, no allocation, no host sync (capturable in a graph).
+ * strides[10], in ELEMENTS: the parts' O {batch, row, head}, the output's O {batch, row, head},
+ * the parts' LSE {batch, head}, the output's LSE {batch, head}.  O's last dimension is contiguous
+ * (fmha_fwd_strided's convention), an LSE row is contiguous (fmha_bwd_sink's): element (b, h, row)
+ * at b * batch + h * head + row; all parts share one stride set.  Dense: O [batch, rows, heads,
+ * head_size], LSE [batch, heads, rows]; packed: batch = 1, rows = total_q, LSE [heads, total_q].
+ * head_size a multiple of 8 and <= 256; O pointers 16-byte aligned, O strides multiples of 8.
+ * Per (batch, row, head), in fp32:
+ *   a part whose LSE is +inf (this library's "no visible key") or -inf (other libraries') is
+ *   absent, and its O never enters the sum (it may hold anything, NaN included);
+ *   over the present parts  m = max LSE_i, w_i = exp(LSE_i - m), den = sum w_i,
+ *   O = sum (w_i / den) O_i  rounded once to the dtype,  LSE = m + log(den);
+ *   sink != NULL (fp32 [num_heads], as in 2.7): the sink joins afterwards - O is scaled by
+ *   f = 1 / (1 + exp(sink[h] - LSE)) and LSE becomes log(exp(LSE) + exp(sink[h])); sink[h] = -inf
+ *   gives the bits of the call without a sink;
+ *   no part present: O = 0 and LSE = +inf, whatever the sink.
+ * o and lse may be exactly part 0's buffers (same pointer and strides) for in-place accumulation;
+ * lse may be NULL.  The parts are summed in index order without atomics: bitwise reproducible.
+ * rows == 0 or batch == 0 launches nothing and succeeds.  Refused with an error, outputs
+ * untouched: num_parts out of range, a NULL part pointer, a bad head_size, bad strides or
+ * alignment, o (or lse) overlapping a part other than part 0 or part 0 only partly (judged on the
+ * byte ranges the strides span). */
+void fmha_merge_states(const void* const* o_parts, const float* const* lse_parts, int32_t num_parts,
+                       void* o, float* lse, const float* sink,
+                       int32_t batch, int32_t rows, int32_t num_heads, int32_t head_size,
+                       const int64_t* strides, bool is_fp16, hipStream_t stream);
 
 #ifdef __cplusplus
 } /* extern "C" */

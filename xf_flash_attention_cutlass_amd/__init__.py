@@ -43,8 +43,10 @@ from .interface import (  # noqa: E402
     flash_attn_varlen_func,
     flash_attn_varlen_kvpacked_func,
     flash_attn_with_kvcache,
+    merge_attn_states,
     quantize_fp8,
 )
+from .sharding import ring_attention, zigzag_gather, zigzag_split  # noqa: E402
 
 __all__ = [
     "paged_attn",
@@ -56,4 +58,8 @@ __all__ = [
     "flash_attn_varlen_kvpacked_func",
     "flash_attn_with_kvcache",
     "quantize_fp8",
+    "merge_attn_states",
+    "ring_attention",
+    "zigzag_split",
+    "zigzag_gather",
 ]

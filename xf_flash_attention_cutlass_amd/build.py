@@ -83,6 +83,7 @@ def build_lib(jobs: int = 8, force: bool = False, verbose: bool = False, variant
             todo.append((src, os.path.join(OBJ, f"fmha_{kind}_hd{hd}_{dt}.o"), defs))
     todo.append((os.path.join(CSRC, "fmha_append.hip"), os.path.join(OBJ, "fmha_append.o"), []))
     todo.append((os.path.join(CSRC, "fmha_quant.hip"), os.path.join(OBJ, "fmha_quant.o"), []))
+    todo.append((os.path.join(CSRC, "fmha_merge.hip"), os.path.join(OBJ, "fmha_merge.o"), []))
     todo.append((os.path.join(CSRC, "fmha_fwd_fp8.hip"), os.path.join(OBJ, "fmha_fwd_fp8.o"), []))
     todo.append((os.path.join(CSRC, "fmha_api.cpp"), os.path.join(OBJ, "fmha_api.o"), []))
     if variants:

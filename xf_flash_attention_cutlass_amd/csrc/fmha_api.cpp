@@ -521,7 +521,7 @@ const char* fmha_last_error(void) { return g_err.c_str(); }
 int fmha_last_status(void) { return g_status; }
 int fmha_last_num_splits(void) { return g_last_splits; }
 const char* fmha_last_kernel(void) { return g_last_kernel; }
-const char* fmha_version(void) { return XFA_VARIANTS ? "xf-fmha-gfx950 2.7 (variants)" : "xf-fmha-gfx950 2.7"; }
+const char* fmha_version(void) { return XFA_VARIANTS ? "xf-fmha-gfx950 2.8 (variants)" : "xf-fmha-gfx950 2.8"; }
 
 void fmha_set_rng_state(uint64_t seed, uint64_t offset) {
     g_seed = seed;
@@ -1341,6 +1341,80 @@ void fmha_bwd_sink(const float* softmax_lse, const float* softmax_d, const float
         hip_ok(launch_bwd_sink(p, stream), "sink backward launch");
     } catch (...) {
         fail(9, "internal error in fmha_bwd_sink");
+    }
+}
+
+static_assert(FMHA_MERGE_MAX_PARTS == kMergeMaxParts, "the header's part limit is the kernel's");
+
+void fmha_merge_states(const void* const* o_parts, const float* const* lse_parts, int32_t num_parts,
+                       void* o, float* lse, const float* sink, int32_t batch, int32_t rows,
+                       int32_t num_heads, int32_t head_size, const int64_t* strides, bool is_fp16,
+                       hipStream_t stream) {
+    try {
+        clear_error();
+        REQUIRE(num_parts >= 1 && num_parts <= FMHA_MERGE_MAX_PARTS,
+                "num_parts must be in [1, %d] (got %d)", FMHA_MERGE_MAX_PARTS, num_parts);
+        REQUIRE(o_parts && lse_parts && o && strides,
+                "o_parts, lse_parts, o and strides must be non-null pointers");
+        for (int i = 0; i < num_parts; ++i)
+            REQUIRE(o_parts[i] && lse_parts[i], "part %d: o and lse must be non-null device pointers", i);
+        REQUIRE(batch >= 0 && rows >= 0 && num_heads > 0,
+                "batch and rows must be non-negative and num_heads positive (got %d, %d, %d)", batch, rows,
+                num_heads);
+        REQUIRE(head_size > 0 && head_size % 8 == 0 && head_size <= 256,
+                "head_size must be a multiple of 8 and at most 256 (got %d)", head_size);
+        if (batch == 0 || rows == 0) return;
+        const int ext[3] = {batch, rows, num_heads};
+        for (int i = 0; i < 6; ++i)
+            REQUIRE(strides[i] >= 0 && (ext[i % 3] == 1 || strides[i] % 8 == 0) &&
+                        (i < 3 || ext[i % 3] == 1 || strides[i] > 0),
+                    "strides: O strides must be non-negative multiples of 8 elements (16 bytes), the "
+                    "output's positive: stride %d is %lld", i, (long long)strides[i]);
+        for (int i = 6; i < 10; ++i)
+            REQUIRE(strides[i] >= 0 && (i < 8 || ext[i % 2 ? 2 : 0] == 1 || strides[i] > 0),
+                    "strides: LSE strides must be non-negative, the output's positive: stride %d is %lld",
+                    i, (long long)strides[i]);
+        REQUIRE(!(((uintptr_t)o) & 15), "o must be a 16-byte aligned device pointer");
+        for (int i = 0; i < num_parts; ++i)
+            REQUIRE(!(((uintptr_t)o_parts[i]) & 15), "part %d: o must be a 16-byte aligned device pointer", i);
+        // Aliasing, on the byte ranges the strides span (views interleaved in one buffer count as
+        // overlapping): the output may be exactly part 0 - same pointer, same strides - and may
+        // touch no other part.
+        auto o_span = [&](const int64_t* s) {
+            return ((int64_t)(batch - 1) * s[0] + (int64_t)(rows - 1) * s[1] + (int64_t)(num_heads - 1) * s[2] + head_size) * 2;
+        };
+        auto l_span = [&](const int64_t* s) {
+            return ((int64_t)(batch - 1) * s[0] + (int64_t)(num_heads - 1) * s[1] + rows) * 4;
+        };
+        auto overlap = [](const void* a, int64_t na, const void* b, int64_t nb) {
+            const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+            return x < y + (uintptr_t)nb && y < x + (uintptr_t)na;
+        };
+        const bool o_same = strides[0] == strides[3] && strides[1] == strides[4] && strides[2] == strides[5];
+        const bool l_same = strides[6] == strides[8] && strides[7] == strides[9];
+        for (int i = 0; i < num_parts; ++i) {
+            if (overlap(o, o_span(strides + 3), o_parts[i], o_span(strides)))
+                REQUIRE(i == 0 && o == o_parts[0] && o_same,
+                        "o overlaps part %d: the output may alias part 0 only, exactly (same pointer and strides)", i);
+            if (lse && overlap(lse, l_span(strides + 8), lse_parts[i], l_span(strides + 6)))
+                REQUIRE(i == 0 && lse == lse_parts[0] && l_same,
+                        "lse overlaps part %d: the output may alias part 0 only, exactly (same pointer and strides)", i);
+        }
+        const int rpb = 256 / (head_size / 8);
+        REQUIRE(((int64_t)batch * rows * num_heads + rpb - 1) / rpb <= 0x7fffffffLL,
+                "batch * rows * num_heads = %lld is more than one launch covers",
+                (long long)batch * rows * num_heads);
+        MergeParams p{};
+        for (int i = 0; i < num_parts; ++i) { p.o_parts[i] = o_parts[i]; p.lse_parts[i] = lse_parts[i]; }
+        p.o = o; p.lse = lse; p.sink = sink;
+        p.po_batch = strides[0]; p.po_row = strides[1]; p.po_head = strides[2];
+        p.o_batch = strides[3]; p.o_row = strides[4]; p.o_head = strides[5];
+        p.pl_batch = strides[6]; p.pl_head = strides[7];
+        p.l_batch = strides[8]; p.l_head = strides[9];
+        p.n = num_parts; p.b = batch; p.rows = rows; p.h = num_heads; p.d = head_size;
+        hip_ok(launch_merge_states(p, is_fp16, stream), "merge launch");
+    } catch (...) {
+        fail(9, "internal error in fmha_merge_states");
     }
 }
 

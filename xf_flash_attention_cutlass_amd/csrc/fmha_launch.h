@@ -244,6 +244,24 @@ struct SinkBwdParams {
 };
 hipError_t launch_bwd_sink(const SinkBwdParams& p, hipStream_t st);
 
+// Merge of partial attention states (fmha_merge.hip): n parts (O_i, LSE_i) -> (O, LSE), the part
+// pointers by value.  O by element strides (the parts share one set), LSE [.., rows] by its
+// strides; a packed input is batch 1 with rows = total_q.  o / lse may be part 0's buffers.
+constexpr int kMergeMaxParts = 16;    // FMHA_MERGE_MAX_PARTS of the header
+struct MergeParams {
+    const void* o_parts[kMergeMaxParts];
+    const float* lse_parts[kMergeMaxParts];
+    void* o;
+    float* lse;                       // or null
+    const float* sink;                // fp32 [h] or null
+    int64_t po_batch, po_row, po_head;
+    int64_t o_batch, o_row, o_head;
+    int64_t pl_batch, pl_head;
+    int64_t l_batch, l_head;
+    int n, b, rows, h, d;
+};
+hipError_t launch_merge_states(const MergeParams& p, bool fp16, hipStream_t st);
+
 // D = 256 (bucket of 129..256): 4 waves x 32 rows, one wave per SIMD (512 registers:
 // Q fragments and the O accumulator alone are 192), no LDS-DMA pipeline
 inline int fwd_block_m(int d, int waves) { return d > 128 ? 128 : waves * 32; }

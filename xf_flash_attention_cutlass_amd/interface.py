@@ -107,6 +107,38 @@ def flash_attn_func(q, k, v, dropout_p=0.0, causal=False, window_size=(-1, -1), 
     return out if not return_attn_probs else (out, lse, s_dmask)
 
 
+def merge_attn_states(outs, lses, *, sink=None, packed=False, out=None, lse_out=None):
+    """Merge partial attention results of the same queries over different keys into the result
+    over all of them: one HIP launch (`paged_attn.merge_states`), no copies.
+
+    outs: 1 to 16 tensors [b, rows, h, d] (packed=True: [total_q, h, d]), bf16 or fp16, of one
+    shape and one stride set (views are fine: last dimension contiguous, 16-byte aligned);
+    lses: their fp32 log-sum-exps [b, h, rows] (packed: [h, total_q]), as `flash_attn_func(...,
+    return_attn_probs=True)`, `flash_attn_with_kvcache(..., return_softmax_lse=True)` and the
+    fp8 functions return them.  Per row: w_i = exp(lse_i - max lse), O = sum w_i O_i / sum w_i in
+    fp32 rounded once, LSE = max + log(sum w_i).  A part whose LSE is +inf (this library's "no
+    visible key") or -inf (other libraries') is absent for that row and its O is ignored; a row
+    with no part present gets O = 0 and LSE = +inf.
+
+    sink: a per-head logit [h] that joins the merged denominator (as `flash_attn_func`'s sink):
+    pass it HERE and not to the partial calls, so that it is counted once.
+    out / lse_out: tensors to write into; they may be outs[0] / lses[0] themselves (in-place
+    accumulation) and must not overlap any other part.  Returns (out, lse).
+
+    Not differentiable: the results carry no grad.  `flash_attn_func` does not propagate a
+    gradient into its LSE output, so a differentiable merge could not be chained through the
+    partial calls anyway; the differentiable path over K/V chunks is `sharding.ring_attention`,
+    which runs the backward kernels on each chunk with the merged out and LSE."""
+    outs, lses = list(outs), list(lses)
+    if not outs:
+        raise ValueError("merge_attn_states needs at least one part")
+    s32 = None if sink is None else _sink_f32(sink, outs[0])
+    with torch.no_grad():
+        o, lse = paged_attn.merge_states([x.detach() for x in outs], [x.detach() for x in lses],
+                                         s32, bool(packed), out, lse_out)
+    return o, lse
+
+
 _GRANULARITY = {"tensor": 0, "head": 1}
 
 

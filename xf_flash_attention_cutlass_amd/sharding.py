@@ -135,7 +135,12 @@ class _AllGatherDim(torch.autograd.Function):
 def all_gather_dim(local: torch.Tensor, sizes: Sequence[int], dim: int):
     """Concatenate per-rank pieces along `dim` (rank r holds sizes[r] entries) on every rank.
     Differentiable (`_AllGatherDim`): the backward narrows the output gradient to this rank's
-    piece.  World size 1 runs no collective: the local piece is the result."""
+    piece.  World size 1 runs no collective: the local piece is the result.
+
+    That backward assumes every rank computes the same loss from the gathered tensor, so the
+    gradient a rank gets for anything upstream of `local` covers its own piece only: gradients of
+    replicated inputs and parameters need a SUM all-reduce over the ranks (not DDP's average, and
+    not nothing) before they are used."""
     dist, rank, world = _world()
     if world == 1:
         return local
@@ -150,7 +155,11 @@ def sharded_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     and, if `gather`, all-gathers the outputs.  With fewer kv heads than ranks, or with
     prefer="batch" and a batch the world divides (whose gather along dim 0 needs no copy), the
     batch is sharded instead.  ALiBi slopes in `kw` are sliced to the rank's heads / batch rows.
-    Returns (out, my shard): a query-head range or a batch range (see `attention_shards`)."""
+    Returns (out, my shard): a query-head range or a batch range (see `attention_shards`).
+
+    Gradients: the gather's backward hands each rank the gradient of its own shard, so what a
+    rank gets for the replicated q / k / v (and for the parameters behind them) is its shard's
+    part only and needs a SUM all-reduce over the ranks (see `all_gather_dim`)."""
     dist, rank, world = _world()
     if local_fn is None:
         from . import flash_attn_func as local_fn
@@ -277,7 +286,11 @@ def sharded_varlen(q, k, v, cu_seqlens_q=None, cu_seqlens_k=None, local_fn: Call
     s_q*s_k; outputs are all-gathered back into the packed [total_q, H, d] order.  Pass a
     `plan` (`varlen_plan`, from host-side lengths) to run without any device sync; without
     one it is built from `cu_seqlens_*` (one host copy of each).  Differentiable: gradients
-    flow to this rank's tokens of q / k / v.  Returns (out, packed positions of my tokens)."""
+    flow to this rank's tokens of q / k / v.  Returns (out, packed positions of my tokens).
+
+    Those gradients cover this rank's sequences only: the gradients of the replicated q / k / v
+    and of the parameters behind them need a SUM all-reduce over the ranks (see
+    `all_gather_dim`)."""
     dist, rank, world = _world()
     if local_fn is None:
         from . import flash_attn_varlen_func as local_fn
@@ -327,3 +340,284 @@ def sharded_decode(q: torch.Tensor, kcache: torch.Tensor, vcache: torch.Tensor,
     if not gather:
         return out_local, bs
     return all_gather_dim(out_local, [s.size for s in shards], 0), bs
+
+
+# ------------------------------------------------------------------ ring attention ------------
+# Context parallelism: one SEQUENCE sharded over the ranks.  Every rank keeps its queries; the
+# K/V shards travel round the ring, each step is one forward of the unchanged kernels on one
+# (queries, K/V shard) pair, and the per-step (O_t, LSE_t) are joined once by `merge_states`
+# (DESIGN.md §3.9, §6).
+
+RING_MAX_WORLD = 16      # one merge call takes this many parts (FMHA_MERGE_MAX_PARTS)
+
+
+def zigzag_split(x: torch.Tensor, world: int, rank: int, dim: int = 1) -> torch.Tensor:
+    """This rank's shard of `x` in the zigzag layout of causal ring attention: `dim` is cut into
+    2 * world chunks and rank r holds chunks r and 2 * world - 1 - r (an early and a late one, so
+    that every rank has the same causal work)."""
+    n = x.shape[dim]
+    if n % (2 * world):
+        raise ValueError(f"zigzag_split: length {n} is not a multiple of 2 * world = {2 * world}")
+    c = n // (2 * world)
+    return torch.cat([x.narrow(dim, rank * c, c), x.narrow(dim, (2 * world - 1 - rank) * c, c)], dim=dim)
+
+
+def zigzag_gather(shards: Sequence[torch.Tensor], dim: int = 1) -> torch.Tensor:
+    """Inverse of `zigzag_split`: the whole tensor from the shards of ranks 0 .. world - 1."""
+    world = len(shards)
+    if shards[0].shape[dim] % 2:
+        raise ValueError("zigzag_gather: a zigzag shard has an even length")
+    c = shards[0].shape[dim] // 2
+    chunks = [None] * (2 * world)
+    for r, s in enumerate(shards):
+        chunks[r], chunks[2 * world - 1 - r] = s.narrow(dim, 0, c), s.narrow(dim, c, c)
+    return torch.cat(chunks, dim=dim)
+
+
+class KernelOps:
+    """The `ops` of `ring_attention` on the gfx950 kernels (the default).  A replacement supplies
+    the same four callables:
+
+      fwd(q, k, v, scale, causal, softcap, out=None) -> (out [b, sq, h, d], lse [b, h, sq])
+      bwd(dout, q, k, v, out, lse, scale, causal, softcap, deterministic)
+                                                     -> (dq, dk, dv, softmax_d [b, h, sq])
+      merge(outs, lses, sink, out, lse_out)          -> (out, lse_out), written in place
+      sink_bwd(lse, softmax_d, sink)                 -> dsink [h]
+
+    `causal` is bottom-right aligned and only ever passed with sq == sk; `bwd` takes the MERGED
+    out and lse of its query rows (it then yields exact dk / dv of its K/V chunk and that chunk's
+    additive share of dq); tensors may be strided views."""
+
+    @staticmethod
+    def fwd(q, k, v, scale, causal, softcap, out=None):
+        from . import paged_attn
+        r = paged_attn.fwd(q, k, v, out, None, 0.0, scale, causal, -1, -1, softcap, False, None)
+        return r[0], r[5]
+
+    @staticmethod
+    def bwd(dout, q, k, v, out, lse, scale, causal, softcap, deterministic):
+        from . import paged_attn
+        return tuple(paged_attn.bwd(dout, q, k, v, out, lse, None, None, None, None, 0.0, scale,
+                                    causal, -1, -1, softcap, deterministic, None, None))
+
+    @staticmethod
+    def merge(outs, lses, sink, out, lse_out):
+        from . import paged_attn
+        return tuple(paged_attn.merge_states(outs, lses, sink, False, out, lse_out))
+
+    @staticmethod
+    def sink_bwd(lse, softmax_d, sink):
+        from . import paged_attn
+        return paged_attn.sink_bwd(lse.contiguous(), softmax_d.contiguous(), sink, False)
+
+
+class DistRing:
+    """The `ring` of `ring_attention` over a torch.distributed group (the default): `shift` posts
+    one batch of isend / irecv (to the next rank, from the previous one) and returns at once;
+    `wait` completes it and returns the received tensors.  A replacement needs `rank`, `world`
+    and `shift(tensors) -> tensors from the previous rank`; if it has no `wait`, what `shift`
+    returns is used as it is."""
+
+    def __init__(self, group=None):
+        import torch.distributed as dist
+        self.dist, self.group = dist, group
+        self.rank, self.world = dist.get_rank(group), dist.get_world_size(group)
+        peer = (lambda i: dist.get_global_rank(group, i)) if group is not None else (lambda i: i)
+        self.next, self.prev = peer((self.rank + 1) % self.world), peer((self.rank - 1) % self.world)
+
+    def shift(self, tensors):
+        dist = self.dist
+        send = [t.contiguous() for t in tensors]
+        recv = [torch.empty_like(t) for t in send]
+        ops = [dist.P2POp(dist.isend, t, self.next, self.group) for t in send]
+        ops += [dist.P2POp(dist.irecv, t, self.prev, self.group) for t in recv]
+        return recv, send, dist.batch_isend_irecv(ops)
+
+    def wait(self, pending):
+        recv, _send, works = pending
+        for w in works:
+            w.wait()
+        return recv
+
+
+def _ring_wait(ring, pending):
+    wait = getattr(ring, "wait", None)
+    return pending if wait is None else wait(pending)
+
+
+def _ring_steps(world: int, rank: int, causal: bool, c: int):
+    """Step t of rank `rank`: the K/V of rank s = (rank - t) mod world and the sub-problem
+    (query rows, key rows, causal flag) the kernels run on it.  Non-causal: everything.  Causal
+    (zigzag shards of 2c rows): s == rank the local causal problem; s < rank all queries against
+    the FIRST half of the keys (the late half lies in every local query's future); s > rank the
+    SECOND half of the queries against all keys (the early half sees none of them)."""
+    everything = slice(None)
+    for t in range(world):
+        s = (rank - t) % world
+        if not causal or s == rank:
+            yield t, everything, everything, causal
+        elif s < rank:
+            yield t, everything, slice(0, c), False
+        else:
+            yield t, slice(c, 2 * c), everything, False
+
+
+def ring_forward(q, k, v, *, causal, softmax_scale, softcap, sink, ops, ring):
+    """The forward of `ring_attention` on this rank's shards: (out [b, s_local, h, d] in q's
+    dtype, lse [b, h, s_local] fp32 of the WHOLE sequence's softmax).  sink: what `ops.merge`
+    takes (fp32 [h]) or None.  No autograd; `ring_attention` wraps it."""
+    world, rank = ring.world, ring.rank
+    b, sl, h, _ = q.shape
+    c = sl // 2
+    kv = (k, v)
+    outs, lses, full = [], [], []
+    for t, rows, keys, cz in _ring_steps(world, rank, causal, c):
+        nxt = ring.shift(kv) if t + 1 < world else None      # posted before this step's compute
+        kt, vt = kv
+        if rows == slice(None):
+            o, l = ops.fwd(q, kt[:, keys], vt[:, keys], softmax_scale, cz, softcap)
+        else:
+            # rows [:c] of this part are never read: the second-half merge takes rows [c:] only
+            o = torch.empty_like(q)
+            o2, l2 = ops.fwd(q[:, rows], kt, vt, softmax_scale, cz, softcap, o[:, rows])
+            if o2.data_ptr() != o[:, rows].data_ptr():
+                o[:, rows].copy_(o2)
+            l = l2.new_empty((b, h, sl))
+            l[:, :, rows].copy_(l2)
+        outs.append(o)
+        lses.append(l)
+        full.append(rows == slice(None))
+        if nxt is not None:
+            kv = _ring_wait(ring, nxt)
+    if all(full):
+        out, lse = ops.merge(outs, lses, sink, None, None)
+        return out, lse
+    out, lse = torch.empty_like(outs[0]), torch.empty_like(lses[0])
+    lo, hi = slice(0, c), slice(c, sl)
+    ops.merge([o[:, lo] for o, f in zip(outs, full) if f], [l[:, :, lo] for l, f in zip(lses, full) if f],
+              sink, out[:, lo], lse[:, :, lo])
+    ops.merge([o[:, hi] for o in outs], [l[:, :, hi] for l in lses], sink, out[:, hi], lse[:, :, hi])
+    return out, lse
+
+
+def ring_backward(dout, q, k, v, out, lse, *, causal, softmax_scale, softcap, deterministic, sink,
+                  ops, ring):
+    """The backward of `ring_attention`: (dq, dk, dv, dsink or None) for this rank's shards from
+    the merged `out` / `lse` of `ring_forward`.  The same ring: every step runs the unchanged
+    `bwd` on the forward step's sub-problem; dq partials are summed in fp32 and rounded once;
+    the dk / dv accumulators (fp32) travel with their K/V shard and are home after `world`
+    steps.  dsink is THIS RANK'S share (its rows only)."""
+    world, rank = ring.world, ring.rank
+    c = q.shape[1] // 2
+    acc_t = torch.float64 if q.dtype == torch.float64 else torch.float32
+    dq = torch.zeros(q.shape, dtype=acc_t, device=q.device)
+    kv = (k, v)
+    acc = (torch.zeros(k.shape, dtype=acc_t, device=k.device), torch.zeros(v.shape, dtype=acc_t, device=v.device))
+    softmax_d = None
+    for t, rows, keys, cz in _ring_steps(world, rank, causal, c):
+        nxt = ring.shift(kv) if t + 1 < world else None
+        kt, vt = kv
+        g = ops.bwd(dout[:, rows], q[:, rows], kt[:, keys], vt[:, keys], out[:, rows], lse[:, :, rows],
+                    softmax_scale, cz, softcap, deterministic)
+        dq[:, rows] += g[0]
+        acc[0][:, keys] += g[1]
+        acc[1][:, keys] += g[2]
+        if t == 0:
+            softmax_d = g[3]          # step 0 is the local problem: all of this rank's rows
+        acc = _ring_wait(ring, ring.shift(acc)) if world > 1 else acc
+        if nxt is not None:
+            kv = _ring_wait(ring, nxt)
+    dsink = None if sink is None else ops.sink_bwd(lse, softmax_d, sink)
+    return dq.to(q.dtype), acc[0].to(k.dtype), acc[1].to(v.dtype), dsink
+
+
+class _RingAttention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, sink, causal, softmax_scale, softcap, deterministic, ops, ring):
+        s32 = None
+        if sink is not None:
+            s32 = sink.detach().to(device=q.device, dtype=torch.float64 if q.dtype == torch.float64
+                                   else torch.float32).contiguous()
+        out, lse = ring_forward(q, k, v, causal=causal, softmax_scale=softmax_scale, softcap=softcap,
+                                sink=s32, ops=ops, ring=ring)
+        ctx.save_for_backward(q, k, v, out, lse, *(() if s32 is None else (s32,)))
+        ctx.args = (causal, softmax_scale, softcap, deterministic, ops, ring)
+        ctx.sink_dtype = None if sink is None else sink.dtype
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, out, lse, *s32 = ctx.saved_tensors
+        causal, scale, softcap, deterministic, ops, ring = ctx.args
+        dq, dk, dv, dsink = ring_backward(dout, q, k, v, out, lse, causal=causal, softmax_scale=scale,
+                                          softcap=softcap, deterministic=deterministic,
+                                          sink=s32[0] if s32 and ctx.needs_input_grad[3] else None,
+                                          ops=ops, ring=ring)
+        if dsink is not None:
+            dsink = dsink.to(ctx.sink_dtype)
+        return (dq, dk, dv, dsink) + (None,) * 6
+
+
+def ring_attention(q, k, v, *, causal=False, softmax_scale=None, softcap=0.0, deterministic=False,
+                   sink=None, group=None, ops=None, ring=None, window_size=(-1, -1),
+                   alibi_slopes=None, dropout_p=0.0):
+    """Ring (context-parallel) attention: q, k, v are THIS RANK'S shard [b, s_local, h(k), d] of
+    one long sequence; returns this rank's rows of the attention over the whole sequence.
+    Differentiable in q, k, v and sink.
+
+    Layout.  Non-causal: contiguous shards (rank r holds rows [r * s_local, (r + 1) * s_local)).
+    Causal: the zigzag layout of `zigzag_split` (rank r holds chunks r and 2W - 1 - r of 2W), so
+    s_local is even and every rank does the same work.
+
+    Forward: W steps; at step t the rank holds the K/V of rank (r - t) mod W and runs one forward
+    of the unchanged kernels on it (for causal: the local causal problem, all queries against
+    the early key half, or the late query half against all keys, passed as strided views); the
+    exchange for step t + 1 is posted before the compute of step t.  The per-step (O_t, LSE_t)
+    stay in the input dtype and are merged once per query half by `merge_states`, which rounds
+    once; the sink joins there and only there.  Backward: the same ring with fp32 dk / dv
+    accumulators travelling alongside K/V; each step calls the unchanged backward with the
+    merged out and LSE, which makes it exact for its chunk.
+
+    sink: a per-head logit [h] as in `flash_attn_func`.  Its gradient is THIS RANK'S share (the
+    sum over this rank's rows): like the gradient of any replicated parameter it needs a
+    SUM all-reduce over the group by the caller (the q / k / v gradients need no reduction).
+
+    ops: the forward / backward / merge / sink-backward callables (`KernelOps`, the gfx950
+    kernels, by default); ring: the exchange (`DistRing` over `group` by default).  world == 1
+    with the default ops runs `flash_attn_func` itself, bit for bit.
+
+    Refused: sliding windows, ALiBi, dropout, fp8 inputs, more than 16 ranks (the part limit of
+    one merge), an odd s_local with causal, and with the default ops a head size that is not a
+    multiple of 8."""
+    if tuple(int(w) for w in window_size) != (-1, -1):
+        raise NotImplementedError("ring_attention does not support sliding windows")
+    if alibi_slopes is not None:
+        raise NotImplementedError("ring_attention does not support ALiBi")
+    if dropout_p != 0.0:
+        raise NotImplementedError("ring_attention does not support dropout")
+    if q.dtype == torch.float8_e4m3fn or k.dtype == torch.float8_e4m3fn or v.dtype == torch.float8_e4m3fn:
+        raise NotImplementedError("ring_attention does not support fp8 inputs")
+    if ring is None:
+        ring = DistRing(group)
+    if ring.world > RING_MAX_WORLD:
+        raise NotImplementedError(f"ring_attention supports at most {RING_MAX_WORLD} ranks "
+                                  f"(got {ring.world}): one merge takes that many parts")
+    if causal and q.shape[1] % 2:
+        raise ValueError(f"ring_attention: causal needs an even s_local (zigzag halves), got {q.shape[1]}")
+    if q.dim() != 4 or k.shape != v.shape or k.shape[1] != q.shape[1]:
+        raise ValueError("ring_attention: q [b, s_local, h, d] and k, v [b, s_local, hk, d] shards "
+                         "of one length are required")
+    if sink is not None and (sink.dim() != 1 or sink.shape[0] != q.shape[2]):
+        raise ValueError(f"sink must have shape (num_heads,) = ({q.shape[2]},), got {tuple(sink.shape)}")
+    if softmax_scale is None:
+        softmax_scale = q.shape[-1] ** (-0.5)
+    if ops is None:
+        if ring.world == 1:
+            from . import flash_attn_func
+            return flash_attn_func(q, k, v, causal=causal, softcap=softcap, deterministic=deterministic,
+                                   softmax_scale=softmax_scale, sink=sink)
+        if q.shape[-1] % 8:
+            raise NotImplementedError("ring_attention: head size must be a multiple of 8")
+        ops = KernelOps
+    return _RingAttention.apply(q, k, v, sink, causal, float(softmax_scale), float(softcap),
+                                bool(deterministic), ops, ring)
