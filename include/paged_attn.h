@@ -127,7 +127,7 @@ void fmha_set_rng_state(uint64_t seed, uint64_t offset);
 void fmha_set_rng_state_device(const int64_t* seed_ptr, const int64_t* offset_ptr,
                                uint64_t offset_add, int64_t* rng_out);
 
-/* Library version / build identification, e.g. "xf-fmha-gfx950 2.8".  2.0 (round 3) changed
+/* Library version / build identification, e.g. "xf-fmha-gfx950 2.9".  2.0 (round 3) changed
  * argument lists of existing symbols; 2.1 exports those under _v2 names (see INTEGRATION.md
  * "ABI history"). */
 const char* fmha_version(void);
@@ -454,6 +454,47 @@ void fmha_merge_states(const void* const* o_parts, const float* const* lse_parts
                        void* o, float* lse, const float* sink,
                        int32_t batch, int32_t rows, int32_t num_heads, int32_t head_size,
                        const int64_t* strides, bool is_fp16, hipStream_t stream);
+
+/* ------------------------------------------------- MLA decode over a latent cache (2.9) ------ */
+
+/* Decode attention for multi-head latent attention (DeepSeek-V2/V3/R1, Kimi) in its "absorbed"
+ * form: every query head attends over ONE shared latent row per token, head_size = 576 wide (512
+ * compressed-KV features + 64 rotary features), and the value is the first head_size_v = 512
+ * features of the same row.  bf16 or fp16.
+ *   q          [batch, seqlen_q, num_heads, 576] by element strides {batch, row, head}, last
+ *              dimension contiguous (fmha_fwd_strided's convention)
+ *   kv_cache   [num_blocks, page_block_size, 1, 576], contiguous; page_block_size % 16 == 0
+ *   block_table int32 [batch, block_table_stride], required; cache_seqlens int32 [batch]
+ *   o          [batch, seqlen_q, num_heads, 512] by element strides {batch, row, head}
+ *   softmax_lse fp32 [batch, num_heads, seqlen_q], or NULL
+ *   strides[6], in ELEMENTS: q {batch, row, head}, then o {batch, row, head}
+ * For sequence b with n = min(cache_seqlens[b], max_seqlen_k) keys K (n x 576, through the table)
+ * and V = K[:, :512]:  S = softmax_scale q K^T (all 576 features), O = softmax(S) V,
+ * LSE = logsumexp(S).  softmax_scale is the caller's (DeepSeek's is not 576^-1/2).
+ * Windows: (-1, -1) full attention; (-1, 0) causal, bottom-right aligned (the query at position s
+ * sees keys < n - seqlen_q + s + 1); any other window is refused.  A row without a visible key
+ * (n = 0; n < seqlen_q under causal) gives O = 0 and LSE = +inf.
+ * max_seqlen_k: an upper bound of the lengths, at most block_table_stride * page_block_size; it
+ * sizes the automatic split count.  num_splits <= 0: chosen from the workgroups against the CU
+ * count, at most the key tiles and 128; 1: a single pass without scratch or combine; up to 128.
+ * The split scratch comes from the per-stream pool: no allocation once it is warm, no host sync
+ * (capturable in a graph).  fmha_last_kernel() names fmha_mla_decode_kernel with its mapping
+ * (<tiles>: the waves of a workgroup are 16-row tiles of one (batch, key split); <splits>: one
+ * row tile, the waves are key splits), fmha_last_num_splits() the split count.
+ * batch_size == 0 launches nothing and succeeds.  Refused with an error, outputs untouched: a NULL
+ * q / kv_cache / o / block_table / cache_seqlens / strides, (head_size, head_size_v) other than
+ * (576, 512), a page size that is no multiple of 16, another window, num_heads < 1 or
+ * seqlen_q < 1, num_splits > 128, strides that are no multiples of 8 or pointers that are not
+ * 16-byte aligned, a page slab beyond the 32-bit offset limit.
+ * Partial results over two caches (a shared prefix and a suffix) are merged with
+ * fmha_merge_states, 256 of the 512 columns per call. */
+void fmha_mla_decode(void* q, void* kv_cache, void* o, void* softmax_lse,
+                     void* block_table, int32_t block_table_stride, void* cache_seqlens,
+                     int32_t seqlen_q, int32_t max_seqlen_k, int32_t batch_size,
+                     int32_t num_heads, int32_t head_size, int32_t head_size_v,
+                     int32_t page_block_size, const int64_t* strides /* q then o: batch,row,head */,
+                     float softmax_scale, int window_size_left, int window_size_right,
+                     int32_t num_splits, bool is_fp16, hipStream_t stream);
 
 #ifdef __cplusplus
 } /* extern "C" */

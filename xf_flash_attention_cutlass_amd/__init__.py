@@ -43,6 +43,7 @@ from .interface import (  # noqa: E402
     flash_attn_varlen_func,
     flash_attn_varlen_kvpacked_func,
     flash_attn_with_kvcache,
+    flash_mla_with_kvcache,
     merge_attn_states,
     quantize_fp8,
 )
@@ -57,6 +58,7 @@ __all__ = [
     "flash_attn_varlen_fp8_func",
     "flash_attn_varlen_kvpacked_func",
     "flash_attn_with_kvcache",
+    "flash_mla_with_kvcache",
     "quantize_fp8",
     "merge_attn_states",
     "ring_attention",

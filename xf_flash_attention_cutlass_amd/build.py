@@ -84,6 +84,11 @@ def build_lib(jobs: int = 8, force: bool = False, verbose: bool = False, variant
     todo.append((os.path.join(CSRC, "fmha_append.hip"), os.path.join(OBJ, "fmha_append.o"), []))
     todo.append((os.path.join(CSRC, "fmha_quant.hip"), os.path.join(OBJ, "fmha_quant.o"), []))
     todo.append((os.path.join(CSRC, "fmha_merge.hip"), os.path.join(OBJ, "fmha_merge.o"), []))
+    # the MLA decode keeps its 128 accumulator registers in the architectural half of the unified
+    # file (VGPR-form MFMAs): with them in the accumulator half the rescale copies all of them
+    # over every tile and the kernel spills
+    todo.append((os.path.join(CSRC, "fmha_mla.hip"), os.path.join(OBJ, "fmha_mla.o"),
+                 ["-mllvm", "-amdgpu-mfma-vgpr-form"]))
     todo.append((os.path.join(CSRC, "fmha_fwd_fp8.hip"), os.path.join(OBJ, "fmha_fwd_fp8.o"), []))
     todo.append((os.path.join(CSRC, "fmha_api.cpp"), os.path.join(OBJ, "fmha_api.o"), []))
     if variants:

@@ -65,6 +65,8 @@ _SIGS = {
     "fmha_bwd_sink": [vp, vp, vp, vp, i32, i32, i32, C.c_int64, C.c_int64, vp],
     "fmha_merge_states": [C.POINTER(vp), C.POINTER(vp), i32, vp, vp, vp, i32, i32, i32, i32,
                           C.POINTER(C.c_int64), b_, vp],
+    "fmha_mla_decode": [vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32,
+                        C.POINTER(C.c_int64), f32, C.c_int, C.c_int, i32, b_, vp],
     "fmha_last_error": [],
     "fmha_last_status": [],
     "fmha_last_num_splits": [],

@@ -521,7 +521,7 @@ const char* fmha_last_error(void) { return g_err.c_str(); }
 int fmha_last_status(void) { return g_status; }
 int fmha_last_num_splits(void) { return g_last_splits; }
 const char* fmha_last_kernel(void) { return g_last_kernel; }
-const char* fmha_version(void) { return XFA_VARIANTS ? "xf-fmha-gfx950 2.8 (variants)" : "xf-fmha-gfx950 2.8"; }
+const char* fmha_version(void) { return XFA_VARIANTS ? "xf-fmha-gfx950 2.9 (variants)" : "xf-fmha-gfx950 2.9"; }
 
 void fmha_set_rng_state(uint64_t seed, uint64_t offset) {
     g_seed = seed;
@@ -1415,6 +1415,88 @@ void fmha_merge_states(const void* const* o_parts, const float* const* lse_parts
         hip_ok(launch_merge_states(p, is_fp16, stream), "merge launch");
     } catch (...) {
         fail(9, "internal error in fmha_merge_states");
+    }
+}
+
+void fmha_mla_decode(void* q, void* kv_cache, void* o, void* softmax_lse, void* block_table,
+                     int32_t block_table_stride, void* cache_seqlens, int32_t seqlen_q,
+                     int32_t max_seqlen_k, int32_t batch_size, int32_t num_heads, int32_t head_size,
+                     int32_t head_size_v, int32_t page_block_size, const int64_t* strides,
+                     float softmax_scale, int window_size_left, int window_size_right,
+                     int32_t num_splits, bool is_fp16, hipStream_t stream) {
+    try {
+        begin_fwd();
+        REQUIRE(q && kv_cache && o, "q, kv_cache and o must be non-null device pointers");
+        REQUIRE(block_table, "MLA decode reads the latent cache through a block_table: it must be non-null");
+        REQUIRE(cache_seqlens, "cache_seqlens must be a non-null device pointer (int32 [batch])");
+        REQUIRE(strides, "strides must be a non-null pointer (q then o: batch, row, head)");
+        REQUIRE(head_size == 576 && head_size_v == 512,
+                "MLA decode supports (head_size, head_size_v) = (576, 512) only (got (%d, %d))", head_size,
+                head_size_v);
+        REQUIRE(page_block_size > 0 && page_block_size % 16 == 0,
+                "page_block_size must be a positive multiple of 16 (got %d)", page_block_size);
+        REQUIRE(window_size_left < 0 && (window_size_right < 0 || window_size_right == 0),
+                "MLA decode supports the windows (-1, -1) and (-1, 0) (causal) only (got (%d, %d))",
+                window_size_left, window_size_right);
+        REQUIRE(num_heads >= 1 && seqlen_q >= 1,
+                "num_heads and seqlen_q must be at least 1 (got %d, %d)", num_heads, seqlen_q);
+        REQUIRE(batch_size >= 0, "batch size must be non-negative (got %d)", batch_size);
+        REQUIRE(num_splits <= 128, "num_splits must be at most 128 (got %d)", num_splits);
+        REQUIRE(block_table_stride >= 1 && max_seqlen_k >= 0 &&
+                    (int64_t)max_seqlen_k <= (int64_t)block_table_stride * page_block_size,
+                "max_seqlen_k must lie in [0, block_table_stride * page_block_size] (got %d, table %d x page %d)",
+                max_seqlen_k, block_table_stride, page_block_size);
+        const int ext[3] = {batch_size, seqlen_q, num_heads};
+        for (int i = 0; i < 6; ++i)
+            REQUIRE(strides[i] >= 0 && (ext[i % 3] <= 1 || strides[i] % 8 == 0) &&
+                        (i < 3 || ext[i % 3] <= 1 || strides[i] > 0),
+                    "strides must be non-negative multiples of 8 elements (16 bytes), the output's "
+                    "positive: stride %d is %lld", i, (long long)strides[i]);
+        REQUIRE(!((((uintptr_t)q) | ((uintptr_t)kv_cache) | ((uintptr_t)o)) & 15),
+                "q, kv_cache and o must be 16-byte aligned device pointers");
+        REQUIRE(!((((uintptr_t)block_table) | ((uintptr_t)cache_seqlens) | ((uintptr_t)softmax_lse)) & 3),
+                "block_table, cache_seqlens and softmax_lse must be 4-byte aligned device pointers");
+        if (!slab_ok("kv_cache page", page_block_size, 576, 2)) return;
+        REQUIRE((int64_t)seqlen_q * num_heads <= 0x7fffffffLL / 16 &&
+                    (int64_t)batch_size * 128 * (((int64_t)seqlen_q * num_heads + 15) / 16) <= 0x7fffffffLL,
+                "batch_size * seqlen_q * num_heads = %lld is more than one launch covers",
+                (long long)batch_size * seqlen_q * num_heads);
+        if (batch_size == 0) return;
+        MlaParams p{};
+        p.q = q; p.kv = kv_cache; p.o = o; p.lse = (float*)softmax_lse;
+        p.block_table = (const int*)block_table; p.cache_seqlens = (const int*)cache_seqlens;
+        p.q_batch = strides[0]; p.q_row = strides[1]; p.q_head = strides[2];
+        p.o_batch = strides[3]; p.o_row = strides[4]; p.o_head = strides[5];
+        p.bt_stride = block_table_stride; p.page_size = page_block_size; p.max_seqlen_k = max_seqlen_k;
+        p.b = batch_size; p.h = num_heads; p.seqlen_q = seqlen_q;
+        p.row_tiles = (seqlen_q * num_heads + 15) / 16;
+        p.causal = window_size_right == 0;
+        p.scale_log2 = softmax_scale * kLog2e;
+        p.device = current_device();
+        p.num_cus = num_cus(p.device);
+        // Splits: one workgroup (4 waves = 4 items, one per SIMD; its images fill the LDS) per CU
+        // over all (batch, row tile, split) items, at most the key tiles and 128
+        const int tiles = std::max(1, (max_seqlen_k + 31) / 32);
+        int splits = num_splits;
+        if (splits <= 0) {
+            const int64_t units = (int64_t)batch_size * p.row_tiles;
+            splits = (int)std::min<int64_t>(128, (4LL * p.num_cus + units - 1) / units);
+        }
+        splits = std::max(1, std::min(splits, std::min(tiles, 128)));
+        p.num_splits = splits;
+        g_last_splits = splits;
+        if (splits > 1) {
+            const size_t rows = (size_t)batch_size * num_heads * seqlen_q;
+            const size_t obytes = (size_t)splits * rows * 512 * sizeof(float);
+            const size_t lbytes = (size_t)splits * rows * sizeof(float);
+            char* base = (char*)pool_get(stream, obytes + lbytes);
+            if (!base) { fail(3, "could not allocate %zu bytes of split scratch", obytes + lbytes); return; }
+            p.oaccum = (float*)base;
+            p.lseaccum = (float*)(base + obytes);
+        }
+        hip_ok(launch_mla_decode(p, is_fp16, stream), "MLA decode launch");
+    } catch (...) {
+        fail(9, "internal error in fmha_mla_decode");
     }
 }
 

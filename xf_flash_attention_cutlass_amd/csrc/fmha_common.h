@@ -231,6 +231,28 @@ struct CombineParams {
     const float* sink;   // attention sink [h] merged after the splits, or null
 };
 
+// MLA decode over a paged latent cache (fmha_mla_decode_kernel.h): one kv head, K = the 576-wide
+// row, V = its first 512 features; strides in elements, LSE contiguous [b, h, seqlen_q].
+struct MlaParams {
+    const void* q;
+    const void* kv;            // [num_blocks, page_size, 1, 576], contiguous
+    void* o;
+    float* lse;                // [b, h, seqlen_q] or null
+    float* oaccum;             // split scratch [splits][b][h][seqlen_q][512] fp32
+    float* lseaccum;           // split scratch [splits][b][h][seqlen_q] fp32
+    const int* block_table;
+    const int* cache_seqlens;
+    int64_t q_batch, q_row, q_head;
+    int64_t o_batch, o_row, o_head;
+    int bt_stride, page_size, max_seqlen_k;
+    int b, h, seqlen_q;
+    int row_tiles;             // ceil(seqlen_q * h / 16)
+    int num_splits;
+    int causal;
+    float scale_log2;
+    int num_cus, device;
+};
+
 struct BwdParams {
     const void* q; const void* k; const void* v; const void* o; const void* dout;
     const float* lse;

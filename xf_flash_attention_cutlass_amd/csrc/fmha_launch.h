@@ -262,6 +262,10 @@ struct MergeParams {
 };
 hipError_t launch_merge_states(const MergeParams& p, bool fp16, hipStream_t st);
 
+// MLA decode over a paged latent cache (fmha_mla.hip): the decode kernel and, for
+// p.num_splits > 1, the split combine at head size 512
+hipError_t launch_mla_decode(const MlaParams& p, bool fp16, hipStream_t st);
+
 // D = 256 (bucket of 129..256): 4 waves x 32 rows, one wave per SIMD (512 registers:
 // Q fragments and the O accumulator alone are 192), no LDS-DMA pipeline
 inline int fwd_block_m(int d, int waves) { return d > 128 ? 128 : waves * 32; }

@@ -1,0 +1,40 @@
+// fmha_mla.hip — MLA decode over a paged latent cache (fmha_mla_decode): the decode kernel
+// (fmha_mla_decode_kernel.h) for bf16 and fp16, and the split combine at head size 512
+// (fmha_combine_kernel<512, T>, the forward's template, instantiated here).  A translation unit of
+// its own: the kernel runs one wave per SIMD with 147,456 B of LDS, unlike anything in fmha_fwd.hip.
+#include "fmha_fwd_kernel.h"
+#include "fmha_mla_decode_kernel.h"
+#include "fmha_launch.h"
+
+namespace xfa {
+
+template <typename T>
+static hipError_t launch_mla_t(const MlaParams& p, hipStream_t st) {
+    allow_lds<fmha_mla_decode_kernel<T>>(p.device, kMlaSmem);
+    const int64_t items = (int64_t)p.b * p.num_splits * p.row_tiles;
+    const dim3 grid((unsigned)((items + kMlaWaves - 1) / kMlaWaves));
+    // the mapping: the waves of a workgroup are row tiles of one (batch, split), or key splits
+    note_launch(p.row_tiles > 1 ? "fmha_mla_decode_kernel<tiles>" : "fmha_mla_decode_kernel<splits>", 0, 0,
+                grid.x, grid.y, grid.z, kMlaWaves * 64);
+    hipLaunchKernelGGL((fmha_mla_decode_kernel<T>), grid, dim3(kMlaWaves * 64), kMlaSmem, st, p);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess || p.num_splits <= 1) return e;
+    CombineParams cp{};
+    cp.oaccum = p.oaccum;
+    cp.lseaccum = p.lseaccum;
+    cp.o = p.o;
+    cp.lse = p.lse;
+    cp.o_batch = p.o_batch; cp.o_row = p.o_row; cp.o_head = p.o_head;
+    cp.lse_batch = (int64_t)p.h * p.seqlen_q; cp.lse_head = p.seqlen_q;
+    cp.b = p.b; cp.h = p.h; cp.seqlen_q = p.seqlen_q; cp.d = kMlaDV; cp.hd = kMlaDV;
+    cp.num_splits = p.num_splits;
+    const int64_t crow = (int64_t)p.b * p.h * p.seqlen_q;
+    hipLaunchKernelGGL((fmha_combine_kernel<kMlaDV, T>), dim3((unsigned)((crow + 3) / 4)), dim3(256), 0, st, cp);
+    return hipGetLastError();
+}
+
+hipError_t launch_mla_decode(const MlaParams& p, bool fp16, hipStream_t st) {
+    return fp16 ? launch_mla_t<_Float16>(p, st) : launch_mla_t<__bf16>(p, st);
+}
+
+}  // namespace xfa

@@ -1069,6 +1069,76 @@ mha_kvcache_append_fp8(const at::Tensor& q, at::Tensor& kcache, at::Tensor& vcac
     return {seqlens_new, q_rot.defined() ? q_rot : qc};
 }
 
+namespace {
+
+// ---- `mla_decode`: q [batch, seqlen_q, heads, 576], fp16 or bf16, by its own strides ...
+void check_mla_q(const at::Tensor& q) {
+    TORCH_CHECK(q.dtype() == torch::kFloat16 || q.dtype() == torch::kBFloat16, "q must be fp16 or bf16");
+    CHECK_DEVICE(q);
+    TORCH_CHECK(q.dim() == 4, "q must be ", kDense);
+    TORCH_CHECK(q.size(3) == 576, "mla_decode takes head_size 576 (512 latent + 64 rotary features), got ", q.size(3));
+    TORCH_CHECK(q.size(1) >= 1 && q.size(2) >= 1, "q must have at least one row and one head");
+    TORCH_CHECK(q.stride(-1) == 1, "q must have contiguous last dimension");
+    TORCH_CHECK(aligned16(q), "q must be 16-byte aligned with strides that are multiples of 16 bytes");
+}
+
+// ... the latent cache [num_blocks, page, 1, 576] of q's dtype, contiguous ...
+void check_mla_cache(const at::Tensor& kv_cache, const at::Tensor& q) {
+    TORCH_CHECK(kv_cache.dtype() == q.dtype(), "kv_cache must have the dtype of q");
+    TORCH_CHECK(kv_cache.is_cuda() && kv_cache.device() == q.device(), "kv_cache must be on q's device");
+    TORCH_CHECK(kv_cache.dim() == 4 && kv_cache.size(2) == 1 && kv_cache.size(3) == 576,
+                "kv_cache must be (num_blocks, page_block_size, 1, 576)");
+    CHECK_CONTIGUOUS(kv_cache);
+    TORCH_CHECK(kv_cache.size(1) % 16 == 0, "page_block_size must be a multiple of 16");
+    TORCH_CHECK(aligned16(kv_cache), "kv_cache must be 16-byte aligned");
+}
+
+// ... and an output: the caller's (written in place by its own strides) or a new contiguous one
+at::Tensor take_mla_out(const OptTensor& out_, const at::Tensor& q, int head_size_v) {
+    const std::vector<int64_t> shape = {q.size(0), q.size(1), q.size(2), head_size_v};
+    if (!out_.has_value()) return torch::empty(shape, q.options());
+    const at::Tensor& out = out_.value();
+    TORCH_CHECK(out.dtype() == q.dtype(), "Output must have the same dtype as inputs");
+    TORCH_CHECK(out.is_cuda() && out.device() == q.device(), "out must be on q's device");
+    TORCH_CHECK(out.sizes() == at::IntArrayRef(shape), "out must have shape ", at::IntArrayRef(shape));
+    TORCH_CHECK(out.stride(-1) == 1, "Output tensor must have contiguous last dimension");
+    TORCH_CHECK(aligned16(out), "out must be 16-byte aligned with strides that are multiples of 16 bytes");
+    return out;
+}
+
+}  // namespace
+
+// MLA decode over a paged latent cache (fmha_mla_decode): q and out go by their own strides,
+// nothing is copied.  Returns {out [batch, seqlen_q, heads, 512], softmax_lse [batch, heads, seqlen_q]}.
+std::vector<at::Tensor>
+mha_mla_decode(const at::Tensor& q, const at::Tensor& kv_cache, const at::Tensor& block_table,
+               const at::Tensor& cache_seqlens, const int head_dim_v, const float softmax_scale,
+               const bool is_causal, const int num_splits, const OptTensor& out_) {
+    check_mla_q(q);
+    check_mla_cache(kv_cache, q);
+    TORCH_CHECK(head_dim_v == 512, "mla_decode takes head_dim_v 512, got ", head_dim_v);
+    const int batch = q.size(0), seqlen_q = q.size(1), heads = q.size(2);
+    TORCH_CHECK(block_table.dim() == 2, "block_table must be (batch_size, max_num_blocks_per_seq)");
+    check_block_table(block_table, batch);
+    check_batch_int32(cache_seqlens, batch, "cache_seqlens");
+    TORCH_CHECK(block_table.device() == q.device() && cache_seqlens.device() == q.device(),
+                "block_table and cache_seqlens must be on q's device");
+    TORCH_CHECK(num_splits <= 128, "num_splits must be at most 128");
+    at::Tensor out = take_mla_out(out_, q, head_dim_v);
+    at::Tensor lse = torch::empty({batch, heads, seqlen_q}, q.options().dtype(torch::kFloat32));
+    if (batch == 0) return {out, lse};
+    const c10::DeviceGuard device_guard(q.device());
+    const int page = kv_cache.size(1);
+    const int64_t st[6] = {q.stride(0), q.stride(1), q.stride(2), out.stride(0), out.stride(1), out.stride(2)};
+    fmha_mla_decode(q.data_ptr(), kv_cache.data_ptr(), out.data_ptr(), lse.data_ptr(), block_table.data_ptr(),
+                    (int)block_table.stride(0), cache_seqlens.data_ptr(), seqlen_q,
+                    (int)std::min<int64_t>(block_table.size(1) * (int64_t)page, 0x7fffffff), batch, heads, 576,
+                    head_dim_v, page, st, softmax_scale, -1, is_causal ? 0 : -1, num_splits,
+                    q.dtype() == torch::kFloat16, cur_stream());
+    raise_if_failed("mla_decode");
+    return {out, lse};
+}
+
 PYBIND11_MODULE(paged_attn, m) {
     m.doc() = "FlashAttention for MI355X (gfx950): hand-written HIP kernels behind the paged_attn C ABI";
     m.def("fwd", without_sink(&mha_fwd), "Forward pass");
@@ -1106,9 +1176,15 @@ PYBIND11_MODULE(paged_attn, m) {
     m.def("_merge_states", &mha_merge_states, "Merge partial attention states (O_i, LSE_i) into one (O, LSE)",
           py::arg("o_parts"), py::arg("lse_parts"), py::arg("sink") = py::none(), py::arg("packed") = false,
           py::arg("out") = py::none(), py::arg("lse_out") = py::none());
+    // `mla_decode` likewise: bound as `_mla_decode`, reached as `paged_attn.mla_decode`
+    m.def("_mla_decode", &mha_mla_decode, "MLA decode over a paged latent KV cache (d_qk 576, d_v 512)",
+          py::arg("q"), py::arg("kv_cache"), py::arg("block_table"), py::arg("cache_seqlens"),
+          py::arg("head_dim_v") = 512, py::arg("softmax_scale") = 0.041666666666666664f,
+          py::arg("is_causal") = false, py::arg("num_splits") = 0, py::arg("out") = py::none());
     const py::handle self = m;
     m.def("__getattr__", [self](const std::string& name) -> py::object {
         if (name == "merge_states") return self.attr("_merge_states");
+        if (name == "mla_decode") return self.attr("_mla_decode");
         PyErr_SetString(PyExc_AttributeError, ("module 'paged_attn' has no attribute '" + name + "'").c_str());
         throw py::error_already_set();
     });

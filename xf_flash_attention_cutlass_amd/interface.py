@@ -139,6 +139,31 @@ def merge_attn_states(outs, lses, *, sink=None, packed=False, out=None, lse_out=
     return o, lse
 
 
+def flash_mla_with_kvcache(q, kv_cache, block_table, cache_seqlens, head_dim_v=512,
+                           softmax_scale=None, causal=False, num_splits=0, out=None):
+    """Decode attention for multi-head latent attention (DeepSeek-V2/V3/R1, Kimi) in its absorbed
+    form, over a paged latent KV cache: one HIP launch (`paged_attn.mla_decode`) plus the split
+    combine, no copies.
+
+    q: [b, seqlen_q, h, 576] bf16 or fp16 (a view is fine: last dimension contiguous, 16-byte
+    aligned); kv_cache: [num_blocks, page_block_size, 1, 576] contiguous, page_block_size a
+    multiple of 16; block_table: int32 [b, max_blocks_per_seq]; cache_seqlens: int32 [b].
+    Every head attends over the one shared 576-wide latent row per token (512 compressed-KV
+    features + 64 rotary features); the value is its first head_dim_v = 512 features.
+    softmax_scale defaults to q.shape[-1] ** -0.5 (pass the model's own: DeepSeek's is not that);
+    causal is bottom-right aligned, as in `flash_attn_with_kvcache`.  A row without a visible key
+    gives out = 0 and softmax_lse = +inf.  num_splits: 0 chooses, 1 forces a single pass.
+
+    Returns (out [b, seqlen_q, h, 512], softmax_lse fp32 [b, h, seqlen_q]).  Not differentiable."""
+    if softmax_scale is None:
+        softmax_scale = q.shape[-1] ** (-0.5)
+    with torch.no_grad():
+        o, lse = paged_attn.mla_decode(q.detach(), kv_cache.detach(), block_table, cache_seqlens,
+                                       int(head_dim_v), float(softmax_scale), bool(causal),
+                                       int(num_splits), out)
+    return o, lse
+
+
 _GRANULARITY = {"tensor": 0, "head": 1}
 
 
