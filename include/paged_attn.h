@@ -127,7 +127,7 @@ void fmha_set_rng_state(uint64_t seed, uint64_t offset);
 void fmha_set_rng_state_device(const int64_t* seed_ptr, const int64_t* offset_ptr,
                                uint64_t offset_add, int64_t* rng_out);
 
-/* Library version / build identification, e.g. "xf-fmha-gfx950 2.9".  2.0 (round 3) changed
+/* Library version / build identification, e.g. "xf-fmha-gfx950 2.10".  2.0 (round 3) changed
  * argument lists of existing symbols; 2.1 exports those under _v2 names (see INTEGRATION.md
  * "ABI history"). */
 const char* fmha_version(void);
@@ -495,6 +495,53 @@ void fmha_mla_decode(void* q, void* kv_cache, void* o, void* softmax_lse,
                      int32_t page_block_size, const int64_t* strides /* q then o: batch,row,head */,
                      float softmax_scale, int window_size_left, int window_size_right,
                      int32_t num_splits, bool is_fp16, hipStream_t stream);
+
+/* ------------------------------------- MLA decode over an fp8 latent cache, its append (2.10) */
+
+/* The fp8 latent cache (FlashMLA's fp8 KV cache, vLLM's fp8_ds_mla): kv_cache8 holds BYTES
+ * [num_blocks, page_block_size, 1, 656], contiguous, page_block_size % 16 == 0, 0.569 of the
+ * 16-bit row.  The row of one token:
+ *   bytes   0 .. 511   latent features 0 .. 511, OCP e4m3fn
+ *   bytes 512 .. 527   four fp32 descales; descale j belongs to features 128 j .. 128 j + 127
+ *   bytes 528 .. 655   rotary features 512 .. 575 in q's dtype (bf16, or fp16 for an fp16 call),
+ *                      not quantised
+ * The operand the kernel attends over: feature i < 512 is T(float(e4m3[i]) * descale[i / 128]) -
+ * one fp32 product, rounded once to q's dtype T (FlashMLA's own dequantisation) - and features
+ * 512 .. 575 are the stored 16-bit values.  With K (n x 576) so defined and V = K[:, :512],
+ * fmha_mla_decode_fp8 is fmha_mla_decode word for word: S over all 576 features, the windows
+ * (-1, -1) and (-1, 0), the empty-row rule, max_seqlen_k and the automatic split count, the LSE
+ * layout, the strides, the scratch pool and graph capturability, every check and refusal (the
+ * page slab judged at 656 bytes a row), fmha_last_num_splits().  fmha_last_kernel() names
+ * fmha_mla_decode_fp8_kernel<tiles> or <splits>.  (The scales are applied to the operands, not to
+ * S and O as the fp8 paged decode does: a scale per (key, 128 features) does not factor out of
+ * O after the PV product.) */
+void fmha_mla_decode_fp8(void* q, void* kv_cache8, void* o, void* softmax_lse,
+                         void* block_table, int32_t block_table_stride, void* cache_seqlens,
+                         int32_t seqlen_q, int32_t max_seqlen_k, int32_t batch_size,
+                         int32_t num_heads, int32_t head_size /* 576 */, int32_t head_size_v /* 512 */,
+                         int32_t page_block_size, const int64_t* strides /* q then o: batch,row,head */,
+                         float softmax_scale, int window_size_left, int window_size_right,
+                         int32_t num_splits, bool is_fp16, hipStream_t stream);
+
+/* Append tokens to the fp8 latent cache: one launch, one pass, no scratch, no host sync
+ * (capturable in a graph).
+ *   latent [num_tokens, 512] and k_pe [num_tokens, 64] in bf16 (fp16 for is_fp16), each by its own
+ *          row stride in ELEMENTS (two views of one 576-wide tensor are the common case); k_pe
+ *          arrives rotated and is copied
+ *   slot_mapping int64 [num_tokens]: slot = block * page_block_size + row (vLLM's
+ *          concat_and_cache_mla convention).  A negative slot, or one >= num_blocks *
+ *          page_block_size, writes nothing; a row is written whole (656 bytes) or not at all.
+ * The quantiser, for each 128-feature group of a row (fmha_quantize_fp8's words at a finer
+ * grain): amax = max |float(x)|; descale = amax / 448.0f, and 1.0f when amax == 0; byte = e4m3fn
+ * round-to-nearest-even of clamp(float(x) * (1.0f / descale), -448, 448).
+ * num_tokens == 0 launches nothing and succeeds.  Refused with an error, the cache untouched: a
+ * NULL pointer, a row stride that is negative or no multiple of 8, latent / k_pe / kv_cache8 not
+ * 16-byte aligned or slot_mapping not 8-byte aligned, a page size that is no multiple of 16, a
+ * negative count. */
+void fmha_mla_cache_append_fp8(const void* latent, int64_t latent_row_stride, const void* k_pe,
+                               int64_t k_pe_row_stride, void* kv_cache8, const void* slot_mapping,
+                               int32_t num_tokens, int32_t num_blocks, int32_t page_block_size,
+                               bool is_fp16, hipStream_t stream);
 
 #ifdef __cplusplus
 } /* extern "C" */

@@ -29,7 +29,9 @@ def units(tree):
             [f"-DXFA_HD={hd}", f"-DXFA_DTN={dt}", f"-DXFA_DT_BF16={int(dt == 'bf16')}"])
            for hd, dt in b.VARIANTS for kind in ("fwd", "bwd")]
     tus += [("fmha_append", "fmha_append.hip", []), ("fmha_quant", "fmha_quant.hip", []),
-            ("fmha_fwd_fp8", "fmha_fwd_fp8.hip", []), ("fmha_api", "fmha_api.cpp", [])]
+            ("fmha_fwd_fp8", "fmha_fwd_fp8.hip", []), ("fmha_api", "fmha_api.cpp", []),
+            ("fmha_merge", "fmha_merge.hip", []),
+            ("fmha_mla", "fmha_mla.hip", ["-mllvm", "-amdgpu-mfma-vgpr-form"])]   # (build.py's flag)
     tus += [(n + "+variants", src, d + ["-DXFA_VARIANTS=1"]) for n, src, d in tus if n + ".o" in b.VARIANT_TUS]
     return b, tus
 

@@ -3,7 +3,12 @@ fmha_mla_decode_kernel launch plus the split combine) against the same attention
 torch eager ops over the gathered cache, at several split counts.
 
   python tools/mla_ab.py [--b 8] [--s 32768] [--page 64] [--heads 16 128] [--splits 0 ...]
-                         [--rounds 7] [--iters 20]
+                         [--rounds 7] [--iters 20] [--fp8] [--append 8192]
+
+--fp8 adds the fp8-cache call (fmha_mla_decode_fp8_kernel over rows of 656 bytes, the same tokens
+appended with mla_cache_append_fp8) as a contender of every split count, next to the 16-bit-cache
+call of the same build, and an eager contender over the dequantised gathered cache; its bytes are
+n * 656 + q + o.  --append N times the append kernel alone on N tokens (bytes read + written).
 
 Per head count (seqlen_q = 1, bf16, uniform lengths):
   bytes = sum n * 1152 (every cache row once) + q + o;  rate in TB/s against the 6.29 TB/s a
@@ -53,24 +58,41 @@ def measure(a, heads):
     out = torch.empty(b, 1, heads, DV, device="cuda", dtype=dt)
     kg = kv[table.long()].reshape(b, s, D)
     scale = D ** -0.5
-    nbytes = b * s * D * 2 + q.numel() * 2 + out.numel() * 2
+    qo = q.numel() * 2 + out.numel() * 2
+    nbytes = {"": b * s * D * 2 + qo}
     flop = 2.0 * b * heads * s * (D + DV)
 
-    def mla(ns):
-        return lambda: xfa.flash_mla_with_kvcache(q, kv, table, lens, num_splits=ns, out=out)
+    def mla(cache, ns):
+        return lambda: xfa.flash_mla_with_kvcache(q, cache, table, lens, num_splits=ns, out=out)
 
+    caches, refs = {"mla_decode": kv}, {"mla_decode": eager(q, kg, scale)}
+    if a.fp8:
+        # the same tokens in an fp8 cache, written by the append kernel through the same table
+        kv8 = torch.zeros(b * per, page, 1, xfa.mla_fp8_cache_row_bytes, device="cuda", dtype=torch.uint8)
+        flat = kv.view(-1, D)
+        xfa.mla_cache_append_fp8(flat[:, :DV], flat[:, DV:], kv8, torch.arange(flat.shape[0], device="cuda"))
+        r8 = kv8.view(-1, xfa.mla_fp8_cache_row_bytes)
+        ds = r8[:, 512:528].contiguous().view(torch.float32).repeat_interleave(128, dim=1)
+        lat = (r8[:, :DV].contiguous().view(torch.float8_e4m3fn).float() * ds).to(dt)
+        kdq = torch.cat([lat, r8[:, 528:].contiguous().view(dt)], 1).view(b * per, page, D)
+        kg8 = kdq[table.long()].reshape(b, s, D)
+        caches["mla_decode_fp8"], refs["mla_decode_fp8"] = kv8, eager(q, kg8, scale)
+        nbytes["fp8"] = b * s * xfa.mla_fp8_cache_row_bytes + qo
+        del r8, ds, lat, kdq
     runs, kern = {}, {}
-    ref = eager(q, kg, scale)
     for ns in a.splits:
-        name = f"mla_decode num_splits={ns}"
-        runs[name] = mla(ns)
-        out.zero_()
-        runs[name]()
-        torch.cuda.synchronize()
-        kern[name] = "%s splits=%d" % (capi.lib().fmha_last_kernel().decode(), capi.lib().fmha_last_num_splits())
-        print(f"check {name}: max|o - eager| {(out.float() - ref.float()).abs().max().item():.3e}  [{kern[name]}]")
+        for op, cache in caches.items():
+            name = f"{op} num_splits={ns}"
+            runs[name] = mla(cache, ns)
+            out.zero_()
+            runs[name]()
+            torch.cuda.synchronize()
+            kern[name] = "%s splits=%d" % (capi.lib().fmha_last_kernel().decode(), capi.lib().fmha_last_num_splits())
+            print(f"check {name}: max|o - eager| {(out.float() - refs[op].float()).abs().max().item():.3e}  [{kern[name]}]")
     runs["torch eager (gathered cache)"] = lambda: eager(q, kg, scale)
-    del ref
+    if a.fp8:
+        runs["torch eager (dequantised gathered cache)"] = lambda: eager(q, kg8, scale)
+    del refs
 
     for run in runs.values():
         for _ in range(3):
@@ -98,16 +120,47 @@ def measure(a, heads):
             s1.record()
             torch.cuda.synchronize()
             times[name].append(s0.elapsed_time(s1) / a.iters)
-    print(f"MLA decode b={b} s_kv={s} page={page} heads={heads} seqlen_q=1 bf16: {nbytes / 1e6:.1f} MB, "
-          f"{flop / 1e9:.1f} GFLOP per call")
+    print(f"MLA decode b={b} s_kv={s} page={page} heads={heads} seqlen_q=1 bf16: {nbytes[''] / 1e6:.1f} MB "
+          + (f"(fp8 cache {nbytes['fp8'] / 1e6:.1f} MB), " if a.fp8 else "") + f"{flop / 1e9:.1f} GFLOP per call")
     for name, t in times.items():
         med = statistics.median(t)
-        tbs, pf = nbytes / med / 1e9, flop / med / 1e12
+        nb = nbytes["fp8" if name.startswith("mla_decode_fp8") else ""]     # bytes the call actually reads
+        tbs, pf = nb / med / 1e9, flop / med / 1e12
         print(f"{name}: median {med * 1e3:.1f} us  min {min(t) * 1e3:.1f}  max {max(t) * 1e3:.1f}  -> "
               f"{tbs:.2f} TB/s = {tbs / STREAM_TBS:.2f} of {STREAM_TBS} TB/s;  {pf:.3f} PFLOP/s = "
               f"{pf / PEAK_PFLOPS:.2f} of {PEAK_PFLOPS} PFLOP/s")
-    del kv, kg
+    del kv, kg, caches
     torch.cuda.empty_cache()
+
+
+def measure_append(a):
+    """The append kernel alone: `a.append` tokens (two views of one 576-wide tensor) into an fp8
+    cache through a shuffled slot_mapping; bytes = tokens * (1152 read + 8 slot + 656 written)."""
+    import xf_flash_attention_cutlass_amd as xfa
+    n, page = a.append, a.page
+    blocks = (n + page - 1) // page
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    x = torch.randn(n, D, device="cuda", dtype=torch.bfloat16, generator=gen)
+    slots = torch.randperm(blocks * page, device="cuda", generator=gen)[:n].contiguous()
+    kv8 = torch.zeros(blocks, page, 1, xfa.mla_fp8_cache_row_bytes, device="cuda", dtype=torch.uint8)
+    run = lambda: xfa.mla_cache_append_fp8(x[:, :DV], x[:, DV:], kv8, slots)  # noqa: E731
+    for _ in range(20):
+        run()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(a.rounds):
+        s0, s1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s0.record()
+        for _ in range(a.iters):
+            run()
+        s1.record()
+        torch.cuda.synchronize()
+        times.append(s0.elapsed_time(s1) / a.iters)
+    med = statistics.median(times)
+    nb = n * (D * 2 + 8 + xfa.mla_fp8_cache_row_bytes)
+    print(f"mla_cache_append_fp8 tokens={n} page={page}: median {med * 1e3:.1f} us  min {min(times) * 1e3:.1f}  "
+          f"max {max(times) * 1e3:.1f}  -> {nb / 1e6:.1f} MB read + written, {nb / med / 1e9:.2f} TB/s = "
+          f"{nb / med / 1e9 / STREAM_TBS:.2f} of {STREAM_TBS} TB/s (launch-bound at this size: back-to-back calls)")
 
 
 def main():
@@ -120,11 +173,15 @@ def main():
                     help="num_splits values to time (0 = the library's choice)")
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--fp8", action="store_true", help="add the fp8-cache call and its eager contender")
+    ap.add_argument("--append", type=int, default=0, help="also time mla_cache_append_fp8 on this many tokens")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "mla_ab.py measures on the GPU"
     assert a.s % a.page == 0
     for heads in a.heads:
         measure(a, heads)
+    if a.append:
+        measure_append(a)
 
 
 if __name__ == "__main__":

@@ -6,6 +6,11 @@ against the same image without the XOR.  Lane groups and bank functions as tools
 
   python tools/mla_banks.py
 
+The fp8-cache kernel (fmha_mla_decode_fp8_kernel.h) reads the same image with the same
+instructions; its 36 image writes per tile (per 16-row half: 8 latent loads x 2 ds_write_b128, 2
+rotary loads x 1) are checked here too, against the order in which every lane writes its even chunk
+first.  Its descales move with ds_bpermute_b32, which addresses no LDS memory and has no banks.
+
 The 1152-byte pitch is 4.5 bank rows of 256 B: odd rows sit half a bank row on, and the XOR with
 row & 6 (period 8 rows, inside the aligned 8-chunk blocks of a 72-chunk row) spreads the even and
 the odd rows over the eight 16-byte slots of their half.
@@ -51,6 +56,39 @@ def writes(off):
             for h in range(2) for i in range(18)]
 
 
+def writes8(swap):
+    """The fp8 kernel's image writes of a half tile.  Latent load i, lane l: row 2 i + l / 32, latent
+    chunk c = l % 32 -> image chunks 2 c and 2 c + 1, one ds_write_b128 each; swap: lanes with bit 2
+    set write the odd chunk first (the kernel), else every lane the even one.  Rotary load j, lane
+    l: row 8 j + l / 8 -> image chunk 64 + l % 8.  Also checks the kernel's address forms."""
+    out, cover = [], set()
+    for i in range(8):
+        first, second = [], []
+        for l in range(64):
+            r, c, odd = 2 * i + (l >> 5), l & 31, ((l >> 2) & 1 if swap else 0)
+            first.append(mla_off(r, 2 * c + odd))
+            second.append(mla_off(r, 2 * c + 1 - odd))
+            wl = (l >> 5) * PITCH + 16 * ((2 * c + odd) ^ (2 * (i & 3)))        # the kernel's wl[i % 4]
+            assert first[-1] == 2 * i * PITCH + wl and second[-1] == 2 * i * PITCH + (wl ^ 16)
+        cover.update(first + second)
+        out += [cycles(first, W8, 16, 32), cycles(second, W8, 16, 32)]
+    for j in range(2):
+        ad = [mla_off(8 * j + (l >> 3), 64 + (l & 7)) for l in range(64)]
+        for l in range(64):
+            assert ad[l] == 8 * j * PITCH + (l >> 3) * PITCH + 16 * ((64 + (l & 7)) ^ ((l >> 3) & 6))   # wr
+        cover.update(ad)
+        out.append(cycles(ad, W8, 16, 32))
+    assert sorted(cover) == list(range(0, 16 * PITCH, 16))      # every chunk of the 16 rows, once
+    return out
+
+
+def report8():
+    plain, swapped = writes8(False), writes8(True)
+    print(f"fp8 image writes per half tile (18 ds_write_b128): even chunk first {sum(plain) / len(plain):.2f} "
+          f"max {max(plain)};  bit 2 of the lane swaps {sum(swapped) / len(swapped):.2f} max {max(swapped)} (8)")
+    return max(swapped)
+
+
 def report(name, off):
     k, v, w = k_reads(off), v_reads(off), writes(off)
     print(f"{name:8s} K ds_read_b128 {sum(k) / len(k):.2f} max {max(k)} (4 ideal)   V ds_read_b64_tr_b16 "
@@ -78,3 +116,5 @@ if __name__ == "__main__":
             got = vrow * PITCH + 32 * ((dt & 3) ^ ((vrow >> 1) & 3)) + 16 * ((l >> 1) & 1) + 8 * (l & 1) + 128 * (dt >> 2)
             assert want == got
     print("conflict-free: every K read 4 cycles, every V read 2, every write 8; address forms verified")
+    assert report8() == 8
+    print("fp8 kernel: every image write 8 cycles; address forms verified")

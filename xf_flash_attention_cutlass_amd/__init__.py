@@ -45,6 +45,8 @@ from .interface import (  # noqa: E402
     flash_attn_with_kvcache,
     flash_mla_with_kvcache,
     merge_attn_states,
+    mla_cache_append_fp8,
+    mla_fp8_cache_row_bytes,
     quantize_fp8,
 )
 from .sharding import ring_attention, zigzag_gather, zigzag_split  # noqa: E402
@@ -59,6 +61,8 @@ __all__ = [
     "flash_attn_varlen_kvpacked_func",
     "flash_attn_with_kvcache",
     "flash_mla_with_kvcache",
+    "mla_cache_append_fp8",
+    "mla_fp8_cache_row_bytes",
     "quantize_fp8",
     "merge_attn_states",
     "ring_attention",

@@ -521,7 +521,7 @@ const char* fmha_last_error(void) { return g_err.c_str(); }
 int fmha_last_status(void) { return g_status; }
 int fmha_last_num_splits(void) { return g_last_splits; }
 const char* fmha_last_kernel(void) { return g_last_kernel; }
-const char* fmha_version(void) { return XFA_VARIANTS ? "xf-fmha-gfx950 2.9 (variants)" : "xf-fmha-gfx950 2.9"; }
+const char* fmha_version(void) { return XFA_VARIANTS ? "xf-fmha-gfx950 2.10 (variants)" : "xf-fmha-gfx950 2.10"; }
 
 void fmha_set_rng_state(uint64_t seed, uint64_t offset) {
     g_seed = seed;
@@ -1418,12 +1418,19 @@ void fmha_merge_states(const void* const* o_parts, const float* const* lse_parts
     }
 }
 
-void fmha_mla_decode(void* q, void* kv_cache, void* o, void* softmax_lse, void* block_table,
-                     int32_t block_table_stride, void* cache_seqlens, int32_t seqlen_q,
-                     int32_t max_seqlen_k, int32_t batch_size, int32_t num_heads, int32_t head_size,
-                     int32_t head_size_v, int32_t page_block_size, const int64_t* strides,
-                     float softmax_scale, int window_size_left, int window_size_right,
-                     int32_t num_splits, bool is_fp16, hipStream_t stream) {
+}  // extern "C"
+
+namespace {
+
+// The one body of fmha_mla_decode and fmha_mla_decode_fp8: every check, the split rule, the
+// scratch and the launch.  fp8: the cache rows are 656 bytes (512 e4m3, 4 fp32 descales, 64
+// rotary features of q's type) instead of 576 elements of q's type.
+void mla_decode_run(const char* entry, bool fp8, void* q, void* kv_cache, void* o, void* softmax_lse,
+                    void* block_table, int32_t block_table_stride, void* cache_seqlens, int32_t seqlen_q,
+                    int32_t max_seqlen_k, int32_t batch_size, int32_t num_heads, int32_t head_size,
+                    int32_t head_size_v, int32_t page_block_size, const int64_t* strides,
+                    float softmax_scale, int window_size_left, int window_size_right,
+                    int32_t num_splits, bool is_fp16, hipStream_t stream) {
     try {
         begin_fwd();
         REQUIRE(q && kv_cache && o, "q, kv_cache and o must be non-null device pointers");
@@ -1456,7 +1463,7 @@ void fmha_mla_decode(void* q, void* kv_cache, void* o, void* softmax_lse, void* 
                 "q, kv_cache and o must be 16-byte aligned device pointers");
         REQUIRE(!((((uintptr_t)block_table) | ((uintptr_t)cache_seqlens) | ((uintptr_t)softmax_lse)) & 3),
                 "block_table, cache_seqlens and softmax_lse must be 4-byte aligned device pointers");
-        if (!slab_ok("kv_cache page", page_block_size, 576, 2)) return;
+        if (!slab_ok("kv_cache page", page_block_size, fp8 ? 656 : 576, fp8 ? 1 : 2)) return;
         REQUIRE((int64_t)seqlen_q * num_heads <= 0x7fffffffLL / 16 &&
                     (int64_t)batch_size * 128 * (((int64_t)seqlen_q * num_heads + 15) / 16) <= 0x7fffffffLL,
                 "batch_size * seqlen_q * num_heads = %lld is more than one launch covers",
@@ -1494,9 +1501,69 @@ void fmha_mla_decode(void* q, void* kv_cache, void* o, void* softmax_lse, void* 
             p.oaccum = (float*)base;
             p.lseaccum = (float*)(base + obytes);
         }
-        hip_ok(launch_mla_decode(p, is_fp16, stream), "MLA decode launch");
+        hip_ok(fp8 ? launch_mla_decode_fp8(p, is_fp16, stream) : launch_mla_decode(p, is_fp16, stream),
+               "MLA decode launch");
     } catch (...) {
-        fail(9, "internal error in fmha_mla_decode");
+        fail(9, "internal error in %s", entry);
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+void fmha_mla_decode(void* q, void* kv_cache, void* o, void* softmax_lse, void* block_table,
+                     int32_t block_table_stride, void* cache_seqlens, int32_t seqlen_q,
+                     int32_t max_seqlen_k, int32_t batch_size, int32_t num_heads, int32_t head_size,
+                     int32_t head_size_v, int32_t page_block_size, const int64_t* strides,
+                     float softmax_scale, int window_size_left, int window_size_right,
+                     int32_t num_splits, bool is_fp16, hipStream_t stream) {
+    mla_decode_run("fmha_mla_decode", false, q, kv_cache, o, softmax_lse, block_table, block_table_stride,
+                   cache_seqlens, seqlen_q, max_seqlen_k, batch_size, num_heads, head_size, head_size_v,
+                   page_block_size, strides, softmax_scale, window_size_left, window_size_right, num_splits,
+                   is_fp16, stream);
+}
+
+void fmha_mla_decode_fp8(void* q, void* kv_cache8, void* o, void* softmax_lse, void* block_table,
+                         int32_t block_table_stride, void* cache_seqlens, int32_t seqlen_q,
+                         int32_t max_seqlen_k, int32_t batch_size, int32_t num_heads, int32_t head_size,
+                         int32_t head_size_v, int32_t page_block_size, const int64_t* strides,
+                         float softmax_scale, int window_size_left, int window_size_right,
+                         int32_t num_splits, bool is_fp16, hipStream_t stream) {
+    mla_decode_run("fmha_mla_decode_fp8", true, q, kv_cache8, o, softmax_lse, block_table, block_table_stride,
+                   cache_seqlens, seqlen_q, max_seqlen_k, batch_size, num_heads, head_size, head_size_v,
+                   page_block_size, strides, softmax_scale, window_size_left, window_size_right, num_splits,
+                   is_fp16, stream);
+}
+
+void fmha_mla_cache_append_fp8(const void* latent, int64_t latent_row_stride, const void* k_pe,
+                               int64_t k_pe_row_stride, void* kv_cache8, const void* slot_mapping,
+                               int32_t num_tokens, int32_t num_blocks, int32_t page_block_size,
+                               bool is_fp16, hipStream_t stream) {
+    try {
+        clear_error();
+        REQUIRE(latent && k_pe && kv_cache8 && slot_mapping,
+                "latent, k_pe, kv_cache8 and slot_mapping must be non-null device pointers");
+        REQUIRE(num_tokens >= 0 && num_blocks >= 0,
+                "num_tokens and num_blocks must be non-negative (got %d, %d)", num_tokens, num_blocks);
+        REQUIRE(page_block_size > 0 && page_block_size % 16 == 0,
+                "page_block_size must be a positive multiple of 16 (got %d)", page_block_size);
+        REQUIRE(latent_row_stride >= 0 && k_pe_row_stride >= 0 && latent_row_stride % 8 == 0 &&
+                    k_pe_row_stride % 8 == 0,
+                "row strides must be non-negative multiples of 8 elements (16 bytes): got %lld, %lld",
+                (long long)latent_row_stride, (long long)k_pe_row_stride);
+        REQUIRE(!((((uintptr_t)latent) | ((uintptr_t)k_pe) | ((uintptr_t)kv_cache8)) & 15),
+                "latent, k_pe and kv_cache8 must be 16-byte aligned device pointers");
+        REQUIRE(!(((uintptr_t)slot_mapping) & 7), "slot_mapping must be an 8-byte aligned device pointer (int64)");
+        if (num_tokens == 0) return;
+        MlaAppendParams p{};
+        p.latent = latent; p.k_pe = k_pe; p.cache = kv_cache8; p.slot = (const int64_t*)slot_mapping;
+        p.latent_row = latent_row_stride; p.pe_row = k_pe_row_stride;
+        p.slots = (int64_t)num_blocks * page_block_size;
+        p.tokens = num_tokens;
+        hip_ok(launch_mla_append_fp8(p, is_fp16, stream), "MLA cache append launch");
+    } catch (...) {
+        fail(9, "internal error in fmha_mla_cache_append_fp8");
     }
 }
 

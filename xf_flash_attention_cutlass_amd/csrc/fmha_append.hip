@@ -21,6 +21,9 @@
 // An fp8 cache (fmha_kvcache_append_fp8; cache element type uint8_t = OCP e4m3fn bytes): the
 // fp32 value (K after its rotary, V as read) is multiplied by 1 / k_scale or 1 / v_scale,
 // clamped to +-448 and rounded once to e4m3 (no 16-bit step in between), 8 bytes per store.
+//
+// The fp8 latent cache of the MLA decode has an append of its own (fmha_mla_cache_append_fp8,
+// below): rows of 656 bytes with a scale per 128 features, through a slot_mapping.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -176,6 +179,44 @@ hipError_t launch_append(const AppendParams& p, bool fp16, hipStream_t st) {
         if (fp16) hipLaunchKernelGGL((fmha_append_kernel<_Float16, _Float16>), dim3(blocks), dim3(256), 0, st, p);
         else hipLaunchKernelGGL((fmha_append_kernel<__bf16, __bf16>), dim3(blocks), dim3(256), 0, st, p);
     }
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------- fp8 latent cache append
+// fmha_mla_cache_append_fp8: one wave per token, one pass.  Lane l holds latent features 8 l .. +7,
+// so the 16 lanes l / 16 == g hold the 128-feature group g: amax by a butterfly over them,
+// descale = amax / 448 (1 where amax == 0), bytes = e4m3(clamp(x * (1 / descale))) - the words of
+// fmha_quantize_fp8 at a finer grain.  The row (656 bytes: 512 e4m3, 4 fp32 descales, the 64
+// rotary features as they come) is written whole or, for a slot outside the cache, not at all.
+template <typename T>
+__global__ void __launch_bounds__(256) fmha_mla_append_fp8_kernel(const MlaAppendParams p) {
+    typedef __attribute__((ext_vector_type(8))) T T8;
+    const int lane = threadIdx.x & 63;
+    const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (t >= p.tokens) return;
+    const int64_t slot = p.slot[t];
+    if (slot < 0 || slot >= p.slots) return;
+    uint8_t* row = reinterpret_cast<uint8_t*>(p.cache) + slot * 656;
+    float x[8];
+    load8(reinterpret_cast<const T*>(p.latent) + (int64_t)t * p.latent_row + 8 * lane, x);
+    float m = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) m = fmaxf(m, fabsf(x[i]));
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    const float descale = m == 0.f ? 1.f : m / 448.f;
+    store8(row + 8 * lane, x, 1.f / descale);
+    if ((lane & 15) == 0) *reinterpret_cast<float*>(row + 512 + 4 * (lane >> 4)) = descale;
+    if (lane < 8)
+        *reinterpret_cast<T8*>(row + 528 + 16 * lane) =
+            *reinterpret_cast<const T8*>(reinterpret_cast<const T*>(p.k_pe) + (int64_t)t * p.pe_row + 8 * lane);
+}
+
+hipError_t launch_mla_append_fp8(const MlaAppendParams& p, bool fp16, hipStream_t st) {
+    if (p.tokens <= 0) return hipSuccess;
+    const dim3 grid((unsigned)((p.tokens + 3) / 4));
+    if (fp16) hipLaunchKernelGGL(fmha_mla_append_fp8_kernel<_Float16>, grid, dim3(256), 0, st, p);
+    else hipLaunchKernelGGL(fmha_mla_append_fp8_kernel<__bf16>, grid, dim3(256), 0, st, p);
     return hipGetLastError();
 }
 

@@ -235,7 +235,8 @@ struct CombineParams {
 // row, V = its first 512 features; strides in elements, LSE contiguous [b, h, seqlen_q].
 struct MlaParams {
     const void* q;
-    const void* kv;            // [num_blocks, page_size, 1, 576], contiguous
+    const void* kv;            // [num_blocks, page_size, 1, 576], contiguous (the fp8 cache:
+                               // bytes [num_blocks, page_size, 1, 656], fmha_mla_decode_fp8_kernel.h)
     void* o;
     float* lse;                // [b, h, seqlen_q] or null
     float* oaccum;             // split scratch [splits][b][h][seqlen_q][512] fp32

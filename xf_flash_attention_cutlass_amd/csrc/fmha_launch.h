@@ -265,6 +265,22 @@ hipError_t launch_merge_states(const MergeParams& p, bool fp16, hipStream_t st);
 // MLA decode over a paged latent cache (fmha_mla.hip): the decode kernel and, for
 // p.num_splits > 1, the split combine at head size 512
 hipError_t launch_mla_decode(const MlaParams& p, bool fp16, hipStream_t st);
+// ... and over an fp8 latent cache (p.kv: rows of 656 bytes, fmha_mla_decode_fp8_kernel.h)
+hipError_t launch_mla_decode_fp8(const MlaParams& p, bool fp16, hipStream_t st);
+
+// Append to an fp8 latent cache (fmha_append.hip): token t's 512 latent features, quantised per
+// 128-feature group, and its 64 rotary features, copied, into the 656-byte row slot[t] of the
+// cache; row strides in elements.  A slot outside [0, slots) writes nothing.
+struct MlaAppendParams {
+    const void* latent;        // [tokens, 512]
+    const void* k_pe;          // [tokens, 64]
+    void* cache;               // [slots, 656] bytes
+    const int64_t* slot;       // [tokens]
+    int64_t latent_row, pe_row;
+    int64_t slots;
+    int tokens;
+};
+hipError_t launch_mla_append_fp8(const MlaAppendParams& p, bool fp16, hipStream_t st);
 
 // D = 256 (bucket of 129..256): 4 waves x 32 rows, one wave per SIMD (512 registers:
 // Q fragments and the O accumulator alone are 192), no LDS-DMA pipeline

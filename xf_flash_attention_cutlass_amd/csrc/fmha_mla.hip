@@ -1,22 +1,25 @@
 // fmha_mla.hip — MLA decode over a paged latent cache (fmha_mla_decode): the decode kernel
-// (fmha_mla_decode_kernel.h) for bf16 and fp16, and the split combine at head size 512
+// (fmha_mla_decode_kernel.h) for bf16 and fp16, its twin over an fp8 latent cache
+// (fmha_mla_decode_fp8, fmha_mla_decode_fp8_kernel.h), and the split combine at head size 512
 // (fmha_combine_kernel<512, T>, the forward's template, instantiated here).  A translation unit of
-// its own: the kernel runs one wave per SIMD with 147,456 B of LDS, unlike anything in fmha_fwd.hip.
+// its own: the kernels run one wave per SIMD with 147,456 B of LDS, unlike anything in
+// fmha_fwd.hip.
 #include "fmha_fwd_kernel.h"
 #include "fmha_mla_decode_kernel.h"
+#include "fmha_mla_decode_fp8_kernel.h"
 #include "fmha_launch.h"
 
 namespace xfa {
 
-template <typename T>
-static hipError_t launch_mla_t(const MlaParams& p, hipStream_t st) {
-    allow_lds<fmha_mla_decode_kernel<T>>(p.device, kMlaSmem);
+// kernel: fmha_mla_decode_kernel<T> or fmha_mla_decode_fp8_kernel<T>
+template <typename T, void (*kernel)(const MlaParams), int kSmem>
+static hipError_t launch_mla_t(const MlaParams& p, hipStream_t st, const char* tiles, const char* splits) {
+    allow_lds<kernel>(p.device, kSmem);
     const int64_t items = (int64_t)p.b * p.num_splits * p.row_tiles;
     const dim3 grid((unsigned)((items + kMlaWaves - 1) / kMlaWaves));
     // the mapping: the waves of a workgroup are row tiles of one (batch, split), or key splits
-    note_launch(p.row_tiles > 1 ? "fmha_mla_decode_kernel<tiles>" : "fmha_mla_decode_kernel<splits>", 0, 0,
-                grid.x, grid.y, grid.z, kMlaWaves * 64);
-    hipLaunchKernelGGL((fmha_mla_decode_kernel<T>), grid, dim3(kMlaWaves * 64), kMlaSmem, st, p);
+    note_launch(p.row_tiles > 1 ? tiles : splits, 0, 0, grid.x, grid.y, grid.z, kMlaWaves * 64);
+    hipLaunchKernelGGL(kernel, grid, dim3(kMlaWaves * 64), kSmem, st, p);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || p.num_splits <= 1) return e;
     CombineParams cp{};
@@ -34,7 +37,15 @@ static hipError_t launch_mla_t(const MlaParams& p, hipStream_t st) {
 }
 
 hipError_t launch_mla_decode(const MlaParams& p, bool fp16, hipStream_t st) {
-    return fp16 ? launch_mla_t<_Float16>(p, st) : launch_mla_t<__bf16>(p, st);
+    const char *tiles = "fmha_mla_decode_kernel<tiles>", *splits = "fmha_mla_decode_kernel<splits>";
+    return fp16 ? launch_mla_t<_Float16, fmha_mla_decode_kernel<_Float16>, kMlaSmem>(p, st, tiles, splits)
+                : launch_mla_t<__bf16, fmha_mla_decode_kernel<__bf16>, kMlaSmem>(p, st, tiles, splits);
+}
+
+hipError_t launch_mla_decode_fp8(const MlaParams& p, bool fp16, hipStream_t st) {
+    const char *tiles = "fmha_mla_decode_fp8_kernel<tiles>", *splits = "fmha_mla_decode_fp8_kernel<splits>";
+    return fp16 ? launch_mla_t<_Float16, fmha_mla_decode_fp8_kernel<_Float16>, kMlaSmem>(p, st, tiles, splits)
+                : launch_mla_t<__bf16, fmha_mla_decode_fp8_kernel<__bf16>, kMlaSmem>(p, st, tiles, splits);
 }
 
 }  // namespace xfa

@@ -1082,12 +1082,17 @@ void check_mla_q(const at::Tensor& q) {
     TORCH_CHECK(aligned16(q), "q must be 16-byte aligned with strides that are multiples of 16 bytes");
 }
 
-// ... the latent cache [num_blocks, page, 1, 576] of q's dtype, contiguous ...
-void check_mla_cache(const at::Tensor& kv_cache, const at::Tensor& q) {
-    TORCH_CHECK(kv_cache.dtype() == q.dtype(), "kv_cache must have the dtype of q");
+// ... the latent cache [num_blocks, page, 1, 576] of q's dtype, contiguous (fp8: bytes
+// [num_blocks, page, 1, 656], uint8 or float8_e4m3fn) ...
+bool is_byte_cache(const at::Tensor& kv_cache) {
+    return kv_cache.dtype() == torch::kUInt8 || kv_cache.dtype() == at::kFloat8_e4m3fn;
+}
+void check_mla_cache(const at::Tensor& kv_cache, const at::Tensor& q, bool fp8 = false) {
+    TORCH_CHECK(!fp8 || is_byte_cache(kv_cache), "kv_cache must be uint8 or float8_e4m3fn (rows of 656 bytes)");
+    TORCH_CHECK(fp8 || kv_cache.dtype() == q.dtype(), "kv_cache must have the dtype of q");
     TORCH_CHECK(kv_cache.is_cuda() && kv_cache.device() == q.device(), "kv_cache must be on q's device");
-    TORCH_CHECK(kv_cache.dim() == 4 && kv_cache.size(2) == 1 && kv_cache.size(3) == 576,
-                "kv_cache must be (num_blocks, page_block_size, 1, 576)");
+    TORCH_CHECK(kv_cache.dim() == 4 && kv_cache.size(2) == 1 && kv_cache.size(3) == (fp8 ? 656 : 576),
+                "kv_cache must be (num_blocks, page_block_size, 1, ", fp8 ? 656 : 576, ")");
     CHECK_CONTIGUOUS(kv_cache);
     TORCH_CHECK(kv_cache.size(1) % 16 == 0, "page_block_size must be a multiple of 16");
     TORCH_CHECK(aligned16(kv_cache), "kv_cache must be 16-byte aligned");
@@ -1108,14 +1113,16 @@ at::Tensor take_mla_out(const OptTensor& out_, const at::Tensor& q, int head_siz
 
 }  // namespace
 
-// MLA decode over a paged latent cache (fmha_mla_decode): q and out go by their own strides,
-// nothing is copied.  Returns {out [batch, seqlen_q, heads, 512], softmax_lse [batch, heads, seqlen_q]}.
+// MLA decode over a paged latent cache (fmha_mla_decode; fp8: fmha_mla_decode_fp8 over rows of 656
+// bytes): q and out go by their own strides, nothing is copied.  Returns {out [batch, seqlen_q,
+// heads, 512], softmax_lse [batch, heads, seqlen_q]}.
+template <bool kFp8>
 std::vector<at::Tensor>
 mha_mla_decode(const at::Tensor& q, const at::Tensor& kv_cache, const at::Tensor& block_table,
                const at::Tensor& cache_seqlens, const int head_dim_v, const float softmax_scale,
                const bool is_causal, const int num_splits, const OptTensor& out_) {
     check_mla_q(q);
-    check_mla_cache(kv_cache, q);
+    check_mla_cache(kv_cache, q, kFp8);
     TORCH_CHECK(head_dim_v == 512, "mla_decode takes head_dim_v 512, got ", head_dim_v);
     const int batch = q.size(0), seqlen_q = q.size(1), heads = q.size(2);
     TORCH_CHECK(block_table.dim() == 2, "block_table must be (batch_size, max_num_blocks_per_seq)");
@@ -1130,13 +1137,47 @@ mha_mla_decode(const at::Tensor& q, const at::Tensor& kv_cache, const at::Tensor
     const c10::DeviceGuard device_guard(q.device());
     const int page = kv_cache.size(1);
     const int64_t st[6] = {q.stride(0), q.stride(1), q.stride(2), out.stride(0), out.stride(1), out.stride(2)};
-    fmha_mla_decode(q.data_ptr(), kv_cache.data_ptr(), out.data_ptr(), lse.data_ptr(), block_table.data_ptr(),
-                    (int)block_table.stride(0), cache_seqlens.data_ptr(), seqlen_q,
-                    (int)std::min<int64_t>(block_table.size(1) * (int64_t)page, 0x7fffffff), batch, heads, 576,
-                    head_dim_v, page, st, softmax_scale, -1, is_causal ? 0 : -1, num_splits,
-                    q.dtype() == torch::kFloat16, cur_stream());
-    raise_if_failed("mla_decode");
+    (kFp8 ? fmha_mla_decode_fp8 : fmha_mla_decode)(
+        q.data_ptr(), kv_cache.data_ptr(), out.data_ptr(), lse.data_ptr(), block_table.data_ptr(),
+        (int)block_table.stride(0), cache_seqlens.data_ptr(), seqlen_q,
+        (int)std::min<int64_t>(block_table.size(1) * (int64_t)page, 0x7fffffff), batch, heads, 576,
+        head_dim_v, page, st, softmax_scale, -1, is_causal ? 0 : -1, num_splits,
+        q.dtype() == torch::kFloat16, cur_stream());
+    raise_if_failed(kFp8 ? "mla_decode_fp8" : "mla_decode");
     return {out, lse};
+}
+
+// Append tokens to the fp8 latent cache (fmha_mla_cache_append_fp8): latent [tokens, 512] and k_pe
+// [tokens, 64] by their own row strides (views of one 576-wide tensor are fine), slot_mapping int64.
+void mha_mla_cache_append_fp8(const at::Tensor& latent, const at::Tensor& k_pe, at::Tensor& kv_cache,
+                              const at::Tensor& slot_mapping) {
+    auto dt = latent.dtype();
+    TORCH_CHECK(dt == torch::kFloat16 || dt == torch::kBFloat16, "latent must be fp16 or bf16");
+    TORCH_CHECK(k_pe.dtype() == dt, "k_pe must have the dtype of latent");
+    CHECK_DEVICE(latent); CHECK_DEVICE(k_pe); CHECK_DEVICE(kv_cache); CHECK_DEVICE(slot_mapping);
+    TORCH_CHECK(k_pe.device() == latent.device() && kv_cache.device() == latent.device() &&
+                    slot_mapping.device() == latent.device(), "all tensors must be on one device");
+    TORCH_CHECK(latent.dim() == 2 && latent.size(1) == 512, "latent must be (num_tokens, 512)");
+    TORCH_CHECK(k_pe.dim() == 2 && k_pe.size(1) == 64 && k_pe.size(0) == latent.size(0),
+                "k_pe must be (num_tokens, 64)");
+    TORCH_CHECK(latent.stride(1) == 1 && k_pe.stride(1) == 1, "latent and k_pe must have contiguous last dimension");
+    TORCH_CHECK(aligned16(latent) && aligned16(k_pe),
+                "latent and k_pe must be 16-byte aligned with row strides that are multiples of 16 bytes");
+    TORCH_CHECK(is_byte_cache(kv_cache), "kv_cache must be uint8 or float8_e4m3fn (rows of 656 bytes)");
+    TORCH_CHECK(kv_cache.dim() == 4 && kv_cache.size(2) == 1 && kv_cache.size(3) == 656,
+                "kv_cache must be (num_blocks, page_block_size, 1, 656)");
+    CHECK_CONTIGUOUS(kv_cache);
+    TORCH_CHECK(kv_cache.size(1) % 16 == 0, "page_block_size must be a multiple of 16");
+    TORCH_CHECK(aligned16(kv_cache), "kv_cache must be 16-byte aligned");
+    TORCH_CHECK(slot_mapping.dtype() == torch::kInt64 && slot_mapping.dim() == 1 &&
+                    slot_mapping.size(0) == latent.size(0) && slot_mapping.is_contiguous(),
+                "slot_mapping must be a contiguous int64 (num_tokens)");
+    if (latent.size(0) == 0) return;
+    const c10::DeviceGuard device_guard(latent.device());
+    fmha_mla_cache_append_fp8(latent.data_ptr(), latent.stride(0), k_pe.data_ptr(), k_pe.stride(0),
+                              kv_cache.data_ptr(), slot_mapping.data_ptr(), (int)latent.size(0),
+                              (int)kv_cache.size(0), (int)kv_cache.size(1), dt == torch::kFloat16, cur_stream());
+    raise_if_failed("mla_cache_append_fp8");
 }
 
 PYBIND11_MODULE(paged_attn, m) {
@@ -1177,14 +1218,23 @@ PYBIND11_MODULE(paged_attn, m) {
           py::arg("o_parts"), py::arg("lse_parts"), py::arg("sink") = py::none(), py::arg("packed") = false,
           py::arg("out") = py::none(), py::arg("lse_out") = py::none());
     // `mla_decode` likewise: bound as `_mla_decode`, reached as `paged_attn.mla_decode`
-    m.def("_mla_decode", &mha_mla_decode, "MLA decode over a paged latent KV cache (d_qk 576, d_v 512)",
+    m.def("_mla_decode", &mha_mla_decode<false>, "MLA decode over a paged latent KV cache (d_qk 576, d_v 512)",
           py::arg("q"), py::arg("kv_cache"), py::arg("block_table"), py::arg("cache_seqlens"),
           py::arg("head_dim_v") = 512, py::arg("softmax_scale") = 0.041666666666666664f,
           py::arg("is_causal") = false, py::arg("num_splits") = 0, py::arg("out") = py::none());
+    // ... and its fp8-cache twin and the append into that cache, reached the same way
+    m.def("_mla_decode_fp8", &mha_mla_decode<true>, "MLA decode over an fp8 paged latent KV cache (rows of 656 bytes)",
+          py::arg("q"), py::arg("kv_cache"), py::arg("block_table"), py::arg("cache_seqlens"),
+          py::arg("head_dim_v") = 512, py::arg("softmax_scale") = 0.041666666666666664f,
+          py::arg("is_causal") = false, py::arg("num_splits") = 0, py::arg("out") = py::none());
+    m.def("_mla_cache_append_fp8", &mha_mla_cache_append_fp8, "Append tokens to an fp8 paged latent KV cache",
+          py::arg("latent"), py::arg("k_pe"), py::arg("kv_cache"), py::arg("slot_mapping"));
     const py::handle self = m;
     m.def("__getattr__", [self](const std::string& name) -> py::object {
         if (name == "merge_states") return self.attr("_merge_states");
         if (name == "mla_decode") return self.attr("_mla_decode");
+        if (name == "mla_decode_fp8") return self.attr("_mla_decode_fp8");
+        if (name == "mla_cache_append_fp8") return self.attr("_mla_cache_append_fp8");
         PyErr_SetString(PyExc_AttributeError, ("module 'paged_attn' has no attribute '" + name + "'").c_str());
         throw py::error_already_set();
     });

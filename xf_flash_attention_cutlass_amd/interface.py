@@ -139,6 +139,9 @@ def merge_attn_states(outs, lses, *, sink=None, packed=False, out=None, lse_out=
     return o, lse
 
 
+mla_fp8_cache_row_bytes = 656      # one token of an fp8 latent cache (flash_mla_with_kvcache)
+
+
 def flash_mla_with_kvcache(q, kv_cache, block_table, cache_seqlens, head_dim_v=512,
                            softmax_scale=None, causal=False, num_splits=0, out=None):
     """Decode attention for multi-head latent attention (DeepSeek-V2/V3/R1, Kimi) in its absorbed
@@ -154,14 +157,37 @@ def flash_mla_with_kvcache(q, kv_cache, block_table, cache_seqlens, head_dim_v=5
     causal is bottom-right aligned, as in `flash_attn_with_kvcache`.  A row without a visible key
     gives out = 0 and softmax_lse = +inf.  num_splits: 0 chooses, 1 forces a single pass.
 
+    An fp8 cache - kv_cache of dtype uint8 or float8_e4m3fn with a last dimension of 656 bytes
+    (`mla_fp8_cache_row_bytes`): 512 e4m3fn latent features, four fp32 descales (one per 128
+    features) and the 64 rotary features in q's dtype, FlashMLA's fp8 KV cache / vLLM's
+    `fp8_ds_mla`, as `mla_cache_append_fp8` writes it - takes `paged_attn.mla_decode_fp8`: the
+    latent features are dequantised to q's dtype (one fp32 product, rounded once) and everything
+    else is as above.
+
     Returns (out [b, seqlen_q, h, 512], softmax_lse fp32 [b, h, seqlen_q]).  Not differentiable."""
     if softmax_scale is None:
         softmax_scale = q.shape[-1] ** (-0.5)
+    fp8 = kv_cache.dtype in (torch.uint8, torch.float8_e4m3fn) and kv_cache.shape[-1] == mla_fp8_cache_row_bytes
+    op = paged_attn.mla_decode_fp8 if fp8 else paged_attn.mla_decode
     with torch.no_grad():
-        o, lse = paged_attn.mla_decode(q.detach(), kv_cache.detach(), block_table, cache_seqlens,
-                                       int(head_dim_v), float(softmax_scale), bool(causal),
-                                       int(num_splits), out)
+        o, lse = op(q.detach(), kv_cache.detach(), block_table, cache_seqlens, int(head_dim_v),
+                    float(softmax_scale), bool(causal), int(num_splits), out)
     return o, lse
+
+
+def mla_cache_append_fp8(latent, k_pe, kv_cache, slot_mapping):
+    """Append tokens to an fp8 paged latent KV cache (the layout `flash_mla_with_kvcache` reads:
+    rows of `mla_fp8_cache_row_bytes` = 656 bytes), one HIP launch, no host sync.
+
+    latent: [tokens, 512] and k_pe: [tokens, 64], bf16 or fp16 (views are fine - typically the two
+    parts of one [tokens, 576] tensor: last dimension contiguous, 16-byte aligned rows); k_pe is
+    already rotated and is copied.  kv_cache: uint8 or float8_e4m3fn [num_blocks, page_block_size,
+    1, 656], page_block_size a multiple of 16, written in place.  slot_mapping: int64 [tokens],
+    slot = block * page_block_size + row (vLLM's `concat_and_cache_mla`); a negative or
+    out-of-range slot is skipped.  Each 128-feature group of a latent row gets its own scale:
+    descale = amax / 448 (1.0 for an all-zero group), bytes = e4m3fn(clamp(x * (1 / descale)))."""
+    with torch.no_grad():
+        paged_attn.mla_cache_append_fp8(latent.detach(), k_pe.detach(), kv_cache, slot_mapping)
 
 
 _GRANULARITY = {"tensor": 0, "head": 1}
