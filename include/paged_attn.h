@@ -146,7 +146,9 @@ const char* fmha_version(void);
  * not paged, else 2; 3 the 8-wave ping-pong kernel on the 16x16x32 MFMA (not paged); 2 the
  * 8-wave ping-pong kernel on 32x32x16; 1 the 4-wave kernel (variants build); 0 neither), fp8_w4 (fp8 forward: 1 the 4-wave kernel, the default; 2 the
  * 8-wave ping-pong kernel, dense launches only; 0 the 8-wave compiler-scheduled one), comb_row (0/1), bwd_order (0/1),
- * bwd_desc (0/1), dec_fold (0/1: the decode split combine folded into the split launch). */
+ * bwd_desc (0/1), dec_fold (0/1: the decode split combine folded into the split launch),
+ * fwd_plain (0/1: the 32x32x16 ping-pong body without the score-feature and left-window code for
+ * the launches with neither; same results; fmha_last_kernel names the body, " body=plain"). */
 int fmha_set_option(const char* name, int value);
 /* Current value of a knob, or -1 (with fmha_last_error set) for an unknown name. */
 int fmha_get_option(const char* name);

@@ -15,7 +15,10 @@ pids=()
 for spec in "$@"; do
     name="${spec%%=*}"; args="${spec#*=}"
     python $gen $args --out "variants/fwdpp_$name.h" > /dev/null
-    python tools/quick_variant.py "$name" "-D$def=\"$PWD/variants/fwdpp_$name.h\"" $objs > "variants/$name.log" 2>&1 &
+    flags="-D$def=\"$PWD/variants/fwdpp_$name.h\""
+    # (gen_fwdpp.py writes the plain body beside the full one)
+    if [ "$def" = XFA_FWDPP_BODY ]; then flags="$flags -DXFA_FWDPP_PLAIN_BODY=\"$PWD/variants/fwdpp_${name}_plain.h\""; fi
+    python tools/quick_variant.py "$name" "$flags" $objs > "variants/$name.log" 2>&1 &
     pids+=($!)
 done
 for p in "${pids[@]}"; do wait "$p"; done

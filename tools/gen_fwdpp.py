@@ -64,7 +64,8 @@ function it is generating.  The other two ping-pong bodies are subclasses in the
 and override the operand-specific methods; the phase program (group_program) and the read
 scheduler (place_reads) exist once, here.
 
-  python tools/gen_fwdpp.py        (writes xf_flash_attention_cutlass_amd/csrc/fmha_fwdpp_body.h)
+  python tools/gen_fwdpp.py        (writes xf_flash_attention_cutlass_amd/csrc/fmha_fwdpp_body.h and the
+                                    build's plain body, lib/gen/fmha_fwdpp_body_plain.h)
 """
 import os
 import struct
@@ -126,7 +127,7 @@ def place_reads(mf, reads, inflight):
 
 
 class PingPong:
-    """The 32x32x16 bf16 / f16 body (fwdpp_item_*, paged: fwdpp_pg_item_*)."""
+    """The 32x32x16 bf16 / f16 body (fwdpp_item_*, paged: fwdpp_pg_item_*, plain: fwdpp_plain_item_*)."""
     NAME = "fwdpp"
     HD = 128
     RB = HD * 16           # one 8-row block of the kv_off image
@@ -155,6 +156,12 @@ class PingPong:
     STAMPS = False         # diagnostic build: s_memtime per phase boundary, summed per class in lanes
                            # 0-7 of %[acc] (fmha_fwdpp_kernel.h XFA_FWDPP_STAMPS; read its SHARES only)
     PRO_V0 = False         # (experiment) the prologue's wait leaves tile 0's V pieces in flight
+    PLAIN = False          # the plain body (fwdpp_plain_item_*): no FEATURES, no LEFTWIN, for the launches
+                           # with neither (plain causal, right window, none); same arithmetic, same order
+    LAZYLIM = False        # (plain) no per-step LIM: a masked V phase and the rare path form it from
+                           # %[lim] and the step counter SJ (unmasked, last and idle steps: one VALU less)
+    MAX0 = False           # (plain) tile 0 wholly visible to the wave (%[ew] > 0): its max without the
+                           # key test (64 VALU less per wave and item)
     # parameters
     RING = 4               # K / V tile slots in LDS
     DLEAD = 3              # V(j) loads tile j + DLEAD (needs RING > DLEAD: B's last read of tile t
@@ -165,33 +172,46 @@ class PingPong:
     VPH_NOPS = ["s_nop 7", "s_nop 7"]              # (a V phase: after its first DMA piece)
     N_EPI_STORES = 9       # 8 O row stores + the LSE store
 
-    SIG = ("const int kblo, const int kbhi, const int vblo, const int vbhi, const int kvbytes, "
-           "const i32x4 qsrd, const i32x4 osrd, const i32x4 lsrd, const int kstep, const int kdst, "
-           "const int ntl, const int tw, const int ew, const int grp, const float c, const float thr, "
-           "const int kb0, const int kb1, const int vb0, const int vb1, const int dma0, const int dma1, "
-           "const int lim, const int qoff, const int ooff, const int loff, const int feat, "
-           "const float scp2, const float alw, const float ald, const float alm, const int lw, "
-           "const int liml, const int wid, const int fw, const float alw2, const float adiag")
-    INS = (asmgen.operands("s", "kblo kbhi vblo vbhi kvbytes qsrd osrd lsrd kstep kdst ntl tw ew grp c thr") +
-           asmgen.operands("v", "kb0 kb1 vb0 vb1 dma0 dma1 lim qoff ooff loff") +
-           asmgen.operands("s", "feat scp2") + asmgen.operands("v", "alw ald alm") +
-           asmgen.operands("s", "lw") + asmgen.operands("v", "liml wid") + asmgen.operands("s", "fw") +
-           asmgen.operands("v", "alw2 adiag"))
+    # the function's parameters in order: (operand constraint, C type, names, the option they serve)
+    ARGS = (("s", "int", "kblo kbhi vblo vbhi kvbytes", None), ("s", "i32x4", "qsrd osrd lsrd", None),
+            ("s", "int", "kstep kdst ntl tw ew grp", None), ("s", "float", "c thr", None),
+            ("v", "int", "kb0 kb1 vb0 vb1 dma0 dma1 lim qoff ooff loff", None),
+            ("s", "int", "feat", "FEATURES"), ("s", "float", "scp2", "FEATURES"),
+            ("v", "float", "alw ald alm", "FEATURES"), ("s", "int", "lw", "LEFTWIN"),
+            ("v", "int", "liml wid", "LEFTWIN"), ("s", "int", "fw", "LEFTWIN"),
+            ("v", "float", "alw2 adiag", "FEATURES"))
+
+    def args(self):
+        """ARGS without the parameters of the options this body is generated without"""
+        return [a for a in self.ARGS if a[3] is None or getattr(self, a[3])]
+
+    @property
+    def SIG(self):
+        return ", ".join(f"const {ty} {n}" for _, ty, names, _ in self.args() for n in names.split())
+
+    @property
+    def INS(self):
+        return sum((asmgen.operands(kind, names) for kind, _, names, _ in self.args()), [])
+
     SIG_PG = (", const int* btab, const int pstr, const int rowb, const int lgp, const int pmask, "
               "const int skv, const int skey0")
     INS_PG = asmgen.operands("s", "btab pstr rowb lgp pmask skv skey0")
 
-    def __init__(self, paged=False, abl=(), stamps=False, pro_v0=False, lead=None):
+    def __init__(self, paged=False, abl=(), stamps=False, pro_v0=False, lead=None, plain=False,
+                 lazy_lim=True, max0=True):
         self.PAGED, self.ABL, self.STAMPS, self.PRO_V0 = paged, frozenset(abl), stamps, pro_v0
         if lead is not None:
             self.LEAD = lead
+        if plain:          # (lazy_lim, max0: the plain body's two reductions, each A/B'd on its own)
+            self.PLAIN, self.FEATURES, self.LEFTWIN = True, False, False
+            self.LAZYLIM, self.MAX0 = lazy_lim, max0
         self.guards = []   # assembler checks of the return-address signs, after the whole program
 
     def function(self, dt):
         """the asm function of one dtype: the item program, then the guards its stubs collected"""
         prog = self.item_program(dt) + self.guards
         self.guards = []
-        return asmgen.asm_function(f"{self.NAME}{'_pg' if self.PAGED else ''}_item_{dt}",
+        return asmgen.asm_function(f"{self.NAME}{'_pg' if self.PAGED else '_plain' if self.PLAIN else ''}_item_{dt}",
                                    self.SIG + (self.SIG_PG if self.PAGED else ""), prog,
                                    self.INS + (self.INS_PG if self.PAGED else []),
                                    asmgen.clobbers(self.nvgpr(), 128, self.SKR, self.SCM + 2, self.STAMPS),
@@ -338,8 +358,19 @@ class PingPong:
         return [f"v_cmp_lt_i32 vcc, {off}, v{self.LIM}"]
 
     def lim_step(self):
+        if self.LAZYLIM:
+            return []
         return [f"v_add_u32 v{self.LIM}, -64, v{self.LIM}"] + (
             [f"v_add_u32 v{self.LIML}, -64, v{self.LIML}"] if self.LEFTWIN else [])
+
+    def lim_form(self):
+        """(LAZYLIM) LIM of tile SJ + 1, the tile whose scores a V phase holds: %[lim] - 64 (SJ + 1)
+        (SJ = -1 in the pre-loop phases) — what lim_step's steps add up to"""
+        if not self.LAZYLIM:
+            return []
+        ST = self.ST
+        return [f"s_add_i32 s{ST}, s{self.SJ}, 1", f"s_lshl_b32 s{ST}, s{ST}, 6",
+                f"v_subrev_u32 v{self.LIM}, s{ST}, %[lim]"]
 
     def cvt_pair(self, dt, v, dword, lo, hi):
         """scores v - 1, v (in lo, hi) packed into P dword `dword`"""
@@ -363,19 +394,30 @@ class PingPong:
             stages.append(st)
         return asmgen.stagger(stages) + ["s_nop 0"]
 
-    def row_max(self, dst, raw=None):
+    def row_max(self, dst, raw=None, visible0=None):
         """masked max of this lane's row over the tile's 64 keys (both lane halves) -> dst (and the
-        unmasked max -> raw)"""
+        unmasked max -> raw).  visible0 = (label, label): tile 0's max, which skips the key test
+        where the whole tile is visible to the wave (MAX0)"""
         t2, ninf = f"v{self.MISC + 1}", f"v{self.MISC + 3}"
         out = [f"v_mov_b32 {ninf}, 0xff800000", f"v_mov_b32 {dst}, {ninf}"]
         if raw:
             out.append(f"v_mov_b32 {raw}, {ninf}")
+        masked = []
         for v in range(32):
             off, _ = self.value_info(v)
-            out += self.vis_test(off) + [f"v_cndmask_b32 {t2}, {ninf}, v{self.SBASE + v}, vcc",
-                                         f"v_max_f32 {dst}, {dst}, {t2}"]
+            masked += self.vis_test(off) + [f"v_cndmask_b32 {t2}, {ninf}, v{self.SBASE + v}, vcc",
+                                            f"v_max_f32 {dst}, {dst}, {t2}"]
             if raw:
-                out.append(f"v_max_f32 {raw}, {raw}, v{self.SBASE + v}")
+                masked.append(f"v_max_f32 {raw}, {raw}, v{self.SBASE + v}")
+        if visible0:
+            # %[ew] > 0: every row of the wave sees all of tile 0, so the key test passes for every
+            # score: the same maxima in the same order without it (bit for bit)
+            lm, lj = visible0
+            out += ["s_cmp_gt_i32 %[ew], 0", f"s_cbranch_scc0 {lm}"]
+            out += [f"v_max_f32 {dst}, {dst}, v{self.SBASE + v}" for v in range(32)]
+            out += [f"s_branch {lj}", f"{lm}:"] + masked + [f"{lj}:"]
+        else:
+            out += masked
         out += [f"v_mov_b32 {t2}, {dst}", "s_nop 1", f"v_permlane32_swap_b32 {dst}, {t2}",
                 "s_nop 1", f"v_max_f32 {dst}, {dst}, {t2}"]
         if raw:
@@ -383,14 +425,15 @@ class PingPong:
                     "s_nop 1", f"v_max_f32 {raw}, {raw}, {t2}"]
         return out
 
-    def first_max(self):
+    def first_max(self, uid):
         """m = the masked max of tile 0 (in log2 units: NM = -c max; 0 for a row with no key).
         LEFTWIN: a row with no visible key in tile 0 (its window starts later) takes NM = +inf, so
         its first visible key gives P = inf and the redo path sets m to that tile's true max — the
         row's reference max is then exact, as tile 0's is for the others (a single-key row gets
         P = 1 and O = its V row bit for bit)"""
         mx, t2, NM = f"v{self.MISC}", f"v{self.MISC + 1}", self.NM
-        out = self.XDL_NOPS + self.row_max(mx) + [f"v_mul_f32_e64 {t2}, -%[c], {mx}",
+        vis0 = (f".Lfmm_{uid}", f".Lfmj_{uid}") if self.MAX0 else None
+        out = self.XDL_NOPS + self.row_max(mx, visible0=vis0) + [f"v_mul_f32_e64 {t2}, -%[c], {mx}",
                                                   f"v_cmp_lg_f32 vcc, 0xff800000, {mx}"]
         if self.LEFTWIN:
             pinf = f"v{self.MISC + 3}"
@@ -427,7 +470,7 @@ class PingPong:
                     "s_nop 0",
                     f"v_mul_f32 v{LRUN}, v{LRUN}, {alpha}"]
         else:
-            out += self.row_max(mx)
+            out += self.lim_form() + self.row_max(mx)     # (reached from unmasked steps too)
             out += [f"v_mul_f32 {t2}, %[c], {mx}",
                     f"v_max_f32_e64 {t2}, {t2}, -v{NM}",          # m_new = max(m_ref, c max)
                     # (LEFTWIN: a row still at NM = +inf with no visible key here keeps m_new finite,
@@ -549,6 +592,8 @@ class PingPong:
             return pre + sum(pieces, []) + self.dma_advance() + self.lim_step(), []
         sm = self.softmax(dt, kind == "m")
         fin, fstub = self.feat_call(uid, tag) if feat else ([], [])
+        if kind == "m":
+            pre = pre + self.lim_form()
         if self.DMAMIX:
             out = pre + pieces[0] + self.VPH_NOPS           # last QK^T results -> VALU
             # the other pieces spread through the softmax
@@ -618,7 +663,7 @@ class PingPong:
         v_wait = [] if grp else [f"s_waitcnt vmcnt({NPIECE * (DLEAD - 2)})"]
         bar = ["s_barrier"]
         out, tail = [], []
-        if self.FEATURES:
+        if self.FEATURES or self.LAZYLIM:
             out += [f"s_mov_b32 s{SJ}, -1"]                    # (tile j + 1 = 0 in the pre-loop phases)
         if grp:
             out += bar                                          # B runs one phase behind A
@@ -633,13 +678,13 @@ class PingPong:
             v, stub = v_phase(dt, DLEAD - 1, "m", uid, "f", feat=False)
             f0, s0 = self.feat_call(uid, "f0", "fsc")
             f1, s1 = self.feat_call(uid, "f1", "fal")
-            out += self.XDL_NOPS + f0 + self.first_max() + [f"v_fma_f32 v{NM}, -%[c], %[alm], v{NM}",
+            out += self.XDL_NOPS + f0 + self.first_max(uid) + [f"v_fma_f32 v{NM}, -%[c], %[alm], v{NM}",
                                                              f"v_mov_b32 v{self.NMTRUE}, v{NM}"] + f1
             out += v + st(ST_V) + v_wait + bar
             stub += s0 + s1
         else:
             v, stub = v_phase(dt, DLEAD - 1, "m", uid, "f")
-            out += self.first_max() + v + st(ST_V) + v_wait + bar
+            out += self.first_max(uid) + v + st(ST_V) + v_wait + bar
         tail += stub
         out += [f"s_branch .Lloop_{uid}", f".Lni_{uid}:"]
         # (no visible key: the same barriers and DMA duty)
@@ -726,19 +771,49 @@ class PingPong:
         return out + self.groups(dt)
 
 
+# The plain body is not committed (a third copy of a 10 000-line body): build.py generates it here
+# before it compiles, and -I's the folder
+GEN_PLAIN = os.path.join(ROOT, "xf_flash_attention_cutlass_amd", "lib", "gen", "fmha_fwdpp_body_plain.h")
+
+
+def plain_path(out):
+    """the plain body's header that goes with `out`: the build's generated one for the committed
+    header, else beside `out` (variants/fwdpp_x.h -> variants/fwdpp_x_plain.h)"""
+    if os.path.abspath(out) == os.path.abspath(OUT):
+        return GEN_PLAIN
+    stem, ext = os.path.splitext(out)
+    return stem + "_plain" + ext
+
+
 def emit(out=OUT, **options):
-    """the dense body, then (not in stamps builds) the paged-K/V body; options: PingPong's"""
-    bodies = [PingPong(paged=False, **options)]
+    """`out`: the dense body, then (not in stamps builds) the paged-K/V body; plain_path(out): the
+    plain body, a header of its own (fmha_fwdpp_kernel.h includes it after `out`).  options:
+    PingPong's (lazy_lim, max0: the plain body's alone)"""
+    full = {k: v for k, v in options.items() if k not in ("lazy_lim", "max0")}
+    bodies = [PingPong(paged=False, **full)]
     stamps = bodies[0].STAMPS
     if not stamps:
-        bodies.append(PingPong(paged=True, **options))
+        bodies.append(PingPong(paged=True, **full))
+    about = ["// The 8-wave ping-pong D = 128 forward's item body (fmha_fwdpp_kernel.h): one asm statement",
+             "// per dtype with a fixed register map; see the generator's docstring for the schedule."]
     asmgen.write_header(
-        out, "gen_fwdpp.py",
-        ["// The 8-wave ping-pong D = 128 forward's item body (fmha_fwdpp_kernel.h): one asm statement",
-         "// per dtype with a fixed register map; see the generator's docstring for the schedule."],
+        out, "gen_fwdpp.py", about,
         [ln for body in bodies for dt in ("bf16", "f16") for ln in body.function(dt)],
         defines=["#define XFA_FWDPP_STAMPS 1           // diagnostic build (--stamps)"] if stamps else [],
         decls=[f"constexpr int kFwdppRing = {PingPong.RING};           // K / V tile slots the body addresses"])
+    emit_plain(plain_path(out), **options)
+
+
+def emit_plain(out=GEN_PLAIN, **options):
+    """the plain body alone (what build.py calls: the header it writes is not committed)"""
+    plain = PingPong(plain=True, **options)
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    asmgen.write_header(
+        out, "gen_fwdpp.py",
+        ["// The 8-wave ping-pong D = 128 forward's item body (fmha_fwdpp_kernel.h): one asm statement",
+         "// per dtype with a fixed register map; see the generator's docstring for the schedule.",
+         "// This header: the plain body (PLAIN: no score features, no left window)."],
+        [ln for dt in ("bf16", "f16") for ln in plain.function(dt)])
 
 
 if __name__ == "__main__":
@@ -748,5 +823,8 @@ if __name__ == "__main__":
     ap.add_argument("--stamps", action="store_true", help="diagnostic phase stamps (XFA_FWDPP_STAMPS)")
     ap.add_argument("--out", default=OUT)
     ap.add_argument("--pro-v0", action="store_true", help="prologue waits for Q and K0 only")
+    ap.add_argument("--no-lazy-lim", action="store_true", help="plain body: LIM stepped in every V phase")
+    ap.add_argument("--no-max0", action="store_true", help="plain body: tile 0's max always with the key test")
     a = ap.parse_args()
-    emit(a.out, abl=[x for x in a.abl.split(",") if x], stamps=a.stamps, pro_v0=a.pro_v0)
+    emit(a.out, abl=[x for x in a.abl.split(",") if x], stamps=a.stamps, pro_v0=a.pro_v0,
+         lazy_lim=not a.no_lazy_lim, max0=not a.no_max0)

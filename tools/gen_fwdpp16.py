@@ -168,7 +168,7 @@ class PingPong16(PingPong):
                     f"v_max_f32 {dst[rt]}, {dst[rt]}, {t2}"]
         return out + self.row_reduce("v_max_f32", dst0, t2) + self.row_reduce("v_max_f32", dst1, t2)
 
-    def first_max(self):
+    def first_max(self, uid):
         """m_rt = the masked max of tile 0 per row (NM = -c max, 0 for a row with no key)"""
         mx, t2 = f"v{self.MISC}", f"v{self.MISC + 2}"
         out = self.XDL_NOPS + self.row_max2(mx, f"v{self.MISC + 1}")

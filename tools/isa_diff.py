@@ -5,11 +5,17 @@ assembler comments (which name labels by the function's index in its unit).  Onl
 __hip_cuid_<hash> symbol (a hash of the source text) may differ.  A kernel only one tree has is
 listed as ONLY IN A / B and does not count as a difference.
 
-  python tools/isa_diff.py <tree A> <tree B> [-j N] [--kernarg]    exit status 1 if any kernel differs
+  python tools/isa_diff.py <tree A> <tree B> [-j N] [--kernarg] [--rename REGEX=REPL]
+                                                          exit status 1 if any kernel differs
 
 --kernarg: for trees whose parameter blocks differ in size (a field added at the end): the
 kernarg size and the offsets of scalar loads / address adds from the kernarg pointer s[0:1] are
 masked, so a kernel counts as identical when nothing but where its arguments lie has changed.
+--rename REGEX=REPL: applied to tree A's assembly first, for a kernel template that gained a
+parameter in tree B (its instantiations' mangled names then differ though their code may not), e.g.
+  --rename 'fmha_fwdpp_kernelILb(\d)ELb(\d)ELb(\d)EEE=fmha_fwdpp_kernelILb\1ELb\2ELb\3ELb0EEE'
+The labels of inline asm statements (.L<name>_<n>, n = the statement's %= number, which counts the
+asm statements the compiler has seen before it) are renumbered per kernel like the .LBB ones.
 """
 import argparse
 import concurrent.futures as cf
@@ -25,6 +31,8 @@ def units(tree):
     spec = importlib.util.spec_from_file_location("b", os.path.join(tree, "xf_flash_attention_cutlass_amd", "build.py"))
     b = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(b)
+    if hasattr(b, "generate"):
+        b.generate()               # (the headers the build generates before compiling)
     tus = [(f"fmha_{kind}_hd{hd}_{dt}", f"fmha_{kind}.hip",
             [f"-DXFA_HD={hd}", f"-DXFA_DTN={dt}", f"-DXFA_DT_BF16={int(dt == 'bf16')}"])
            for hd, dt in b.VARIANTS for kind in ("fwd", "bwd")]
@@ -37,6 +45,7 @@ def units(tree):
 
 
 MASK_KERNARG = False
+RENAME = None       # (regex, replacement) for tree A's assembly
 
 
 def kernels(tree, tu, out_dir):
@@ -45,7 +54,10 @@ def kernels(tree, tu, out_dir):
     asm = os.path.join(out_dir, name + ".s")
     subprocess.run([b.HIPCC, "-x", "hip", *b.HIP_FLAGS, *defs, "--cuda-device-only", "-S",
                     os.path.join(b.CSRC, src), "-o", asm], check=True)
-    return name, normalise(open(asm).read())
+    text = open(asm).read()
+    if RENAME and tree == RENAME[2]:
+        text = re.sub(RENAME[0], RENAME[1], text)
+    return name, normalise(text)
 
 
 def normalise(text):
@@ -60,7 +72,12 @@ def normalise(text):
         labels = {}
         body = re.sub(r"\.Lfunc_end\d+", ".Lfunc_end", m.group(0))     # (a function's index in its unit)
         body = re.sub(r"(?m)[ \t]*;.*$", "", body)
-        out[m.group(1)] = re.sub(r"\.LBB\d+_\d+", lambda l: labels.setdefault(l.group(0), f".L{len(labels)}"), body)
+        body = re.sub(r"\.LBB\d+_\d+", lambda l: labels.setdefault(l.group(0), f".L{len(labels)}"), body)
+        far = {}    # the compiler's long-branch labels, numbered through the unit
+        body = re.sub(r"\.Lpost_getpc\d+", lambda l: far.setdefault(l.group(0), f".Lpost_getpc<{len(far)}>"), body)
+        ids = {}    # inline asm labels: the %= number of their statement
+        out[m.group(1)] = re.sub(r"(\.L[A-Za-z][A-Za-z0-9_]*_)(\d+)\b",
+                                 lambda l: l.group(1) + ids.setdefault(l.group(2), f"<{len(ids)}>"), body)
     for m in re.finditer(r"(?ms)^\s*\.amdhsa_kernel (\w+)\n.*?\.end_amdhsa_kernel", text):
         out[m.group(1)] += m.group(0)          # registers, LDS, the kernel descriptor's settings
     return out
@@ -71,9 +88,12 @@ def main():
     ap.add_argument("trees", nargs=2)
     ap.add_argument("-j", type=int, default=8)
     ap.add_argument("--kernarg", action="store_true", help="mask kernarg size and offsets")
+    ap.add_argument("--rename", default="", help="REGEX=REPL applied to tree A's assembly")
     a = ap.parse_args()
-    global MASK_KERNARG
+    global MASK_KERNARG, RENAME
     MASK_KERNARG = a.kernarg
+    if a.rename:
+        RENAME = (*a.rename.split("=", 1), a.trees[0])
     res, bad = [], 0
     with tempfile.TemporaryDirectory() as tmp, cf.ThreadPoolExecutor(a.j) as ex:
         for i, tree in enumerate(a.trees):

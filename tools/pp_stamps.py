@@ -25,12 +25,14 @@ def main():
     ap.add_argument("--noncausal", action="store_true")
     ap.add_argument("--w4", type=int, default=2, help="fwd_w4: 2 the 32x32x16 body, 3 the 16x16x32 body")
     ap.add_argument("--wl", type=int, default=-1, help="left window (causal: a sliding window)")
+    ap.add_argument("--plain", type=int, default=1, help="fwd_plain: 1 the plain body where it applies, 0 the full one")
     ap.add_argument("--iters", type=int, default=3,
                     help="launches summed (the device counters are 32-bit: keep 256 CUs x launches x cycles < 2^32)")
     a = ap.parse_args()
     from xf_flash_attention_cutlass_amd import capi
     lib = capi.load(a.lib, strict=False)
     assert lib.fmha_set_option(b"fwd_w4", a.w4) == 0
+    assert lib.fmha_set_option(b"fwd_plain", a.plain) == 0
     st = ctypes.CDLL(a.lib).fmha_fwdpp_stamps
     st.argtypes = [ctypes.POINTER(ctypes.c_uint), ctypes.c_int]
     b, h, s, d = 4, 32, 4096, 128

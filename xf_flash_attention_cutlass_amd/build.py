@@ -30,12 +30,13 @@ CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "lib")
 OBJ = os.path.join(PKG, "lib", "obj")
 INCLUDE = os.path.join(ROOT, "include")
+GEN = os.path.join(LIB, "gen")     # headers generated before compiling (generate()), not committed
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("XFA_ARCH", "gfx950")
 LIBNAME = "libpaged-attention.so"
 
 HIP_FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-munsafe-fp-atomics",
-             "-Wno-unused-result", "-I", CSRC, "-I", INCLUDE]
+             "-Wno-unused-result", "-I", CSRC, "-I", INCLUDE, "-I", GEN]
 # extra -D/-f flags for A/B variants of the library (tools/build_variant.sh); not for releases
 HIP_FLAGS += os.environ.get("XFA_EXTRA_FLAGS", "").split()
 
@@ -51,7 +52,35 @@ def _newer(out: str, deps) -> bool:
 
 
 def _headers():
-    return glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(INCLUDE, "*.h"))
+    return (glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(INCLUDE, "*.h")) +
+            glob.glob(os.path.join(GEN, "*.h")))
+
+
+def generate() -> str:
+    """lib/gen/fmha_fwdpp_body_plain.h: the plain ping-pong body (tools/gen_fwdpp.py emit_plain, its
+    default options), the one generated body that is not committed.  Rewritten only when its text
+    changes, so an up-to-date build stays up to date."""
+    import contextlib
+    import importlib.util
+    import io
+    import tempfile
+    tools = os.path.join(ROOT, "tools")
+    sys.path.insert(0, tools)
+    try:
+        spec = importlib.util.spec_from_file_location("_xfa_gen_fwdpp", os.path.join(tools, "gen_fwdpp.py"))
+        gen = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(gen)
+    finally:
+        sys.path.remove(tools)
+    out = os.path.join(GEN, "fmha_fwdpp_body_plain.h")
+    os.makedirs(GEN, exist_ok=True)
+    with tempfile.TemporaryDirectory(dir=GEN) as tmp:
+        new = os.path.join(tmp, "plain.h")
+        with contextlib.redirect_stdout(io.StringIO()):
+            gen.emit_plain(new)
+        if not os.path.exists(out) or open(out, "rb").read() != open(new, "rb").read():
+            os.replace(new, out)
+    return out
 
 
 def _compile(job):
@@ -75,6 +104,7 @@ def build_lib(jobs: int = 8, force: bool = False, verbose: bool = False, variant
     are rebuilt with it (into lib/obj_variants), the others shared with the product build."""
     obj_dir = os.path.join(LIB, "obj_variants") if variants else OBJ
     os.makedirs(obj_dir, exist_ok=True)
+    generate()
     todo = []
     for hd, dt in VARIANTS:
         defs = [f"-DXFA_HD={hd}", f"-DXFA_DTN={dt}", f"-DXFA_DT_BF16={1 if dt == 'bf16' else 0}"]

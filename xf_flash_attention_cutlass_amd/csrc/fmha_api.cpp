@@ -36,6 +36,10 @@ void note_launch(const char* kernel, int persistent, int xcdq, unsigned gx, unsi
     snprintf(g_last_kernel, sizeof(g_last_kernel), "%s persistent=%d xcdq=%d grid=%ux%ux%u block=%d",
              kernel, persistent, xcdq, gx, gy, gz, block);
 }
+void note_body(const char* body) {
+    const size_t n = strlen(g_last_kernel);
+    snprintf(g_last_kernel + n, sizeof(g_last_kernel) - n, " body=%s", body);
+}
 thread_local SinkMech g_sink_mech = kSinkNone;   // how this thread's last forward applied its sink
 void note_sink(SinkMech mech) { g_sink_mech = mech; }
 }  // namespace xfa

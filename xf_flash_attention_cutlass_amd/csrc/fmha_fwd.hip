@@ -153,10 +153,21 @@ static hipError_t launch_fwdpp(const FwdParams& p, hipStream_t st) {
     // faster of the two per mask on the same box
     const bool m16 = !p.block_table &&
                      (p.fwd4 == 3 || (p.fwd4 == 4 && p.wr < 0 && !p.alibi && !(p.softcap_pre > 0.f)));
-    allow_lds<fmha_fwdpp_kernel<BF, false>, fmha_fwdpp_kernel<BF, true>, fmha_fwdpp_kernel<BF, false, true>>(p.device, kFwdppSmem);
+    // the plain body (fwd_plain; gen_fwdpp.py PLAIN): the 32x32x16 launches with no score feature
+    // and no left window in effect (the normalised wl of a causal or right-window launch is
+    // seqlen_k, fwd4_eligible) — dense and varlen causal, right window only, fwd_w4 = 2 without a
+    // mask.  (The knob is read here: the params block, and with it every other kernel, stays as it is.)
+    const bool plain = !m16 && !p.block_table && !(p.wl >= 0 && p.wl < p.seqlen_k) && !p.alibi &&
+                       !(p.softcap_pre > 0.f) && options().fwd_plain.load();
+    allow_lds<fmha_fwdpp_kernel<BF, false>, fmha_fwdpp_kernel<BF, true>, fmha_fwdpp_kernel<BF, false, true>,
+              fmha_fwdpp_kernel<BF, false, false, true>>(p.device, kFwdppSmem);
     if (m16) return launch_planned("fmha_fwdpp16_kernel", fmha_fwdpp_kernel<BF, true>, s, 512, kFwdppSmem, st);
-    if (p.block_table) return launch_planned("fmha_fwdpp_paged_kernel", fmha_fwdpp_kernel<BF, false, true>, s, 512, kFwdppSmem, st);
-    return launch_planned("fmha_fwdpp_kernel", fmha_fwdpp_kernel<BF, false>, s, 512, kFwdppSmem, st);
+    const hipError_t e =
+        p.block_table ? launch_planned("fmha_fwdpp_paged_kernel", fmha_fwdpp_kernel<BF, false, true>, s, 512, kFwdppSmem, st)
+        : plain       ? launch_planned("fmha_fwdpp_kernel", fmha_fwdpp_kernel<BF, false, false, true>, s, 512, kFwdppSmem, st)
+                      : launch_planned("fmha_fwdpp_kernel", fmha_fwdpp_kernel<BF, false>, s, 512, kFwdppSmem, st);
+    note_body(p.block_table ? "paged" : plain ? "plain" : "full");
+    return e;
 }
 
 static hipError_t launch_fwd4(const FwdParams& p, hipStream_t st) {

@@ -29,6 +29,12 @@ namespace xfa {
        causal +2-3 %, C4 +3 %, non-causal equal), 1 the 4-wave kernel (fmha_fwd4_kernel.h, the    \
        variants build only), 0 neither (8-wave fmha_fwd_kernel) */                                \
     X(fwd_w4, 4, 0, 4)                                                                            \
+    /* the 32x32x16 ping-pong body generated without the score features and the left window       \
+       (fwdpp_plain_item_*) for the launches with neither; 0 the full body everywhere.  Same bits \
+       (tests/test_fwdpp_plain_gpu.py).  Same box, alternating with the library before it, 9      \
+       rounds: C2 causal 1159-1162 vs 1129-1134 TFLOP/s (+2.4 %), C4 +2.3 %, sq 2048 / sk 4096    \
+       +2.3 %; VALU 87.2 M vs 92.0 M, SALU 16.5 M vs 19.6 M per C2 launch */     \
+    X(fwd_plain, 1, 0, 1)                                                                         \
     /* 4-wave fp8 forward (fmha_fwd8w_kernel.h) where eligible (C2 shape, same box: 1610 vs 1576  \
        TFLOP/s causal, 1852 vs 1799 non-causal); 2 the ping-pong one (the variants build only) */ \
     X(fp8_w4, 1, 0, 2)                                                                            \
@@ -87,6 +93,9 @@ Options& options();
 // the persistent mode (0 = one workgroup per item, 1 boustrophedon, 2 XCD-grouped pairs,
 // 3 dynamic queue), the per-XCD queues flag and the grid.  Thread-local, set by the launchers.
 void note_launch(const char* kernel, int persistent, int xcdq, unsigned gx, unsigned gy, unsigned gz, int block);
+// ... and which generated body the kernel ran where one kernel name covers several: a trailing
+// " body=<name>" field of the same record (after note_launch)
+void note_body(const char* body);
 
 // Which mechanism applies the attention sink of a launch with p.sink: the
 // launcher records it, the C ABI then runs the post-pass where it is kSinkPass and names the
