@@ -127,7 +127,7 @@ void fmha_set_rng_state(uint64_t seed, uint64_t offset);
 void fmha_set_rng_state_device(const int64_t* seed_ptr, const int64_t* offset_ptr,
                                uint64_t offset_add, int64_t* rng_out);
 
-/* Library version / build identification, e.g. "xf-fmha-gfx950 2.10".  2.0 (round 3) changed
+/* Library version / build identification, e.g. "xf-fmha-gfx950 2.11".  2.0 (round 3) changed
  * argument lists of existing symbols; 2.1 exports those under _v2 names (see INTEGRATION.md
  * "ABI history"). */
 const char* fmha_version(void);
@@ -544,6 +544,60 @@ void fmha_mla_cache_append_fp8(const void* latent, int64_t latent_row_stride, co
                                int64_t k_pe_row_stride, void* kv_cache8, const void* slot_mapping,
                                int32_t num_tokens, int32_t num_blocks, int32_t page_block_size,
                                bool is_fp16, hipStream_t stream);
+
+/* --------------------------- MLA decode over index-selected tokens: sparse attention (2.11) */
+
+/* MLA decode where an indexer has chosen the tokens (DeepSeek-V3.2's sparse attention; FlashMLA's
+ * flash_mla_with_kvcache(..., indices=...)): the decode attends over exactly the selected rows of
+ * the paged latent cache, gathered inside the kernel.  fmha_mla_decode_sparse reads the 16-bit
+ * cache of fmha_mla_decode, fmha_mla_decode_sparse_fp8 the 656-byte rows of fmha_mla_decode_fp8
+ * (the operand is that entry's rounded row, unchanged).
+ *   q, o, softmax_lse, strides, softmax_scale, num_splits, is_fp16: as fmha_mla_decode
+ *   kv_cache   contiguous [num_blocks, page_block_size, 1, 576] of q's type, or bytes
+ *              [num_blocks, page_block_size, 1, 656]; num_blocks >= 1, page_block_size % 16 == 0.
+ *              The cache may be larger than 4 GiB: slot-to-byte arithmetic is done in 64 bits.
+ *   indices    int32 [batch, seqlen_q, topk], last dimension contiguous, 4-byte aligned;
+ *              indices_batch_stride and indices_row_stride in ELEMENTS, non-negative; topk >= 1
+ * An entry is a PHYSICAL SLOT, block * page_block_size + row (FlashMLA's convention, the one
+ * fmha_mla_cache_append_fp8 writes): the row of slot s starts at byte s * 1152 (s * 656).  An entry
+ * is valid iff 0 <= entry < num_blocks * page_block_size; every other value (-1, FlashMLA's
+ * padding; INT32_MIN; INT32_MAX; num_blocks * page_block_size) contributes nothing and is never
+ * turned into an address.  The kernel validates: the host cannot without a sync, and no index
+ * value, however wild, produces a load outside [kv_cache, kv_cache + num_blocks *
+ * page_block_size * row bytes).
+ * For query (b, pos, head), K is the rows at the valid entries of indices[b, pos, :], in that
+ * order, duplicates as often as they occur, V = K[:, :512]:  S = softmax_scale q K^T (all 576
+ * features), O = softmax(S) V, LSE = logsumexp(S).  A row whose entries are all invalid gives O = 0
+ * and LSE = +inf.  There is no block table, no cache_seqlens and no mask: visibility is what the
+ * indexer chose.  Per-batch topk lengths are expressed by padding with -1.
+ * A 16-row tile is 16 heads of ONE position (row tiles = seqlen_q * ceil(num_heads / 16)); a split
+ * is an equal range of the ceil(topk / 32) index tiles.  num_splits <= 0: fmha_mla_decode's rule
+ * over these row tiles, at most ceil(topk / 32) and 128.  The split scratch comes from the
+ * per-stream pool; no host sync (capturable in a graph).  fmha_last_kernel() names
+ * fmha_mla_decode_sparse_kernel<tiles> or <splits> (fmha_mla_decode_sparse_fp8_kernel<...>),
+ * fmha_last_num_splits() the split count.  With indices[b, 0, :] the slots of a dense sequence in
+ * order, the result equals fmha_mla_decode[_fp8] over that sequence bit for bit at the same split
+ * count.
+ * batch_size == 0 validates in full, launches nothing and succeeds.  Refused with an error, outputs
+ * untouched: a NULL q / kv_cache / o / indices / strides, (head_size, head_size_v) other than
+ * (576, 512), topk < 1, num_blocks < 1, a page size that is no positive multiple of 16,
+ * num_heads < 1 or seqlen_q < 1, a negative batch, num_splits > 128, q / o strides that are no
+ * multiples of 8 or pointers that are not 16-byte aligned (indices, softmax_lse: 4-byte), a
+ * negative indices stride, a launch larger than one grid covers. */
+void fmha_mla_decode_sparse(void* q, void* kv_cache, void* o, void* softmax_lse,
+                            void* indices, int64_t indices_batch_stride, int64_t indices_row_stride,
+                            int32_t topk, int32_t seqlen_q, int32_t batch_size, int32_t num_heads,
+                            int32_t head_size /* 576 */, int32_t head_size_v /* 512 */,
+                            int32_t num_blocks, int32_t page_block_size,
+                            const int64_t* strides /* q then o: batch,row,head */,
+                            float softmax_scale, int32_t num_splits, bool is_fp16, hipStream_t stream);
+void fmha_mla_decode_sparse_fp8(void* q, void* kv_cache8, void* o, void* softmax_lse,
+                                void* indices, int64_t indices_batch_stride, int64_t indices_row_stride,
+                                int32_t topk, int32_t seqlen_q, int32_t batch_size, int32_t num_heads,
+                                int32_t head_size /* 576 */, int32_t head_size_v /* 512 */,
+                                int32_t num_blocks, int32_t page_block_size,
+                                const int64_t* strides /* q then o: batch,row,head */,
+                                float softmax_scale, int32_t num_splits, bool is_fp16, hipStream_t stream);
 
 #ifdef __cplusplus
 } /* extern "C" */

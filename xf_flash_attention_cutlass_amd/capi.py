@@ -70,6 +70,10 @@ _SIGS = {
     "fmha_mla_decode_fp8": [vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32,
                             C.POINTER(C.c_int64), f32, C.c_int, C.c_int, i32, b_, vp],
     "fmha_mla_cache_append_fp8": [vp, C.c_int64, vp, C.c_int64, vp, vp, i32, i32, i32, b_, vp],
+    "fmha_mla_decode_sparse": [vp, vp, vp, vp, vp, C.c_int64, C.c_int64, i32, i32, i32, i32, i32, i32, i32,
+                               i32, C.POINTER(C.c_int64), f32, i32, b_, vp],
+    "fmha_mla_decode_sparse_fp8": [vp, vp, vp, vp, vp, C.c_int64, C.c_int64, i32, i32, i32, i32, i32, i32,
+                                   i32, i32, C.POINTER(C.c_int64), f32, i32, b_, vp],
     "fmha_last_error": [],
     "fmha_last_status": [],
     "fmha_last_num_splits": [],

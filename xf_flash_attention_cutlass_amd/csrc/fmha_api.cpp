@@ -525,7 +525,7 @@ const char* fmha_last_error(void) { return g_err.c_str(); }
 int fmha_last_status(void) { return g_status; }
 int fmha_last_num_splits(void) { return g_last_splits; }
 const char* fmha_last_kernel(void) { return g_last_kernel; }
-const char* fmha_version(void) { return XFA_VARIANTS ? "xf-fmha-gfx950 2.10 (variants)" : "xf-fmha-gfx950 2.10"; }
+const char* fmha_version(void) { return XFA_VARIANTS ? "xf-fmha-gfx950 2.11 (variants)" : "xf-fmha-gfx950 2.11"; }
 
 void fmha_set_rng_state(uint64_t seed, uint64_t offset) {
     g_seed = seed;
@@ -1569,6 +1569,116 @@ void fmha_mla_cache_append_fp8(const void* latent, int64_t latent_row_stride, co
     } catch (...) {
         fail(9, "internal error in fmha_mla_cache_append_fp8");
     }
+}
+
+}  // extern "C"
+
+namespace {
+
+// The one body of fmha_mla_decode_sparse and fmha_mla_decode_sparse_fp8: every check, the split
+// rule, the scratch and the launch.  The indices are not read here (no sync): the kernel validates
+// every entry against num_blocks * page_block_size.
+void mla_sparse_run(const char* entry, bool fp8, void* q, void* kv_cache, void* o, void* softmax_lse,
+                    void* indices, int64_t indices_batch_stride, int64_t indices_row_stride, int32_t topk,
+                    int32_t seqlen_q, int32_t batch_size, int32_t num_heads, int32_t head_size,
+                    int32_t head_size_v, int32_t num_blocks, int32_t page_block_size, const int64_t* strides,
+                    float softmax_scale, int32_t num_splits, bool is_fp16, hipStream_t stream) {
+    try {
+        begin_fwd();
+        REQUIRE(q && kv_cache && o, "q, kv_cache and o must be non-null device pointers");
+        REQUIRE(indices, "the sparse MLA decode reads its keys through indices: it must be non-null");
+        REQUIRE(strides, "strides must be a non-null pointer (q then o: batch, row, head)");
+        REQUIRE(head_size == 576 && head_size_v == 512,
+                "MLA decode supports (head_size, head_size_v) = (576, 512) only (got (%d, %d))", head_size,
+                head_size_v);
+        REQUIRE(topk >= 1, "topk must be at least 1 (got %d)", topk);
+        REQUIRE(num_blocks >= 1, "num_blocks must be at least 1 (got %d)", num_blocks);
+        REQUIRE(page_block_size > 0 && page_block_size % 16 == 0,
+                "page_block_size must be a positive multiple of 16 (got %d)", page_block_size);
+        REQUIRE(num_heads >= 1 && seqlen_q >= 1,
+                "num_heads and seqlen_q must be at least 1 (got %d, %d)", num_heads, seqlen_q);
+        REQUIRE(batch_size >= 0, "batch size must be non-negative (got %d)", batch_size);
+        REQUIRE(num_splits <= 128, "num_splits must be at most 128 (got %d)", num_splits);
+        const int ext[3] = {batch_size, seqlen_q, num_heads};
+        for (int i = 0; i < 6; ++i)
+            REQUIRE(strides[i] >= 0 && (ext[i % 3] <= 1 || strides[i] % 8 == 0) &&
+                        (i < 3 || ext[i % 3] <= 1 || strides[i] > 0),
+                    "strides must be non-negative multiples of 8 elements (16 bytes), the output's "
+                    "positive: stride %d is %lld", i, (long long)strides[i]);
+        REQUIRE(indices_batch_stride >= 0 && indices_row_stride >= 0,
+                "the indices strides must be non-negative (got %lld, %lld)",
+                (long long)indices_batch_stride, (long long)indices_row_stride);
+        REQUIRE(!((((uintptr_t)q) | ((uintptr_t)kv_cache) | ((uintptr_t)o)) & 15),
+                "q, kv_cache and o must be 16-byte aligned device pointers");
+        REQUIRE(!((((uintptr_t)indices) | ((uintptr_t)softmax_lse)) & 3),
+                "indices and softmax_lse must be 4-byte aligned device pointers");
+        const int64_t row_tiles = (int64_t)seqlen_q * ((num_heads + 15) / 16);
+        REQUIRE((int64_t)seqlen_q * num_heads <= 0x7fffffffLL / 16 &&
+                    (int64_t)batch_size * 128 * row_tiles <= 0x7fffffffLL,
+                "batch_size * seqlen_q * num_heads = %lld is more than one launch covers",
+                (long long)batch_size * seqlen_q * num_heads);
+        if (batch_size == 0) return;
+        MlaParams p{};
+        p.q = q; p.kv = kv_cache; p.o = o; p.lse = (float*)softmax_lse;
+        p.indices = (const int*)indices; p.ind_batch = indices_batch_stride; p.ind_row = indices_row_stride;
+        p.topk = topk; p.num_slots = (int64_t)num_blocks * page_block_size;
+        p.q_batch = strides[0]; p.q_row = strides[1]; p.q_head = strides[2];
+        p.o_batch = strides[3]; p.o_row = strides[4]; p.o_head = strides[5];
+        p.page_size = page_block_size;
+        p.b = batch_size; p.h = num_heads; p.seqlen_q = seqlen_q;
+        p.row_tiles = (int)row_tiles;
+        p.scale_log2 = softmax_scale * kLog2e;
+        p.device = current_device();
+        p.num_cus = num_cus(p.device);
+        // Splits: fmha_mla_decode's rule over these row tiles, at most the index tiles and 128
+        const int tiles = (int)(((int64_t)topk + 31) / 32);
+        int splits = num_splits;
+        if (splits <= 0) {
+            const int64_t units = (int64_t)batch_size * p.row_tiles;
+            splits = (int)std::min<int64_t>(128, (4LL * p.num_cus + units - 1) / units);
+        }
+        splits = std::max(1, std::min(splits, std::min(tiles, 128)));
+        p.num_splits = splits;
+        g_last_splits = splits;
+        if (splits > 1) {
+            const size_t rows = (size_t)batch_size * num_heads * seqlen_q;
+            const size_t obytes = (size_t)splits * rows * 512 * sizeof(float);
+            const size_t lbytes = (size_t)splits * rows * sizeof(float);
+            char* base = (char*)pool_get(stream, obytes + lbytes);
+            if (!base) { fail(3, "could not allocate %zu bytes of split scratch", obytes + lbytes); return; }
+            p.oaccum = (float*)base;
+            p.lseaccum = (float*)(base + obytes);
+        }
+        hip_ok(launch_mla_decode_sparse(p, fp8, is_fp16, stream), "sparse MLA decode launch");
+    } catch (...) {
+        fail(9, "internal error in %s", entry);
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+void fmha_mla_decode_sparse(void* q, void* kv_cache, void* o, void* softmax_lse, void* indices,
+                            int64_t indices_batch_stride, int64_t indices_row_stride, int32_t topk,
+                            int32_t seqlen_q, int32_t batch_size, int32_t num_heads, int32_t head_size,
+                            int32_t head_size_v, int32_t num_blocks, int32_t page_block_size,
+                            const int64_t* strides, float softmax_scale, int32_t num_splits, bool is_fp16,
+                            hipStream_t stream) {
+    mla_sparse_run("fmha_mla_decode_sparse", false, q, kv_cache, o, softmax_lse, indices, indices_batch_stride,
+                   indices_row_stride, topk, seqlen_q, batch_size, num_heads, head_size, head_size_v,
+                   num_blocks, page_block_size, strides, softmax_scale, num_splits, is_fp16, stream);
+}
+
+void fmha_mla_decode_sparse_fp8(void* q, void* kv_cache8, void* o, void* softmax_lse, void* indices,
+                                int64_t indices_batch_stride, int64_t indices_row_stride, int32_t topk,
+                                int32_t seqlen_q, int32_t batch_size, int32_t num_heads, int32_t head_size,
+                                int32_t head_size_v, int32_t num_blocks, int32_t page_block_size,
+                                const int64_t* strides, float softmax_scale, int32_t num_splits, bool is_fp16,
+                                hipStream_t stream) {
+    mla_sparse_run("fmha_mla_decode_sparse_fp8", true, q, kv_cache8, o, softmax_lse, indices,
+                   indices_batch_stride, indices_row_stride, topk, seqlen_q, batch_size, num_heads, head_size,
+                   head_size_v, num_blocks, page_block_size, strides, softmax_scale, num_splits, is_fp16, stream);
 }
 
 }  // extern "C"

@@ -252,6 +252,14 @@ struct MlaParams {
     int causal;
     float scale_log2;
     int num_cus, device;
+    // the sparse decode (fmha_mla_decode_sparse_kernel.h): keys are the cache rows at the valid
+    // entries of indices[b, pos, 0 .. topk) (physical slots, valid iff 0 <= entry < num_slots);
+    // block_table, cache_seqlens, max_seqlen_k and causal are unused, and
+    // row_tiles = seqlen_q * ceil(h / 16)
+    const int* indices;        // int32 [b, seqlen_q, topk], last dimension contiguous
+    int64_t ind_batch, ind_row;  // its strides, in elements
+    int64_t num_slots;         // num_blocks * page_size
+    int topk;
 };
 
 struct BwdParams {

@@ -276,6 +276,9 @@ hipError_t launch_merge_states(const MergeParams& p, bool fp16, hipStream_t st);
 hipError_t launch_mla_decode(const MlaParams& p, bool fp16, hipStream_t st);
 // ... and over an fp8 latent cache (p.kv: rows of 656 bytes, fmha_mla_decode_fp8_kernel.h)
 hipError_t launch_mla_decode_fp8(const MlaParams& p, bool fp16, hipStream_t st);
+// ... and over index-selected tokens of either cache (p.indices, fmha_mla_decode_sparse_kernel.h
+// and fmha_mla_decode_sparse_fp8_kernel.h)
+hipError_t launch_mla_decode_sparse(const MlaParams& p, bool fp8, bool fp16, hipStream_t st);
 
 // Append to an fp8 latent cache (fmha_append.hip): token t's 512 latent features, quantised per
 // 128-feature group, and its 64 rotary features, copied, into the 656-byte row slot[t] of the

@@ -1,17 +1,20 @@
 // fmha_mla.hip — MLA decode over a paged latent cache (fmha_mla_decode): the decode kernel
 // (fmha_mla_decode_kernel.h) for bf16 and fp16, its twin over an fp8 latent cache
-// (fmha_mla_decode_fp8, fmha_mla_decode_fp8_kernel.h), and the split combine at head size 512
+// (fmha_mla_decode_fp8, fmha_mla_decode_fp8_kernel.h), the two over index-selected tokens
+// (fmha_mla_decode_sparse[_fp8], fmha_mla_decode_sparse[_fp8]_kernel.h), and the split combine at head size 512
 // (fmha_combine_kernel<512, T>, the forward's template, instantiated here).  A translation unit of
 // its own: the kernels run one wave per SIMD with 147,456 B of LDS, unlike anything in
 // fmha_fwd.hip.
 #include "fmha_fwd_kernel.h"
 #include "fmha_mla_decode_kernel.h"
 #include "fmha_mla_decode_fp8_kernel.h"
+#include "fmha_mla_decode_sparse_kernel.h"
+#include "fmha_mla_decode_sparse_fp8_kernel.h"
 #include "fmha_launch.h"
 
 namespace xfa {
 
-// kernel: fmha_mla_decode_kernel<T> or fmha_mla_decode_fp8_kernel<T>
+// kernel: fmha_mla_decode_kernel<T>, fmha_mla_decode_fp8_kernel<T> or one of their sparse twins
 template <typename T, void (*kernel)(const MlaParams), int kSmem>
 static hipError_t launch_mla_t(const MlaParams& p, hipStream_t st, const char* tiles, const char* splits) {
     allow_lds<kernel>(p.device, kSmem);
@@ -46,6 +49,17 @@ hipError_t launch_mla_decode_fp8(const MlaParams& p, bool fp16, hipStream_t st) 
     const char *tiles = "fmha_mla_decode_fp8_kernel<tiles>", *splits = "fmha_mla_decode_fp8_kernel<splits>";
     return fp16 ? launch_mla_t<_Float16, fmha_mla_decode_fp8_kernel<_Float16>, kMlaSmem>(p, st, tiles, splits)
                 : launch_mla_t<__bf16, fmha_mla_decode_fp8_kernel<__bf16>, kMlaSmem>(p, st, tiles, splits);
+}
+
+hipError_t launch_mla_decode_sparse(const MlaParams& p, bool fp8, bool fp16, hipStream_t st) {
+    if (fp8) {
+        const char *tiles = "fmha_mla_decode_sparse_fp8_kernel<tiles>", *splits = "fmha_mla_decode_sparse_fp8_kernel<splits>";
+        return fp16 ? launch_mla_t<_Float16, fmha_mla_decode_sparse_fp8_kernel<_Float16>, kMlaSmem>(p, st, tiles, splits)
+                    : launch_mla_t<__bf16, fmha_mla_decode_sparse_fp8_kernel<__bf16>, kMlaSmem>(p, st, tiles, splits);
+    }
+    const char *tiles = "fmha_mla_decode_sparse_kernel<tiles>", *splits = "fmha_mla_decode_sparse_kernel<splits>";
+    return fp16 ? launch_mla_t<_Float16, fmha_mla_decode_sparse_kernel<_Float16>, kMlaSmem>(p, st, tiles, splits)
+                : launch_mla_t<__bf16, fmha_mla_decode_sparse_kernel<__bf16>, kMlaSmem>(p, st, tiles, splits);
 }
 
 }  // namespace xfa

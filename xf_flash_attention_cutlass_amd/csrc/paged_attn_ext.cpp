@@ -1111,6 +1111,18 @@ at::Tensor take_mla_out(const OptTensor& out_, const at::Tensor& q, int head_siz
     return out;
 }
 
+// ... and, for the sparse decode, the indexer's choice: int32 [batch, seqlen_q, topk] of q's batch
+// and seqlen_q, by its own batch and row strides
+void check_mla_indices(const at::Tensor& indices, const at::Tensor& q) {
+    TORCH_CHECK(indices.dtype() == torch::kInt32, "indices must have dtype int32");
+    TORCH_CHECK(indices.is_cuda() && indices.device() == q.device(), "indices must be on q's device");
+    TORCH_CHECK(indices.dim() == 3 && indices.size(0) == q.size(0) && indices.size(1) == q.size(1),
+                "indices must be (batch_size, seqlen_q, topk) with q's batch_size and seqlen_q");
+    TORCH_CHECK(indices.size(2) >= 1, "indices must hold at least one entry per query position (topk >= 1)");
+    TORCH_CHECK(indices.stride(2) == 1 || indices.size(2) == 1, "indices must have contiguous last dimension");
+    TORCH_CHECK(indices.stride(0) >= 0 && indices.stride(1) >= 0, "indices must have non-negative strides");
+}
+
 }  // namespace
 
 // MLA decode over a paged latent cache (fmha_mla_decode; fp8: fmha_mla_decode_fp8 over rows of 656
@@ -1144,6 +1156,36 @@ mha_mla_decode(const at::Tensor& q, const at::Tensor& kv_cache, const at::Tensor
         head_dim_v, page, st, softmax_scale, -1, is_causal ? 0 : -1, num_splits,
         q.dtype() == torch::kFloat16, cur_stream());
     raise_if_failed(kFp8 ? "mla_decode_fp8" : "mla_decode");
+    return {out, lse};
+}
+
+// MLA decode over index-selected tokens (fmha_mla_decode_sparse; fp8: fmha_mla_decode_sparse_fp8):
+// the keys of query (b, pos) are the cache rows at the valid entries of indices[b, pos, :], physical
+// slots block * page + row.  The kernel validates the entries; nothing is copied or synchronised.
+template <bool kFp8>
+std::vector<at::Tensor>
+mha_mla_decode_sparse(const at::Tensor& q, const at::Tensor& kv_cache, const at::Tensor& indices,
+                      const int head_dim_v, const float softmax_scale, const int num_splits,
+                      const OptTensor& out_) {
+    check_mla_q(q);
+    check_mla_cache(kv_cache, q, kFp8);
+    check_mla_indices(indices, q);
+    TORCH_CHECK(head_dim_v == 512, "mla_decode_sparse takes head_dim_v 512, got ", head_dim_v);
+    TORCH_CHECK(kv_cache.size(0) >= 1 && kv_cache.size(1) >= 16, "kv_cache must hold at least one page");
+    TORCH_CHECK(kv_cache.size(0) <= 0x7fffffff && indices.size(2) <= 0x7fffffff, "kv_cache or indices too large");
+    TORCH_CHECK(num_splits <= 128, "num_splits must be at most 128");
+    const int batch = q.size(0), seqlen_q = q.size(1), heads = q.size(2);
+    at::Tensor out = take_mla_out(out_, q, head_dim_v);
+    at::Tensor lse = torch::empty({batch, heads, seqlen_q}, q.options().dtype(torch::kFloat32));
+    if (batch == 0) return {out, lse};
+    const c10::DeviceGuard device_guard(q.device());
+    const int64_t st[6] = {q.stride(0), q.stride(1), q.stride(2), out.stride(0), out.stride(1), out.stride(2)};
+    (kFp8 ? fmha_mla_decode_sparse_fp8 : fmha_mla_decode_sparse)(
+        q.data_ptr(), kv_cache.data_ptr(), out.data_ptr(), lse.data_ptr(), indices.data_ptr(),
+        indices.stride(0), indices.stride(1), (int)indices.size(2), seqlen_q, batch, heads, 576, head_dim_v,
+        (int)kv_cache.size(0), (int)kv_cache.size(1), st, softmax_scale, num_splits,
+        q.dtype() == torch::kFloat16, cur_stream());
+    raise_if_failed(kFp8 ? "mla_decode_sparse_fp8" : "mla_decode_sparse");
     return {out, lse};
 }
 
@@ -1229,12 +1271,21 @@ PYBIND11_MODULE(paged_attn, m) {
           py::arg("is_causal") = false, py::arg("num_splits") = 0, py::arg("out") = py::none());
     m.def("_mla_cache_append_fp8", &mha_mla_cache_append_fp8, "Append tokens to an fp8 paged latent KV cache",
           py::arg("latent"), py::arg("k_pe"), py::arg("kv_cache"), py::arg("slot_mapping"));
+    // ... and the two decodes over index-selected tokens
+    m.def("_mla_decode_sparse", &mha_mla_decode_sparse<false>, "MLA decode over index-selected tokens of a paged latent KV cache",
+          py::arg("q"), py::arg("kv_cache"), py::arg("indices"), py::arg("head_dim_v") = 512,
+          py::arg("softmax_scale") = 0.041666666666666664f, py::arg("num_splits") = 0, py::arg("out") = py::none());
+    m.def("_mla_decode_sparse_fp8", &mha_mla_decode_sparse<true>, "MLA decode over index-selected tokens of an fp8 paged latent KV cache",
+          py::arg("q"), py::arg("kv_cache"), py::arg("indices"), py::arg("head_dim_v") = 512,
+          py::arg("softmax_scale") = 0.041666666666666664f, py::arg("num_splits") = 0, py::arg("out") = py::none());
     const py::handle self = m;
     m.def("__getattr__", [self](const std::string& name) -> py::object {
         if (name == "merge_states") return self.attr("_merge_states");
         if (name == "mla_decode") return self.attr("_mla_decode");
         if (name == "mla_decode_fp8") return self.attr("_mla_decode_fp8");
         if (name == "mla_cache_append_fp8") return self.attr("_mla_cache_append_fp8");
+        if (name == "mla_decode_sparse") return self.attr("_mla_decode_sparse");
+        if (name == "mla_decode_sparse_fp8") return self.attr("_mla_decode_sparse_fp8");
         PyErr_SetString(PyExc_AttributeError, ("module 'paged_attn' has no attribute '" + name + "'").c_str());
         throw py::error_already_set();
     });

@@ -143,7 +143,7 @@ mla_fp8_cache_row_bytes = 656      # one token of an fp8 latent cache (flash_mla
 
 
 def flash_mla_with_kvcache(q, kv_cache, block_table, cache_seqlens, head_dim_v=512,
-                           softmax_scale=None, causal=False, num_splits=0, out=None):
+                           softmax_scale=None, causal=False, num_splits=0, out=None, *, indices=None):
     """Decode attention for multi-head latent attention (DeepSeek-V2/V3/R1, Kimi) in its absorbed
     form, over a paged latent KV cache: one HIP launch (`paged_attn.mla_decode`) plus the split
     combine, no copies.
@@ -164,10 +164,29 @@ def flash_mla_with_kvcache(q, kv_cache, block_table, cache_seqlens, head_dim_v=5
     latent features are dequantised to q's dtype (one fp32 product, rounded once) and everything
     else is as above.
 
+    indices (keyword only; FlashMLA's argument of that name, DeepSeek-V3.2's sparse attention):
+    int32 [b, seqlen_q, topk], last dimension contiguous.  Query (b, pos) then attends over exactly
+    the cache rows at the valid entries of indices[b, pos, :], in that order, gathered inside the
+    kernel (`paged_attn.mla_decode_sparse` / `mla_decode_sparse_fp8`).  An entry is a physical
+    slot, block * page_block_size + row (what `mla_cache_append_fp8`'s slot_mapping holds); any
+    value outside [0, num_blocks * page_block_size) - -1 is the usual padding - contributes
+    nothing, and the kernel checks every entry, so no host sync is needed.  block_table and
+    cache_seqlens are not read and may be None; causal=True raises (visibility is the indexer's
+    choice).  A position whose entries are all invalid gives out = 0 and softmax_lse = +inf.
+
     Returns (out [b, seqlen_q, h, 512], softmax_lse fp32 [b, h, seqlen_q]).  Not differentiable."""
     if softmax_scale is None:
         softmax_scale = q.shape[-1] ** (-0.5)
     fp8 = kv_cache.dtype in (torch.uint8, torch.float8_e4m3fn) and kv_cache.shape[-1] == mla_fp8_cache_row_bytes
+    if indices is not None:
+        if causal:
+            raise ValueError("flash_mla_with_kvcache: causal=True cannot be combined with indices "
+                             "(the indexer decides what a position sees)")
+        op = paged_attn.mla_decode_sparse_fp8 if fp8 else paged_attn.mla_decode_sparse
+        with torch.no_grad():
+            o, lse = op(q.detach(), kv_cache.detach(), indices, int(head_dim_v), float(softmax_scale),
+                        int(num_splits), out)
+        return o, lse
     op = paged_attn.mla_decode_fp8 if fp8 else paged_attn.mla_decode
     with torch.no_grad():
         o, lse = op(q.detach(), kv_cache.detach(), block_table, cache_seqlens, int(head_dim_v),
