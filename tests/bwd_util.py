@@ -7,8 +7,9 @@
 * `Arena`: every operand of a C-ABI call as an interior slice of one poisoned byte arena.
 * `capi_bwd`, `capi_varlen_bwd`: fmha_bwd / fmha_varlen_bwd on arena operands with a workspace that
   holds a chosen number of dQ slices.
-* `emulate_bwd`: a CPU model of a correct kernel (fp32 accumulation, P and dS rounded to the input
-  dtype) with plantable defects, for tests/test_bwd_util.py.
+* `emulate_bwd` / `emulate_fwd`: a CPU model of a correct kernel (fp32 accumulation, P and dS
+  rounded to the input dtype) with plantable defects, for tests/test_bwd_util.py; given a forward's
+  stored O and LSE it is the second estimate of tests/bwd_stress_util.py.
 * `instance_table`: the (bucket, dtype, mask, feat, deterministic) cases of
   tests/test_bwd_instances_gpu.py.
 """
@@ -323,20 +324,18 @@ def capi_varlen_bwd(xfa, q, k, v, g, lq, lk, *, causal=False, window=(-1, -1),
 
 
 # ---------------------------------------------------------------- CPU emulation ----------
-def emulate_bwd(q, k, v, g, causal=False, window=(-1, -1), defect=None, softcap=0.0,
-                attn_bias=None, exact_d=False):
-    """A correct kernel's arithmetic on the CPU: fp32 accumulation, O / P / dS rounded to the
-    input dtype before they feed a product, results rounded to the dtype.  `defect` plants one
-    tiling bug: 'dk_block', 'dq_tail', 'dq_twice' or 'dv_lastkey' (tests/test_bwd_util.py).
-    D = rowsum(dO * O) uses the forward's O as stored, i.e. rounded to the dtype, as every
-    flash-attention backward does; `exact_d` takes the unrounded O instead (to size that term)."""
-    dt = q.dtype
+DEFECT_ROWS = slice(32, 64)                       # the query rows the D / mask defects touch
+DEFECTS = ("dk_block", "dq_tail", "dq_twice", "dv_lastkey",
+           "d_neighbour", "d_zero", "unmasked_block", "lse_as_d")
+
+
+def _emulate_scores(q, k, causal, window, softcap, attn_bias, sink):
+    """fp32 scores of the emulation: (s masked, s before the mask, d softcap / d s, lse
+    [b, h, sq, 1] with +inf on rows without a visible key).  sink [h]: joins the LSE only."""
     b, sq, h, d = q.shape
-    sk, hk = k.shape[1], k.shape[2]
-    G = h // hk
+    sk = k.shape[1]
     scale = d ** -0.5
-    qf, gf = q.float(), g.float()
-    kf, vf = orc.expand_kv(k, h).float(), orc.expand_kv(v, h).float()
+    qf, kf = q.float(), orc.expand_kv(k, h).float()
     s = torch.einsum("bthd,bshd->bhts", qf, kf) * scale
     dcap = 1.0
     if softcap > 0:
@@ -348,15 +347,69 @@ def emulate_bwd(q, k, v, g, causal=False, window=(-1, -1), defect=None, softcap=
     masked = torch.zeros(sq, sk, dtype=torch.bool)
     if w[0] >= 0 or w[1] >= 0:
         masked = orc.local_mask(sq, sk, w)
+    raw = s
     s = s.masked_fill(masked, float("-inf"))
     lse = torch.logsumexp(s, -1, keepdim=True)
+    if sink is not None:
+        dead = torch.isneginf(lse)
+        lse = torch.logaddexp(lse, sink.float().view(1, h, 1, 1).expand_as(lse))
+        lse = torch.where(dead, torch.full_like(lse, float("-inf")), lse)
     lse = torch.where(torch.isneginf(lse), torch.full_like(lse, float("inf")), lse)
+    return s, raw, dcap, lse
+
+
+def emulate_fwd(q, k, v, causal=False, window=(-1, -1), softcap=0.0, attn_bias=None, sink=None):
+    """The (O in the input dtype, LSE [b, h, sq] fp32) that `emulate_bwd` takes D and P from when
+    it is given none."""
+    s, _, _, lse = _emulate_scores(q, k, causal, window, softcap, attn_bias, sink)
+    p16 = torch.exp(s - lse).to(q.dtype).float()
+    o = torch.einsum("bhts,bshd->bthd", p16, orc.expand_kv(v, q.shape[2]).float())
+    return o.to(q.dtype), lse.squeeze(-1)
+
+
+def emulate_bwd(q, k, v, g, causal=False, window=(-1, -1), defect=None, softcap=0.0,
+                attn_bias=None, exact_d=False, o=None, lse=None, sink=None):
+    """A correct kernel's arithmetic on the CPU: fp32 accumulation, O / P / dS rounded to the
+    input dtype before they feed a product, results rounded to the dtype.  `defect` plants one
+    bug (DEFECTS): the tiling ones 'dk_block', 'dq_tail', 'dq_twice', 'dv_lastkey'
+    (tests/test_bwd_util.py), and on query rows 32..63 'd_neighbour' (D of row r - 1), 'd_zero'
+    (D ignored), 'lse_as_d' (the row's LSE in D's place) and, causal only, 'unmasked_block' (the
+    32 x 32 block at keys sk - sq + 64 .. + 95 visible in P against the masked LSE)
+    (tests/test_bwd_stress_util.py).
+    D = rowsum(dO * O) uses the forward's O as stored, i.e. rounded to the dtype, as every
+    flash-attention backward does; `exact_d` takes the unrounded O instead (to size that term).
+    `o` [b, sq, h, d] / `lse` [b, h, sq]: a forward's stored O and LSE in place of the
+    emulation's own, in D and in P = exp(S - LSE) (`emulate_fwd` gives the defaults).  `sink`
+    [h]: a per-head sink logit in the LSE."""
+    dt = q.dtype
+    b, sq, h, d = q.shape
+    sk, hk = k.shape[1], k.shape[2]
+    G = h // hk
+    scale = d ** -0.5
+    qf, gf = q.float(), g.float()
+    kf, vf = orc.expand_kv(k, h).float(), orc.expand_kv(v, h).float()
+    s, raw, dcap, own_lse = _emulate_scores(q, k, causal, window, softcap, attn_bias, sink)
+    lse = own_lse if lse is None else lse.float().unsqueeze(-1)
     p = torch.exp(s - lse)                                           # [b, h, sq, sk]
+    R = DEFECT_ROWS
+    if defect == "unmasked_block":
+        assert causal, "unmasked_block needs a causal mask"
+        c0 = sk - sq + 64
+        p = p.clone()
+        p[:, :, R, c0:c0 + 32] = torch.exp(raw[:, :, R, c0:c0 + 32] - lse[:, :, R])
     p16 = p.to(dt).float()
-    o = torch.einsum("bhts,bshd->bthd", p16, vf)
-    if not exact_d:
-        o = o.to(dt).float()
+    if o is None:
+        o = torch.einsum("bhts,bshd->bthd", p16, vf)
+        if not exact_d:
+            o = o.to(dt).float()
+    else:
+        o = o.float()
     dsum = (gf * o).sum(-1).permute(0, 2, 1).unsqueeze(-1)           # [b, h, sq, 1]
+    if defect in ("d_neighbour", "d_zero", "lse_as_d"):
+        dsum = dsum.clone()
+        n = dsum[:, :, R].shape[2]                # (fewer than 32 where the rows end inside)
+        dsum[:, :, R] = {"d_neighbour": dsum[:, :, R.start - 1:R.start - 1 + n].clone(),
+                         "d_zero": torch.zeros_like(dsum[:, :, R]), "lse_as_d": lse[:, :, R]}[defect]
     dp = torch.einsum("bthd,bshd->bhts", gf, vf)
     ds16 = (p * (dp - dsum) * dcap).to(dt).float()
     bn = 128 if d > 128 else 256
@@ -370,7 +423,7 @@ def emulate_bwd(q, k, v, g, causal=False, window=(-1, -1), defect=None, softcap=
     elif defect == "dv_lastkey":                  # the last key's P column missing from dV
         p_dv = p16.clone()
         p_dv[..., sk - 1] = 0
-    elif defect not in (None, "dq_twice"):
+    elif defect is not None and defect not in DEFECTS:
         raise ValueError(defect)
     dq = torch.einsum("bhts,bshd->bthd", ds_dq, kf)
     if defect == "dq_twice":                      # one key block added twice into one dQ tile

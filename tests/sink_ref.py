@@ -12,6 +12,8 @@ the project's pass rules.  Autograd through it gives the reference gradients.
 * `dsink_formula`: -sum exp(s - LSE) D.
 * `sink_values`: per-head values that differ, with one head at +20 and one at -inf.
 * `fwd_refs` / `check_fwd`: float64 reference, low-precision estimate and the forward rules.
+* `grad_refs`, `dsink_term`, `check_dsink`: the reference gradients and the dsink rule of
+  tests/test_sink_bwd_gpu.py (shared with tests/test_bwd_stress_gpu.py).
 """
 from __future__ import annotations
 
@@ -156,3 +158,44 @@ def check_fwd(name, o, lse, refs: FwdRefs, dtype, report=None, mult=2.0, atol=0.
     assert err <= bound, f"{name}: max|O - ref| = {err:.3e} > {bound:.3e}"
     assert inf_ok, f"{name}: the LSE's +inf rows differ from the reference's"
     assert lse_err <= LSE_ATOL, f"{name}: LSE off by {lse_err:.3e}"
+
+
+# ---------------------------------------------------------------- backward ---------------
+def _ref_grads(fn, q, k, v, go, sink, cast, reorder):
+    """Gradients (dq, dk, dv, dsink) and (out, lse) of `fn` (a sink_ref forward) over inputs cast
+    by `cast`."""
+    qq, kk, vv, ss = (cast(x).clone().requires_grad_(True) for x in (q, k, v, sink))
+    out, lse = fn(qq, kk, vv, ss, reorder_ops=reorder)
+    grads = torch.autograd.grad(out, (qq, kk, vv, ss), cast(go))
+    return grads, out.detach(), lse.detach()
+
+
+def grad_refs(fn, q, k, v, go, sink, dtype=torch.bfloat16):
+    """(bwd_util.Refs of (dq, dk, dv), dsink ref64, dsink pt, out64, lse64) of `fn`, a sink_ref
+    forward taking (q, k, v, sink, reorder_ops=)."""
+    from tests.bwd_util import Refs
+    g64, o64, l64 = _ref_grads(fn, q, k, v, go, sink, lambda x: x.double(), False)
+    g32, _, _ = _ref_grads(fn, q, k, v, go, sink, lambda x: x.float(), False)
+    gpt, _, _ = _ref_grads(fn, q, k, v, go, sink, lambda x: x.to(dtype), True)
+    refs = Refs(g64[:3], tuple(x.to(dtype) for x in g32[:3]), gpt[:3])
+    return refs, g64[3], gpt[3].double(), o64, l64
+
+
+def dsink_term(sink, lse64, go, o64, dtype=torch.bfloat16):
+    """eps / 2 * sum_rows exp(s - LSE) sum_d |dO O| per head; lse64 [h, rows], go / o64
+    [rows, h, d]."""
+    w = torch.exp(sink.double().view(-1, 1) - lse64)               # [h, rows]
+    a = (go.double() * o64).abs().sum(-1)                          # [rows, h]
+    return 0.5 * EPS[dtype] * (w * a.transpose(0, 1)).sum(1)
+
+
+def check_dsink(name, dsink, ref64, pt, term, report):
+    dsink = dsink.double().cpu()
+    assert torch.isfinite(dsink).all(), f"{name}: dsink not finite"
+    err = (dsink - ref64).abs()
+    bound = 3.0 * (pt - ref64).abs() + term + 1e-5
+    ratio = err / bound
+    print(f"{name}: dsink {dsink.tolist()} ref {ref64.tolist()} ratios {[round(x, 3) for x in ratio.tolist()]}")
+    i = int(ratio.argmax())
+    report(dict(case=name, metric="dsink", err=err[i].item(), bound=bound[i].item(), head=i))
+    assert bool((ratio <= 1.0).all()), f"{name}: dsink err {err.tolist()} > bound {bound.tolist()}"

@@ -37,44 +37,6 @@ def _inputs(b, s, h, hk, d, seed):
     return q, k, v, go
 
 
-def _ref_grads(fn, q, k, v, go, sink, cast, reorder):
-    """Gradients (dq, dk, dv, dsink) and (out, lse) of `fn` (a sink_ref forward) over inputs cast
-    by `cast`."""
-    qq, kk, vv, ss = (cast(x).clone().requires_grad_(True) for x in (q, k, v, sink))
-    out, lse = fn(qq, kk, vv, ss, reorder_ops=reorder)
-    grads = torch.autograd.grad(out, (qq, kk, vv, ss), cast(go))
-    return grads, out.detach(), lse.detach()
-
-
-def _all_refs(fn, q, k, v, go, sink):
-    """(Refs of (dq, dk, dv), dsink ref64, dsink pt, the derived dsink term)."""
-    g64, o64, l64 = _ref_grads(fn, q, k, v, go, sink, lambda x: x.double(), False)
-    g32, _, _ = _ref_grads(fn, q, k, v, go, sink, lambda x: x.float(), False)
-    gpt, _, _ = _ref_grads(fn, q, k, v, go, sink, lambda x: x.to(BF), True)
-    refs = bu.Refs(g64[:3], tuple(x.to(BF) for x in g32[:3]), gpt[:3])
-    return refs, g64[3], gpt[3].double(), o64, l64
-
-
-def _dsink_term(sink, lse64, go, o64):
-    """eps / 2 * sum_rows exp(s - LSE) sum_d |dO O| per head; lse64 [h, rows], go / o64
-    [rows, h, d]."""
-    w = torch.exp(sink.double().view(-1, 1) - lse64)               # [h, rows]
-    a = (go.double() * o64).abs().sum(-1)                          # [rows, h]
-    return 0.5 * bu.EPS[BF] * (w * a.transpose(0, 1)).sum(1)
-
-
-def _check_dsink(name, dsink, ref64, pt, term, report):
-    dsink = dsink.double().cpu()
-    assert torch.isfinite(dsink).all(), f"{name}: dsink not finite"
-    err = (dsink - ref64).abs()
-    bound = 3.0 * (pt - ref64).abs() + term + 1e-5
-    ratio = err / bound
-    print(f"{name}: dsink {dsink.tolist()} ref {ref64.tolist()} ratios {[round(x, 3) for x in ratio.tolist()]}")
-    i = int(ratio.argmax())
-    report(dict(case=name, metric="dsink", err=err[i].item(), bound=bound[i].item(), head=i))
-    assert bool((ratio <= 1.0).all()), f"{name}: dsink err {err.tolist()} > bound {bound.tolist()}"
-
-
 DENSE = {"d64_causal": (64, dict(causal=True)), "d128_window100_0": (128, dict(window=(100, 0)))}
 
 
@@ -85,7 +47,7 @@ def test_dense_backward_with_sink(xfa, parity_report, case, deterministic):
     q, k, v, go = _inputs(2, 130, 4, 2, d, 71 + d)
     sink = sr.sink_values(4)
     fn = lambda a, b_, c, s, reorder_ops: sr.sink_attention(a, b_, c, s, reorder_ops=reorder_ops, **mask)
-    refs, ds64, dspt, o64, l64 = _all_refs(fn, q, k, v, go, sink)
+    refs, ds64, dspt, o64, l64 = sr.grad_refs(fn, q, k, v, go, sink)
     qd, kd, vd = (x.to(DEV).requires_grad_(True) for x in (q, k, v))
     sd = sink.to(DEV).requires_grad_(True)
     kw = dict(causal=mask.get("causal", False), window_size=mask.get("window", (-1, -1)))
@@ -94,8 +56,8 @@ def test_dense_backward_with_sink(xfa, parity_report, case, deterministic):
     (dsink2,) = torch.autograd.grad(out, (sd,), go.to(DEV))
     name = f"sink bwd {case} det={deterministic}"
     bu.check_grads(name, (dq, dk, dv), refs, BF, parity_report)
-    term = sum(_dsink_term(sink, l64[i], go[i], o64[i]) for i in range(q.shape[0]))
-    _check_dsink(name, dsink, ds64, dspt, term, parity_report)
+    term = sum(sr.dsink_term(sink, l64[i], go[i], o64[i]) for i in range(q.shape[0]))
+    sr.check_dsink(name, dsink, ds64, dspt, term, parity_report)
     assert dsink.dtype == sink.dtype and torch.equal(dsink.view(torch.int32), dsink2.view(torch.int32))
 
 
@@ -106,7 +68,7 @@ def test_varlen_backward_with_sink(xfa, parity_report, deterministic):
     sink = sr.sink_values(4)
     fn = lambda a, b_, c, s, reorder_ops: sr.sink_attention_varlen(a, b_, c, s, lens, lens, causal=True,
                                                                    reorder_ops=reorder_ops)
-    refs, ds64, dspt, o64, l64 = _all_refs(fn, q, k, v, go, sink)
+    refs, ds64, dspt, o64, l64 = sr.grad_refs(fn, q, k, v, go, sink)
     cu = torch.tensor([0] + list(itertools.accumulate(lens)), dtype=torch.int32, device=DEV)
     qd, kd, vd = (x.to(DEV).requires_grad_(True) for x in (q, k, v))
     sd = sink.to(DEV).requires_grad_(True)
@@ -120,7 +82,7 @@ def test_varlen_backward_with_sink(xfa, parity_report, deterministic):
         seq = bu.Refs(*(tuple(x[sl][None] for x in r) for r in refs))
         bu.check_grads(name, tuple(x[sl][None] for x in (dq, dk, dv)), seq, BF, worst)
     worst.flush(parity_report)
-    _check_dsink(name, dsink, ds64, dspt, _dsink_term(sink, l64, go, o64), parity_report)
+    sr.check_dsink(name, dsink, ds64, dspt, sr.dsink_term(sink, l64, go, o64), parity_report)
     assert torch.equal(dsink.view(torch.int32), dsink2.view(torch.int32))
 
 
