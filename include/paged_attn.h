@@ -127,7 +127,7 @@ void fmha_set_rng_state(uint64_t seed, uint64_t offset);
 void fmha_set_rng_state_device(const int64_t* seed_ptr, const int64_t* offset_ptr,
                                uint64_t offset_add, int64_t* rng_out);
 
-/* Library version / build identification, e.g. "xf-fmha-gfx950 2.11".  2.0 (round 3) changed
+/* Library version / build identification, e.g. "xf-fmha-gfx950 2.12".  2.0 (round 3) changed
  * argument lists of existing symbols; 2.1 exports those under _v2 names (see INTEGRATION.md
  * "ABI history"). */
 const char* fmha_version(void);
@@ -598,6 +598,51 @@ void fmha_mla_decode_sparse_fp8(void* q, void* kv_cache8, void* o, void* softmax
                                 int32_t num_blocks, int32_t page_block_size,
                                 const int64_t* strides /* q then o: batch,row,head */,
                                 float softmax_scale, int32_t num_splits, bool is_fp16, hipStream_t stream);
+
+/* ------------------------- MLA prefill: head size 192 for Q K^T, 128 for V (2.12) */
+
+/* The prefill half of multi-head latent attention in its un-absorbed form (DeepSeek-V2/V3/R1,
+ * Kimi): q and k carry 192 features a head (128 "nope" + 64 rotary), v and o 128.
+ *   S = softmax_scale q K^T over all 192 features, O = softmax(S) V, LSE = logsumexp(S) in fp32.
+ * One pass of fmha_fwd_mla_kernel (fmha_last_kernel() names it with its schedule); no ALiBi,
+ * softcap, dropout, sink, paged or fp8 K/V and no KV split.  Windows as every forward here:
+ * bottom-right aligned, causal <=> (-1, 0); a row without a visible key gives O = 0 and
+ * LSE = +inf.  GQA: num_heads % num_heads_k == 0.  The default softmax_scale of the models is
+ * 192^-1/2 (possibly times a YaRN factor); it is the caller's.
+ * Nothing is copied or padded: every tensor goes by its own strides, in ELEMENTS, last dimension
+ * contiguous; V's row and head pitch are independent of K's.  Loads go through descriptors sized
+ * to each sequence: nothing outside a sequence's rows and columns reaches a result, and nothing
+ * but o's and softmax_lse's own elements is written.  No scratch and no host sync; the first
+ * forward call on a stream allocates that stream's item-queue counters, so warm a stream up
+ * before capturing a graph on it.
+ *
+ * fmha_fwd_mla: dense q [batch, seqlen_q, heads, 192], k [batch, seqlen_k, heads_k, 192],
+ * v [batch, seqlen_k, heads_k, 128], o [batch, seqlen_q, heads, 128]; strides[12] = {batch, row,
+ * head} of q, k, v, o; softmax_lse fp32 [batch, heads, seqlen_q] contiguous, or NULL.
+ *
+ * fmha_varlen_fwd_mla: packed q [total_q, heads, 192], k [total_k, heads_k, 192], v [total_k,
+ * heads_k, 128], o [total_q, heads, 128]; strides[8] = {row, head} of q, k, v, o; cu_seqlens_q /
+ * cu_seqlens_k int32 [batch + 1]; seqused_k int32 [batch] or NULL: the keys of sequence b are the
+ * first seqused_k[b] rows at cu_seqlens_k[b]; softmax_lse fp32 [heads, total_q], or NULL.  A
+ * sequence without keys (or without queries) is fine; max_seqlen_k == 0 is refused.
+ *
+ * Refused with an error, outputs untouched: (head_size_qk, head_size_v) other than (192, 128); a
+ * NULL q / k / v / o / strides (varlen: cu_seqlens_q / cu_seqlens_k); batch_size < 1;
+ * num_heads % num_heads_k != 0; q / k / v / o not 16-byte aligned; a stride that is negative or,
+ * over an extent above 1, no multiple of 8; a k (v) row stride below 192 (128); non-positive
+ * lengths; one sequence's slab beyond the 32-bit offset limit. */
+void fmha_fwd_mla(void* q, void* k, void* v, void* o, void* softmax_lse,
+                  int32_t seqlen_q, int32_t seqlen_k, int32_t batch_size, int32_t num_heads,
+                  int32_t num_heads_k, int32_t head_size_qk /* 192 */, int32_t head_size_v /* 128 */,
+                  const int64_t* strides /* q, k, v, o: batch,row,head */, float softmax_scale,
+                  int window_size_left, int window_size_right, bool is_fp16, hipStream_t stream);
+void fmha_varlen_fwd_mla(void* q, void* k, void* v, void* o, void* softmax_lse,
+                         void* cu_seqlens_q, void* cu_seqlens_k, void* seqused_k /* nullable */,
+                         int32_t max_seqlen_q, int32_t max_seqlen_k, int32_t total_q,
+                         int32_t batch_size, int32_t num_heads, int32_t num_heads_k,
+                         int32_t head_size_qk /* 192 */, int32_t head_size_v /* 128 */,
+                         const int64_t* strides /* q, k, v, o: row,head */, float softmax_scale,
+                         int window_size_left, int window_size_right, bool is_fp16, hipStream_t stream);
 
 #ifdef __cplusplus
 } /* extern "C" */

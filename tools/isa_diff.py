@@ -40,6 +40,9 @@ def units(tree):
             ("fmha_fwd_fp8", "fmha_fwd_fp8.hip", []), ("fmha_api", "fmha_api.cpp", []),
             ("fmha_merge", "fmha_merge.hip", []),
             ("fmha_mla", "fmha_mla.hip", ["-mllvm", "-amdgpu-mfma-vgpr-form"])]   # (build.py's flag)
+    if os.path.exists(os.path.join(b.CSRC, "fmha_fwd_mla.hip")):      # (trees from 2.12 on)
+        tus += [(f"fmha_fwd_mla_{dt}", "fmha_fwd_mla.hip", [f"-DXFA_DTN={dt}", f"-DXFA_DT_BF16={int(dt == 'bf16')}"])
+                for dt in ("bf16", "f16")]
     tus += [(n + "+variants", src, d + ["-DXFA_VARIANTS=1"]) for n, src, d in tus if n + ".o" in b.VARIANT_TUS]
     return b, tus
 

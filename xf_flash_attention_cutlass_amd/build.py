@@ -120,6 +120,11 @@ def build_lib(jobs: int = 8, force: bool = False, verbose: bool = False, variant
     todo.append((os.path.join(CSRC, "fmha_mla.hip"), os.path.join(OBJ, "fmha_mla.o"),
                  ["-mllvm", "-amdgpu-mfma-vgpr-form"]))
     todo.append((os.path.join(CSRC, "fmha_fwd_fp8.hip"), os.path.join(OBJ, "fmha_fwd_fp8.o"), []))
+    # the MLA prefill forward (d_qk 192, d_v 128): a translation unit of its own per dtype, so the
+    # code objects of the other forwards stay as they are
+    for dt in ("bf16", "f16"):
+        todo.append((os.path.join(CSRC, "fmha_fwd_mla.hip"), os.path.join(OBJ, f"fmha_fwd_mla_{dt}.o"),
+                     [f"-DXFA_DTN={dt}", f"-DXFA_DT_BF16={1 if dt == 'bf16' else 0}"]))
     todo.append((os.path.join(CSRC, "fmha_api.cpp"), os.path.join(OBJ, "fmha_api.o"), []))
     if variants:
         todo = [(src, os.path.join(obj_dir, os.path.basename(out)), defs + ["-DXFA_VARIANTS=1"])

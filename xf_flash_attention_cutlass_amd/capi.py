@@ -74,6 +74,10 @@ _SIGS = {
                                i32, C.POINTER(C.c_int64), f32, i32, b_, vp],
     "fmha_mla_decode_sparse_fp8": [vp, vp, vp, vp, vp, C.c_int64, C.c_int64, i32, i32, i32, i32, i32, i32,
                                    i32, i32, C.POINTER(C.c_int64), f32, i32, b_, vp],
+    "fmha_fwd_mla": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, C.POINTER(C.c_int64), f32,
+                     C.c_int, C.c_int, b_, vp],
+    "fmha_varlen_fwd_mla": [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32,
+                            C.POINTER(C.c_int64), f32, C.c_int, C.c_int, b_, vp],
     "fmha_last_error": [],
     "fmha_last_status": [],
     "fmha_last_num_splits": [],

@@ -525,7 +525,7 @@ const char* fmha_last_error(void) { return g_err.c_str(); }
 int fmha_last_status(void) { return g_status; }
 int fmha_last_num_splits(void) { return g_last_splits; }
 const char* fmha_last_kernel(void) { return g_last_kernel; }
-const char* fmha_version(void) { return XFA_VARIANTS ? "xf-fmha-gfx950 2.11 (variants)" : "xf-fmha-gfx950 2.11"; }
+const char* fmha_version(void) { return XFA_VARIANTS ? "xf-fmha-gfx950 2.12 (variants)" : "xf-fmha-gfx950 2.12"; }
 
 void fmha_set_rng_state(uint64_t seed, uint64_t offset) {
     g_seed = seed;
@@ -1679,6 +1679,125 @@ void fmha_mla_decode_sparse_fp8(void* q, void* kv_cache8, void* o, void* softmax
     mla_sparse_run("fmha_mla_decode_sparse_fp8", true, q, kv_cache8, o, softmax_lse, indices,
                    indices_batch_stride, indices_row_stride, topk, seqlen_q, batch_size, num_heads, head_size,
                    head_size_v, num_blocks, page_block_size, strides, softmax_scale, num_splits, is_fp16, stream);
+}
+
+}  // extern "C"
+
+namespace {
+
+// ---- MLA prefill: fmha_fwd_mla and fmha_varlen_fwd_mla -------------------------------------
+// The pair of head sizes, then the tensors' own strides (q, k, v, o in that order, `per` strides
+// each: batch / row / head, or row / head): non-negative, multiples of 8 elements where the
+// extent is not 1, K and V rows at least a head apart (a shorter pitch would let the rows past a
+// sequence's end alias its own), and one sequence's slab within the 32-bit offsets.
+bool check_mla_pair(int head_size_qk, int head_size_v) {
+    return (head_size_qk == 192 && head_size_v == 128) ||
+           fail(1, "MLA prefill supports (head_size_qk, head_size_v) = (192, 128) only (got (%d, %d))",
+                head_size_qk, head_size_v);
+}
+bool check_mla_strides(const int64_t* st, int per, int batch, int rows_q, int rows_k, int h, int hk) {
+    if (!st) return fail(1, "strides must be non-null");
+    static const char* const kName[4] = {"q", "k", "v", "o"};
+    for (int t = 0; t < 4; ++t) {
+        const int rows = (t == 0 || t == 3) ? rows_q : rows_k;
+        const int heads = (t == 0 || t == 3) ? h : hk;
+        const int width = (t == 0 || t == 1) ? 192 : 128;
+        const int64_t* s = st + t * per;
+        const int64_t row = s[per - 2], head = s[per - 1];
+        const int ext[3] = {batch, rows, heads};
+        for (int i = 0; i < per; ++i) {
+            if (s[i] < 0) return fail(1, "strides must be non-negative: %s stride %d is %lld", kName[t], i, (long long)s[i]);
+            if (ext[3 - per + i] != 1 && s[i] % 8 != 0)
+                return fail(1, "strides must be multiples of 8 elements (16 bytes): %s stride %d is %lld",
+                            kName[t], i, (long long)s[i]);
+        }
+        if ((t == 1 || t == 2) && rows > 1 && row < width)
+            return fail(1, "%s row stride must be at least its head size %d (got %lld)", kName[t], width, (long long)row);
+        const int64_t bytes = ((int64_t)(rows - 1) * row + (int64_t)(heads - 1) * head + width) * 2;
+        if (bytes >= kMaxSlabBytes)
+            return fail(1, "%s: one sequence spans %lld bytes; this build addresses a sequence with "
+                        "32-bit offsets and supports < %lld bytes", kName[t], (long long)bytes,
+                        (long long)kMaxSlabBytes);
+    }
+    return true;
+}
+// the launch: the schedule knobs every forward shares, one pass, the item queue as run_fwd takes it
+// (fwd_dyn >= 1 for packed launches, 2 for dense ones)
+void run_fwd_mla(FwdParams& p, bool bf16, hipStream_t st) {
+    Options& o = options();
+    load_schedule(p, o.fwd_w4, bf16 ? 16 : 15);
+    p.prio_hi = o.fwd_prio.load();
+    p.pipe = o.fwd_pipe.load();
+    p.num_splits = 1;
+    g_last_splits = 1;
+    if (!take_item_queue(p, st, p.cu_seqlens_q ? 1 : 2, 3)) return;
+    hip_ok(bf16 ? launch_fwd_mla_bf16(p, st) : launch_fwd_mla_f16(p, st), "MLA prefill launch");
+}
+
+}  // namespace
+
+extern "C" {
+
+void fmha_fwd_mla(void* q, void* k, void* v, void* o, void* softmax_lse, int32_t seqlen_q,
+                  int32_t seqlen_k, int32_t batch_size, int32_t num_heads, int32_t num_heads_k,
+                  int32_t head_size_qk, int32_t head_size_v, const int64_t* strides,
+                  float softmax_scale, int window_size_left, int window_size_right, bool is_fp16,
+                  hipStream_t stream) {
+    try {
+        begin_fwd();
+        if (!check_mla_pair(head_size_qk, head_size_v)) return;
+        if (!check_common(q, k, v, o, batch_size, num_heads, num_heads_k, head_size_qk)) return;
+        REQUIRE(seqlen_q > 0 && seqlen_k > 0, "seqlen_q/seqlen_k must be positive (%d, %d)", seqlen_q, seqlen_k);
+        REQUIRE(!(((uintptr_t)softmax_lse) & 3), "softmax_lse must be a 4-byte aligned device pointer");
+        if (!check_mla_strides(strides, 3, batch_size, seqlen_q, seqlen_k, num_heads, num_heads_k)) return;
+        FwdParams p{};
+        fwd_common(p, q, k, v, o, softmax_lse, batch_size, num_heads, num_heads_k, head_size_qk,
+                   seqlen_q, seqlen_k, window_size_left, window_size_right, softmax_scale, 0.f, nullptr, 0);
+        p.q_batch = strides[0]; p.q_row = strides[1]; p.q_head = strides[2];
+        p.k_batch = strides[3]; p.k_row = strides[4]; p.k_head = strides[5];
+        p.v_batch = strides[6]; p.v_row = strides[7]; p.v_head = strides[8];
+        p.o_batch = strides[9]; p.o_row = strides[10]; p.o_head = strides[11];
+        p.lse_batch = (int64_t)num_heads * seqlen_q; p.lse_head = seqlen_q;
+        run_fwd_mla(p, !is_fp16, stream);
+    } catch (...) {
+        fail(9, "internal error in fmha_fwd_mla");
+    }
+}
+
+void fmha_varlen_fwd_mla(void* q, void* k, void* v, void* o, void* softmax_lse, void* cu_seqlens_q,
+                         void* cu_seqlens_k, void* seqused_k, int32_t max_seqlen_q,
+                         int32_t max_seqlen_k, int32_t total_q, int32_t batch_size, int32_t num_heads,
+                         int32_t num_heads_k, int32_t head_size_qk, int32_t head_size_v,
+                         const int64_t* strides, float softmax_scale, int window_size_left,
+                         int window_size_right, bool is_fp16, hipStream_t stream) {
+    try {
+        begin_fwd();
+        if (!check_mla_pair(head_size_qk, head_size_v)) return;
+        if (!check_common(q, k, v, o, batch_size, num_heads, num_heads_k, head_size_qk)) return;
+        REQUIRE(cu_seqlens_q && cu_seqlens_k, "cu_seqlens_q and cu_seqlens_k must be given");
+        REQUIRE(max_seqlen_q > 0, "max_seqlen_q must be positive (got %d)", max_seqlen_q);
+        REQUIRE(max_seqlen_k > 0, "max_seqlen_k must be positive (got %d): nothing to attend to", max_seqlen_k);
+        REQUIRE(!softmax_lse || total_q > 0, "total_q must be given to address the LSE");
+        REQUIRE(!(((uintptr_t)softmax_lse | (uintptr_t)cu_seqlens_q | (uintptr_t)cu_seqlens_k | (uintptr_t)seqused_k) & 3),
+                "softmax_lse, cu_seqlens_q, cu_seqlens_k and seqused_k must be 4-byte aligned device pointers");
+        if (!check_mla_strides(strides, 2, 1, max_seqlen_q, max_seqlen_k, num_heads, num_heads_k)) return;
+        if (softmax_lse && !slab_ok("softmax_lse", total_q, num_heads, 4)) return;
+        FwdParams p{};
+        fwd_common(p, q, k, v, o, softmax_lse, batch_size, num_heads, num_heads_k, head_size_qk,
+                   max_seqlen_q, max_seqlen_k, window_size_left, window_size_right, softmax_scale, 0.f,
+                   nullptr, 0);
+        p.q_row = strides[0]; p.q_head = strides[1];
+        p.k_row = strides[2]; p.k_head = strides[3];
+        p.v_row = strides[4]; p.v_head = strides[5];
+        p.o_row = strides[6]; p.o_head = strides[7];
+        p.lse_batch = 0; p.lse_head = total_q;
+        p.cu_seqlens_q = (const int*)cu_seqlens_q;
+        p.cu_seqlens_k = (const int*)cu_seqlens_k;
+        p.seqused_k = (const int*)seqused_k;
+        run_fwd_mla(p, !is_fp16, stream);
+    } catch (...) {
+        fail(9, "internal error in fmha_varlen_fwd_mla");
+    }
 }
 
 }  // extern "C"

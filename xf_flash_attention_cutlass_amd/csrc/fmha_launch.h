@@ -280,6 +280,11 @@ hipError_t launch_mla_decode_fp8(const MlaParams& p, bool fp16, hipStream_t st);
 // and fmha_mla_decode_sparse_fp8_kernel.h)
 hipError_t launch_mla_decode_sparse(const MlaParams& p, bool fp8, bool fp16, hipStream_t st);
 
+// MLA prefill (fmha_fwd_mla.hip): the forward at head size 192 for Q K^T and 128 for V; one pass
+// (p.num_splits = 1), none of the score features, p.d unused
+hipError_t launch_fwd_mla_bf16(const FwdParams& p, hipStream_t st);
+hipError_t launch_fwd_mla_f16(const FwdParams& p, hipStream_t st);
+
 // Append to an fp8 latent cache (fmha_append.hip): token t's 512 latent features, quantised per
 // 128-feature group, and its 64 rotary features, copied, into the 656-byte row slot[t] of the
 // cache; row strides in elements.  A slot outside [0, slots) writes nothing.

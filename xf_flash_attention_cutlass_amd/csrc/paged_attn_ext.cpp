@@ -1222,6 +1222,102 @@ void mha_mla_cache_append_fp8(const at::Tensor& latent, const at::Tensor& k_pe, 
     raise_if_failed("mla_cache_append_fp8");
 }
 
+namespace {
+
+// ---- `fwd_mla` / `varlen_fwd_mla`: q and k with 192 features a head, v with 128, each by its own
+// strides.  Nothing is padded or copied: a tensor the kernel cannot read as it stands is refused.
+void check_mla_prefill_tensor(const at::Tensor& t, const at::Tensor& q, const char* name) {
+    TORCH_CHECK(t.dtype() == q.dtype(), name, " must have the dtype of q");
+    TORCH_CHECK(t.is_cuda() && t.device() == q.device(), name, " must be on q's device");
+    TORCH_CHECK(t.stride(-1) == 1, name, " must have contiguous last dimension");
+    TORCH_CHECK(aligned16(t), name, " must be 16-byte aligned with strides that are multiples of 16 bytes");
+}
+// the pair of head sizes, the head counts and the four tensors; `rank` 4 (dense) or 3 (packed)
+void check_mla_prefill(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, int rank) {
+    TORCH_CHECK(q.dtype() == torch::kFloat16 || q.dtype() == torch::kBFloat16, "q must be fp16 or bf16");
+    CHECK_DEVICE(q);
+    const char* layout = rank == 4 ? kDense : kPacked;
+    TORCH_CHECK(q.dim() == rank, "q must be ", layout);
+    TORCH_CHECK(k.dim() == rank, "k must be ", layout);
+    TORCH_CHECK(v.dim() == rank, "v must be ", layout);
+    TORCH_CHECK(q.size(-1) == 192 && k.size(-1) == 192 && v.size(-1) == 128,
+                "MLA prefill supports (head_size_qk, head_size_v) = (192, 128) only (got q ", q.size(-1),
+                ", k ", k.size(-1), ", v ", v.size(-1), ")");
+    check_mla_prefill_tensor(q, q, "q");
+    check_mla_prefill_tensor(k, q, "k");
+    check_mla_prefill_tensor(v, q, "v");
+    TORCH_CHECK(k.size(-2) == v.size(-2), "k and v must have the same number of heads");
+    TORCH_CHECK(k.size(-3) == v.size(-3), "k and v must have the same number of rows");
+    TORCH_CHECK(q.size(-2) >= 1 && k.size(-2) >= 1 && q.size(-2) % k.size(-2) == 0,
+                "Number of heads in key/value must divide number of heads in query");
+}
+// the caller's output (written in place by its own strides) or a new contiguous one
+at::Tensor take_mla_prefill_out(const OptTensor& out_, const at::Tensor& q) {
+    std::vector<int64_t> shape = q.sizes().vec();
+    shape.back() = 128;
+    if (!out_.has_value()) return torch::empty(shape, q.options());
+    const at::Tensor& out = out_.value();
+    TORCH_CHECK(out.sizes() == at::IntArrayRef(shape), "out must have shape ", at::IntArrayRef(shape));
+    check_mla_prefill_tensor(out, q, "out");
+    return out;
+}
+
+}  // namespace
+
+// MLA prefill, dense (fmha_fwd_mla).  Returns {out [batch, seqlen_q, heads, 128], softmax_lse
+// [batch, heads, seqlen_q]}.
+std::vector<at::Tensor>
+mha_fwd_mla(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, const OptTensor& out_,
+            const float softmax_scale, const bool is_causal, int window_size_left, int window_size_right) {
+    check_mla_prefill(q, k, v, 4);
+    const int batch = q.size(0), seqlen_q = q.size(1), heads = q.size(2);
+    const int seqlen_k = k.size(1), heads_k = k.size(2);
+    TORCH_CHECK(batch > 0, "batch size must be positive");
+    TORCH_CHECK(k.size(0) == batch && v.size(0) == batch, "k and v must have q's batch size");
+    TORCH_CHECK(seqlen_q > 0 && seqlen_k > 0, "seqlen_q and seqlen_k must be positive");
+    normalize_window(is_causal, false, seqlen_k, false, window_size_left, window_size_right);
+    at::Tensor out = take_mla_prefill_out(out_, q);
+    at::Tensor lse = torch::empty({batch, heads, seqlen_q}, q.options().dtype(torch::kFloat32));
+    const c10::DeviceGuard device_guard(q.device());
+    const int64_t st[12] = {q.stride(0), q.stride(1), q.stride(2), k.stride(0), k.stride(1), k.stride(2),
+                            v.stride(0), v.stride(1), v.stride(2), out.stride(0), out.stride(1), out.stride(2)};
+    fmha_fwd_mla(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), lse.data_ptr(), seqlen_q, seqlen_k,
+                 batch, heads, heads_k, 192, 128, st, softmax_scale, window_size_left, window_size_right,
+                 q.dtype() == torch::kFloat16, cur_stream());
+    raise_if_failed("fwd_mla");
+    return {out, lse};
+}
+
+// MLA prefill, packed (fmha_varlen_fwd_mla).  Returns {out [total_q, heads, 128], softmax_lse
+// [heads, total_q]}.
+std::vector<at::Tensor>
+mha_varlen_fwd_mla(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, const OptTensor& out_,
+                   const at::Tensor& cu_seqlens_q, const at::Tensor& cu_seqlens_k, const OptTensor& seqused_k_,
+                   const int max_seqlen_q, const int max_seqlen_k, const float softmax_scale,
+                   const bool is_causal, int window_size_left, int window_size_right) {
+    check_mla_prefill(q, k, v, 3);
+    const int batch = check_cu_seqlens(cu_seqlens_q, cu_seqlens_k);
+    const at::Tensor seqused_k = batch_int32(seqused_k_, batch, "seqused_k");
+    TORCH_CHECK(cu_seqlens_q.device() == q.device() && cu_seqlens_k.device() == q.device() &&
+                    (!seqused_k.defined() || seqused_k.device() == q.device()),
+                "cu_seqlens_q, cu_seqlens_k and seqused_k must be on q's device");
+    const int total_q = q.size(0), heads = q.size(1), heads_k = k.size(1);
+    TORCH_CHECK(total_q > 0 && max_seqlen_q > 0, "total_q and max_seqlen_q must be positive");
+    TORCH_CHECK(max_seqlen_k > 0, "max_seqlen_k must be positive: nothing to attend to");
+    normalize_window(is_causal, false, max_seqlen_k, false, window_size_left, window_size_right);
+    at::Tensor out = take_mla_prefill_out(out_, q);
+    at::Tensor lse = torch::empty({heads, total_q}, q.options().dtype(torch::kFloat32));
+    const c10::DeviceGuard device_guard(q.device());
+    const int64_t st[8] = {q.stride(0), q.stride(1), k.stride(0), k.stride(1),
+                           v.stride(0), v.stride(1), out.stride(0), out.stride(1)};
+    fmha_varlen_fwd_mla(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), lse.data_ptr(),
+                        cu_seqlens_q.data_ptr(), cu_seqlens_k.data_ptr(), ptr_or_null(seqused_k), max_seqlen_q,
+                        max_seqlen_k, total_q, batch, heads, heads_k, 192, 128, st, softmax_scale,
+                        window_size_left, window_size_right, q.dtype() == torch::kFloat16, cur_stream());
+    raise_if_failed("varlen_fwd_mla");
+    return {out, lse};
+}
+
 PYBIND11_MODULE(paged_attn, m) {
     m.doc() = "FlashAttention for MI355X (gfx950): hand-written HIP kernels behind the paged_attn C ABI";
     m.def("fwd", without_sink(&mha_fwd), "Forward pass");
@@ -1278,6 +1374,15 @@ PYBIND11_MODULE(paged_attn, m) {
     m.def("_mla_decode_sparse_fp8", &mha_mla_decode_sparse<true>, "MLA decode over index-selected tokens of an fp8 paged latent KV cache",
           py::arg("q"), py::arg("kv_cache"), py::arg("indices"), py::arg("head_dim_v") = 512,
           py::arg("softmax_scale") = 0.041666666666666664f, py::arg("num_splits") = 0, py::arg("out") = py::none());
+    // ... and the MLA prefill (head size 192 for q / k, 128 for v), dense and packed
+    m.def("_fwd_mla", &mha_fwd_mla, "MLA prefill forward (d_qk 192, d_v 128)", py::arg("q"), py::arg("k"),
+          py::arg("v"), py::arg("out") = py::none(), py::arg("softmax_scale") = 0.07216878364870322f,
+          py::arg("is_causal") = false, py::arg("window_size_left") = -1, py::arg("window_size_right") = -1);
+    m.def("_varlen_fwd_mla", &mha_varlen_fwd_mla, "MLA prefill forward over packed sequences (d_qk 192, d_v 128)",
+          py::arg("q"), py::arg("k"), py::arg("v"), py::arg("out"), py::arg("cu_seqlens_q"),
+          py::arg("cu_seqlens_k"), py::arg("seqused_k"), py::arg("max_seqlen_q"), py::arg("max_seqlen_k"),
+          py::arg("softmax_scale") = 0.07216878364870322f, py::arg("is_causal") = false,
+          py::arg("window_size_left") = -1, py::arg("window_size_right") = -1);
     const py::handle self = m;
     m.def("__getattr__", [self](const std::string& name) -> py::object {
         if (name == "merge_states") return self.attr("_merge_states");
@@ -1286,6 +1391,8 @@ PYBIND11_MODULE(paged_attn, m) {
         if (name == "mla_cache_append_fp8") return self.attr("_mla_cache_append_fp8");
         if (name == "mla_decode_sparse") return self.attr("_mla_decode_sparse");
         if (name == "mla_decode_sparse_fp8") return self.attr("_mla_decode_sparse_fp8");
+        if (name == "fwd_mla") return self.attr("_fwd_mla");
+        if (name == "varlen_fwd_mla") return self.attr("_varlen_fwd_mla");
         PyErr_SetString(PyExc_AttributeError, ("module 'paged_attn' has no attribute '" + name + "'").c_str());
         throw py::error_already_set();
     });

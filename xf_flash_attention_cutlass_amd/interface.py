@@ -75,6 +75,43 @@ class _FlashAttnFunc(torch.autograd.Function):
         return (dq, dk, dv, dsink) + (None,) * 8
 
 
+def _mla_prefill(q, k, v, packed, dropout_p, softmax_scale, causal, window_size, softcap,
+                 alibi_slopes, sink, block_table=None):
+    """`flash_attn_func` / `flash_attn_varlen_func` with v narrower than q: MLA prefill in its
+    un-absorbed form, q and k with 192 features a head (128 "nope" + 64 rotary), v with 128
+    (`paged_attn.fwd_mla` / `varlen_fwd_mla`, one HIP launch, no padded copy of v and no slice of
+    the output).  `packed`: () or (cu_seqlens_q, cu_seqlens_k, seqused_k, max_seqlen_q,
+    max_seqlen_k).  Forward only; every argument the kernel has no code for is refused by name.
+    Returns (out [..., h, 128], lse)."""
+    pair = (q.shape[-1], v.shape[-1])
+    if pair != (192, 128) or k.shape[-1] != 192:
+        raise NotImplementedError("q/k/v head sizes: v narrower or wider than q is supported for MLA "
+                                  f"prefill at (192, 128) only (got q {q.shape[-1]}, k {k.shape[-1]}, "
+                                  f"v {v.shape[-1]})")
+    if q.dtype == torch.float8_e4m3fn:
+        raise NotImplementedError("fp8 q/k/v: MLA prefill (192, 128) takes bf16 or fp16")
+    if dropout_p != 0.0:
+        raise NotImplementedError(f"dropout_p={dropout_p}: MLA prefill (192, 128) has no dropout")
+    if alibi_slopes is not None:
+        raise NotImplementedError("alibi_slopes: MLA prefill (192, 128) has no ALiBi")
+    if softcap != 0.0:
+        raise NotImplementedError(f"softcap={softcap}: MLA prefill (192, 128) has no softcap")
+    if sink is not None:
+        raise NotImplementedError("sink: MLA prefill (192, 128) has no attention sink")
+    if block_table is not None:
+        raise NotImplementedError("block_table: MLA prefill (192, 128) reads no paged K/V")
+    if torch.is_grad_enabled():
+        for name, x in (("q", q), ("k", k), ("v", v)):
+            if x.requires_grad:
+                raise NotImplementedError(f"{name}.requires_grad: MLA prefill (192, 128) has no backward "
+                                          "(call it under torch.no_grad() or detach the inputs)")
+    op = paged_attn.varlen_fwd_mla if packed else paged_attn.fwd_mla
+    with torch.no_grad():
+        out, lse = op(q.detach(), k.detach(), v.detach(), None, *packed, float(softmax_scale),
+                      bool(causal), int(window_size[0]), int(window_size[1]))
+    return out, lse
+
+
 def flash_attn_func(q, k, v, dropout_p=0.0, causal=False, window_size=(-1, -1), softcap=0.0,
                     alibi_slopes=None, deterministic=False, return_attn_probs=False, *,
                     softmax_scale=None, q_descale=None, k_descale=None, v_descale=None,
@@ -87,9 +124,17 @@ def flash_attn_func(q, k, v, dropout_p=0.0, causal=False, window_size=(-1, -1), 
     sink: a per-head logit [h] (any float dtype; gpt-oss's learned sinks) that joins each row's
     softmax denominator and carries no value, in the units of the scaled scores; its gradient is
     returned in sink's dtype.  Not with ALiBi, dropout or fp8 q/k/v; with return_attn_probs the
-    third result is None."""
+    third result is None.
+
+    MLA prefill: q and k [.., 192], v [.., 128] (v.shape[-1] != q.shape[-1]) run the (192, 128)
+    forward (`_mla_prefill`): out [b, sq, h, 128]; forward only, no dropout / ALiBi / softcap /
+    sink; the default scale is still q.shape[-1] ** -0.5."""
     if softmax_scale is None:
         softmax_scale = q.shape[-1] ** (-0.5)
+    if v.shape[-1] != q.shape[-1]:
+        out, lse = _mla_prefill(q, k, v, (), dropout_p, softmax_scale, causal, window_size, softcap,
+                                alibi_slopes, sink)
+        return out if not return_attn_probs else (out, lse, None)
     if sink is not None:
         _check_sink_args(q, dropout_p, alibi_slopes)
     if q.dtype == torch.float8_e4m3fn:
@@ -368,9 +413,17 @@ def flash_attn_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, ma
     Extension: float8_e4m3fn q/k/v (with per-tensor descales) run the fp8-MFMA varlen forward
     (forward only, d = 128, no ALiBi / softcap / dropout / block_table); out is `out_dtype`.
 
-    sink: as `flash_attn_func`."""
+    sink: as `flash_attn_func`.
+
+    MLA prefill: q and k [.., 192], v [.., 128] run the (192, 128) forward as in `flash_attn_func`
+    (out [total_q, h, 128], LSE [h, total_q]; no block_table)."""
     if softmax_scale is None:
         softmax_scale = q.shape[-1] ** (-0.5)
+    if v.shape[-1] != q.shape[-1]:
+        packed = (cu_seqlens_q, cu_seqlens_k, None, int(max_seqlen_q), int(max_seqlen_k))
+        out, lse = _mla_prefill(q, k, v, packed, dropout_p, softmax_scale, causal, window_size,
+                                softcap, alibi_slopes, sink, block_table)
+        return out if not return_attn_probs else (out, lse, None)
     if sink is not None:
         _check_sink_args(q, dropout_p, alibi_slopes)
     if q.dtype == torch.float8_e4m3fn:
