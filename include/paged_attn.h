@@ -127,7 +127,7 @@ void fmha_set_rng_state(uint64_t seed, uint64_t offset);
 void fmha_set_rng_state_device(const int64_t* seed_ptr, const int64_t* offset_ptr,
                                uint64_t offset_add, int64_t* rng_out);
 
-/* Library version / build identification, e.g. "xf-fmha-gfx950 2.12".  2.0 (round 3) changed
+/* Library version / build identification, e.g. "xf-fmha-gfx950 2.13".  2.0 (round 3) changed
  * argument lists of existing symbols; 2.1 exports those under _v2 names (see INTEGRATION.md
  * "ABI history"). */
 const char* fmha_version(void);
@@ -643,6 +643,47 @@ void fmha_varlen_fwd_mla(void* q, void* k, void* v, void* o, void* softmax_lse,
                          int32_t head_size_qk /* 192 */, int32_t head_size_v /* 128 */,
                          const int64_t* strides /* q, k, v, o: row,head */, float softmax_scale,
                          int window_size_left, int window_size_right, bool is_fp16, hipStream_t stream);
+
+/* ------------------------- MLA prefill backward: dq, dk (192 wide), dv (128 wide) (2.13) */
+
+/* The gradient of fmha_fwd_mla / fmha_varlen_fwd_mla from dout (like o), the forward's inputs, its
+ * o and its softmax_lse: dq (like q), dk (like k), dv (like v).  Three launches on `stream`:
+ *   fmha_bwd_mla_pre_kernel   D[row] = sum over the 128 columns of dout * o (fp32);
+ *   fmha_bwd_mla_dkdv_kernel  one workgroup a 128-key block of one (batch, kv head): dk, dv;
+ *   fmha_bwd_mla_dq_kernel    one workgroup a 128-row block of one (batch, head): dq.
+ * No atomics: every output element has one writer and one summation order, so results are
+ * bitwise reproducible and there is no deterministic flag, no fp32 dq accumulator and no
+ * workspace.  The only scratch is D, num_heads x tokens fp32 laid out like softmax_lse: the
+ * caller's softmax_d, or with softmax_d == NULL the stream's scratch pool (the first call on a
+ * stream allocates it: warm a stream up before capturing a graph on it).
+ * Every dq / dk / dv element of every sequence is written, exact zeros for rows without a visible
+ * key and keys no row sees; nothing else is.  Windows as the forward; no ALiBi, softcap, dropout,
+ * sink or seqused_k.  fmha_last_kernel() names the three kernels and the dq grid.
+ *
+ * fmha_bwd_mla: dense tensors as fmha_fwd_mla; strides[24] = {batch, row, head} of q, k, v, out,
+ * dout, dq, dk, dv; softmax_lse (and softmax_d) fp32 [batch, heads, seqlen_q] contiguous.
+ * fmha_varlen_bwd_mla: packed tensors as fmha_varlen_fwd_mla; strides[16] = {row, head} of the
+ * same eight; softmax_lse (and softmax_d) fp32 [heads, total_q].
+ *
+ * Refused with an error, nothing launched, outputs untouched: what fmha_fwd_mla refuses (for
+ * all eight tensors: dq as q, dk as k, dv as v, out and dout as o), and a NULL dout /
+ * softmax_lse / dq / dk / dv; the message names the argument. */
+void fmha_bwd_mla(void* dout, void* q, void* k, void* v, void* out, void* softmax_lse,
+                  void* dq, void* dk, void* dv, void* softmax_d /* nullable: pool */,
+                  int32_t seqlen_q, int32_t seqlen_k, int32_t batch_size, int32_t num_heads,
+                  int32_t num_heads_k, int32_t head_size_qk /* 192 */, int32_t head_size_v /* 128 */,
+                  const int64_t* strides /* q,k,v,out,dout,dq,dk,dv: batch,row,head */,
+                  float softmax_scale, int window_size_left, int window_size_right, bool is_fp16,
+                  hipStream_t stream);
+void fmha_varlen_bwd_mla(void* dout, void* q, void* k, void* v, void* out, void* softmax_lse,
+                         void* dq, void* dk, void* dv, void* softmax_d /* nullable: pool */,
+                         void* cu_seqlens_q, void* cu_seqlens_k, int32_t max_seqlen_q,
+                         int32_t max_seqlen_k, int32_t total_q, int32_t total_k, int32_t batch_size,
+                         int32_t num_heads, int32_t num_heads_k, int32_t head_size_qk /* 192 */,
+                         int32_t head_size_v /* 128 */,
+                         const int64_t* strides /* q,k,v,out,dout,dq,dk,dv: row,head */,
+                         float softmax_scale, int window_size_left, int window_size_right,
+                         bool is_fp16, hipStream_t stream);
 
 #ifdef __cplusplus
 } /* extern "C" */

@@ -43,6 +43,9 @@ def units(tree):
     if os.path.exists(os.path.join(b.CSRC, "fmha_fwd_mla.hip")):      # (trees from 2.12 on)
         tus += [(f"fmha_fwd_mla_{dt}", "fmha_fwd_mla.hip", [f"-DXFA_DTN={dt}", f"-DXFA_DT_BF16={int(dt == 'bf16')}"])
                 for dt in ("bf16", "f16")]
+    if os.path.exists(os.path.join(b.CSRC, "fmha_bwd_mla.hip")):      # (trees from 2.13 on)
+        tus += [(f"fmha_bwd_mla_{dt}", "fmha_bwd_mla.hip", [f"-DXFA_DTN={dt}", f"-DXFA_DT_BF16={int(dt == 'bf16')}"])
+                for dt in ("bf16", "f16")]
     tus += [(n + "+variants", src, d + ["-DXFA_VARIANTS=1"]) for n, src, d in tus if n + ".o" in b.VARIANT_TUS]
     return b, tus
 

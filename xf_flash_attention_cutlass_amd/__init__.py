@@ -39,6 +39,8 @@ from .interface import (  # noqa: E402
     flash_attn_fp8_func,
     flash_attn_func,
     flash_attn_kvpacked_func,
+    flash_attn_mla_func,
+    flash_attn_mla_varlen_func,
     flash_attn_varlen_fp8_func,
     flash_attn_varlen_func,
     flash_attn_varlen_kvpacked_func,
@@ -61,6 +63,8 @@ __all__ = [
     "flash_attn_varlen_kvpacked_func",
     "flash_attn_with_kvcache",
     "flash_mla_with_kvcache",
+    "flash_attn_mla_func",
+    "flash_attn_mla_varlen_func",
     "mla_cache_append_fp8",
     "mla_fp8_cache_row_bytes",
     "quantize_fp8",

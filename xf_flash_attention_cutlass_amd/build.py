@@ -125,6 +125,10 @@ def build_lib(jobs: int = 8, force: bool = False, verbose: bool = False, variant
     for dt in ("bf16", "f16"):
         todo.append((os.path.join(CSRC, "fmha_fwd_mla.hip"), os.path.join(OBJ, f"fmha_fwd_mla_{dt}.o"),
                      [f"-DXFA_DTN={dt}", f"-DXFA_DT_BF16={1 if dt == 'bf16' else 0}"]))
+    # ... and its backward, likewise
+    for dt in ("bf16", "f16"):
+        todo.append((os.path.join(CSRC, "fmha_bwd_mla.hip"), os.path.join(OBJ, f"fmha_bwd_mla_{dt}.o"),
+                     [f"-DXFA_DTN={dt}", f"-DXFA_DT_BF16={1 if dt == 'bf16' else 0}"]))
     todo.append((os.path.join(CSRC, "fmha_api.cpp"), os.path.join(OBJ, "fmha_api.o"), []))
     if variants:
         todo = [(src, os.path.join(obj_dir, os.path.basename(out)), defs + ["-DXFA_VARIANTS=1"])

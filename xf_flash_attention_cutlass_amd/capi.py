@@ -78,6 +78,10 @@ _SIGS = {
                      C.c_int, C.c_int, b_, vp],
     "fmha_varlen_fwd_mla": [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32,
                             C.POINTER(C.c_int64), f32, C.c_int, C.c_int, b_, vp],
+    "fmha_bwd_mla": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32,
+                     C.POINTER(C.c_int64), f32, C.c_int, C.c_int, b_, vp],
+    "fmha_varlen_bwd_mla": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32,
+                            i32, i32, i32, i32, C.POINTER(C.c_int64), f32, C.c_int, C.c_int, b_, vp],
     "fmha_last_error": [],
     "fmha_last_status": [],
     "fmha_last_num_splits": [],

@@ -525,7 +525,7 @@ const char* fmha_last_error(void) { return g_err.c_str(); }
 int fmha_last_status(void) { return g_status; }
 int fmha_last_num_splits(void) { return g_last_splits; }
 const char* fmha_last_kernel(void) { return g_last_kernel; }
-const char* fmha_version(void) { return XFA_VARIANTS ? "xf-fmha-gfx950 2.12 (variants)" : "xf-fmha-gfx950 2.12"; }
+const char* fmha_version(void) { return XFA_VARIANTS ? "xf-fmha-gfx950 2.13 (variants)" : "xf-fmha-gfx950 2.13"; }
 
 void fmha_set_rng_state(uint64_t seed, uint64_t offset) {
     g_seed = seed;
@@ -1695,28 +1695,35 @@ bool check_mla_pair(int head_size_qk, int head_size_v) {
            fail(1, "MLA prefill supports (head_size_qk, head_size_v) = (192, 128) only (got (%d, %d))",
                 head_size_qk, head_size_v);
 }
-bool check_mla_strides(const int64_t* st, int per, int batch, int rows_q, int rows_k, int h, int hk) {
+// (bwd: the backward's eight tensors q, k, v, out, dout, dq, dk, dv - dq goes as q, dk as k, dv
+// as v, out and dout as o)
+bool check_mla_strides(const int64_t* st, int per, int batch, int rows_q, int rows_k, int h, int hk,
+                       bool bwd = false) {
     if (!st) return fail(1, "strides must be non-null");
-    static const char* const kName[4] = {"q", "k", "v", "o"};
-    for (int t = 0; t < 4; ++t) {
+    static const char* const kFwdName[4] = {"q", "k", "v", "o"};
+    static const char* const kBwdName[8] = {"q", "k", "v", "out", "dout", "dq", "dk", "dv"};
+    static const int kBwdKind[8] = {0, 1, 2, 3, 3, 0, 1, 2};
+    const char* const* kName = bwd ? kBwdName : kFwdName;
+    for (int i8 = 0; i8 < (bwd ? 8 : 4); ++i8) {
+        const int t = bwd ? kBwdKind[i8] : i8;
         const int rows = (t == 0 || t == 3) ? rows_q : rows_k;
         const int heads = (t == 0 || t == 3) ? h : hk;
         const int width = (t == 0 || t == 1) ? 192 : 128;
-        const int64_t* s = st + t * per;
+        const int64_t* s = st + i8 * per;
         const int64_t row = s[per - 2], head = s[per - 1];
         const int ext[3] = {batch, rows, heads};
         for (int i = 0; i < per; ++i) {
-            if (s[i] < 0) return fail(1, "strides must be non-negative: %s stride %d is %lld", kName[t], i, (long long)s[i]);
+            if (s[i] < 0) return fail(1, "strides must be non-negative: %s stride %d is %lld", kName[i8], i, (long long)s[i]);
             if (ext[3 - per + i] != 1 && s[i] % 8 != 0)
                 return fail(1, "strides must be multiples of 8 elements (16 bytes): %s stride %d is %lld",
-                            kName[t], i, (long long)s[i]);
+                            kName[i8], i, (long long)s[i]);
         }
         if ((t == 1 || t == 2) && rows > 1 && row < width)
-            return fail(1, "%s row stride must be at least its head size %d (got %lld)", kName[t], width, (long long)row);
+            return fail(1, "%s row stride must be at least its head size %d (got %lld)", kName[i8], width, (long long)row);
         const int64_t bytes = ((int64_t)(rows - 1) * row + (int64_t)(heads - 1) * head + width) * 2;
         if (bytes >= kMaxSlabBytes)
             return fail(1, "%s: one sequence spans %lld bytes; this build addresses a sequence with "
-                        "32-bit offsets and supports < %lld bytes", kName[t], (long long)bytes,
+                        "32-bit offsets and supports < %lld bytes", kName[i8], (long long)bytes,
                         (long long)kMaxSlabBytes);
     }
     return true;
@@ -1797,6 +1804,123 @@ void fmha_varlen_fwd_mla(void* q, void* k, void* v, void* o, void* softmax_lse, 
         run_fwd_mla(p, !is_fp16, stream);
     } catch (...) {
         fail(9, "internal error in fmha_varlen_fwd_mla");
+    }
+}
+
+}  // extern "C"
+
+namespace {
+
+// ---- MLA prefill backward: fmha_bwd_mla and fmha_varlen_bwd_mla -----------------------------
+// What both entries check alike after the pair and check_common: the backward's own pointers,
+// one message an argument
+struct MlaBwdTensors { void *dout, *q, *k, *v, *out, *lse, *dq, *dk, *dv, *softmax_d; };
+bool check_mla_bwd_ptrs(const MlaBwdTensors& t) {
+    const struct { const char* name; const void* ptr; } need[5] = {
+        {"dout", t.dout}, {"softmax_lse", t.lse}, {"dq", t.dq}, {"dk", t.dk}, {"dv", t.dv}};
+    for (const auto& n : need)
+        if (!n.ptr) return fail(1, "%s must be a non-null device pointer", n.name);
+    const struct { const char* name; const void* ptr; } vec[4] = {
+        {"dout", t.dout}, {"dq", t.dq}, {"dk", t.dk}, {"dv", t.dv}};
+    for (const auto& n : vec)
+        if ((uintptr_t)n.ptr & 15) return fail(1, "%s must be a 16-byte aligned device pointer", n.name);
+    if (((uintptr_t)t.lse | (uintptr_t)t.softmax_d) & 3)
+        return fail(1, "softmax_lse and softmax_d must be 4-byte aligned device pointers");
+    return true;
+}
+// The backward of both entries.  `tokens`: the query rows of the whole batch; packed: st holds
+// {row, head} of the eight tensors and the LSE / D are [h, tokens], else {batch, row, head} and
+// [b, h, seqlen_q].  The only scratch is D (the caller's softmax_d or the stream's pool).
+void run_bwd_mla(const MlaBwdTensors& t, const int64_t* st, int64_t tokens, const void* cu_seqlens_q,
+                 const void* cu_seqlens_k, int seqlen_q, int seqlen_k, int b, int h, int hk,
+                 float softmax_scale, int wl, int wr, bool is_fp16, hipStream_t stream, const char* what) {
+    const bool packed = cu_seqlens_q != nullptr;
+    // the preprocess kernel indexes (token, head, 16-byte chunk) with one 32-bit thread id
+    REQUIRE(tokens * h * 16 < (1LL << 31) - 256,
+            "backward: %lld (token, head) rows exceed the 32-bit thread index", (long long)(tokens * h));
+    if (!slab_ok("softmax_lse", tokens, h, 4)) return;
+    float* dsum = (float*)t.softmax_d;
+    if (!dsum) dsum = (float*)pool_get(stream, (size_t)tokens * h * sizeof(float));
+    REQUIRE(dsum, "could not allocate %zu bytes of backward scratch", (size_t)tokens * h * sizeof(float));
+    BwdParams p{};
+    p.q = t.q; p.k = t.k; p.v = t.v; p.o = t.out; p.dout = t.dout; p.lse = (const float*)t.lse;
+    p.dq = t.dq; p.dk = t.dk; p.dv = t.dv;
+    p.dsum = dsum;
+    int64_t* const dst[8][3] = {
+        {&p.q_batch, &p.q_row, &p.q_head},    {&p.k_batch, &p.k_row, &p.k_head},
+        {&p.v_batch, &p.v_row, &p.v_head},    {&p.o_batch, &p.o_row, &p.o_head},
+        {&p.do_batch, &p.do_row, &p.do_head}, {&p.dq_batch, &p.dq_row, &p.dq_head},
+        {&p.dk_batch, &p.dk_row, &p.dk_head}, {&p.dv_batch, &p.dv_row, &p.dv_head}};
+    const int per = packed ? 2 : 3;
+    for (int i = 0; i < 8; ++i) {
+        *dst[i][0] = packed ? 0 : st[i * per];
+        *dst[i][1] = st[i * per + per - 2];
+        *dst[i][2] = st[i * per + per - 1];
+    }
+    const int64_t rows = packed ? tokens : seqlen_q;      // rows under one head of the LSE / D
+    p.lse_head = rows; p.lse_batch = packed ? 0 : (int64_t)h * rows;
+    p.cu_seqlens_q = (const int*)cu_seqlens_q;
+    p.cu_seqlens_k = (const int*)cu_seqlens_k;
+    p.b = b; p.h = h; p.hk = hk; p.group = h / hk; p.d = 192;
+    p.seqlen_q = seqlen_q; p.seqlen_k = seqlen_k;
+    set_windows(wl, wr, seqlen_k);
+    p.wl = wl; p.wr = wr;
+    set_scales(p, softmax_scale, 0.f);
+    p.scale = softmax_scale;
+    p.device = current_device();
+    hip_ok(is_fp16 ? launch_bwd_mla_f16(p, tokens, stream) : launch_bwd_mla_bf16(p, tokens, stream), what);
+}
+
+}  // namespace
+
+extern "C" {
+
+void fmha_bwd_mla(void* dout, void* q, void* k, void* v, void* out, void* softmax_lse, void* dq,
+                  void* dk, void* dv, void* softmax_d, int32_t seqlen_q, int32_t seqlen_k,
+                  int32_t batch_size, int32_t num_heads, int32_t num_heads_k, int32_t head_size_qk,
+                  int32_t head_size_v, const int64_t* strides, float softmax_scale,
+                  int window_size_left, int window_size_right, bool is_fp16, hipStream_t stream) {
+    try {
+        begin_fwd();
+        const MlaBwdTensors t{dout, q, k, v, out, softmax_lse, dq, dk, dv, softmax_d};
+        if (!check_mla_pair(head_size_qk, head_size_v)) return;
+        if (!check_common(q, k, v, out, batch_size, num_heads, num_heads_k, head_size_qk)) return;
+        if (!check_mla_bwd_ptrs(t)) return;
+        REQUIRE(seqlen_q > 0 && seqlen_k > 0, "seqlen_q/seqlen_k must be positive (%d, %d)", seqlen_q, seqlen_k);
+        if (!check_mla_strides(strides, 3, batch_size, seqlen_q, seqlen_k, num_heads, num_heads_k, true)) return;
+        run_bwd_mla(t, strides, (int64_t)batch_size * seqlen_q, nullptr, nullptr, seqlen_q, seqlen_k,
+                    batch_size, num_heads, num_heads_k, softmax_scale, window_size_left,
+                    window_size_right, is_fp16, stream, "MLA prefill backward launch");
+    } catch (...) {
+        fail(9, "internal error in fmha_bwd_mla");
+    }
+}
+
+void fmha_varlen_bwd_mla(void* dout, void* q, void* k, void* v, void* out, void* softmax_lse,
+                         void* dq, void* dk, void* dv, void* softmax_d, void* cu_seqlens_q,
+                         void* cu_seqlens_k, int32_t max_seqlen_q, int32_t max_seqlen_k,
+                         int32_t total_q, int32_t total_k, int32_t batch_size, int32_t num_heads,
+                         int32_t num_heads_k, int32_t head_size_qk, int32_t head_size_v,
+                         const int64_t* strides, float softmax_scale, int window_size_left,
+                         int window_size_right, bool is_fp16, hipStream_t stream) {
+    try {
+        begin_fwd();
+        const MlaBwdTensors t{dout, q, k, v, out, softmax_lse, dq, dk, dv, softmax_d};
+        if (!check_mla_pair(head_size_qk, head_size_v)) return;
+        if (!check_common(q, k, v, out, batch_size, num_heads, num_heads_k, head_size_qk)) return;
+        if (!check_mla_bwd_ptrs(t)) return;
+        REQUIRE(cu_seqlens_q && cu_seqlens_k, "cu_seqlens_q and cu_seqlens_k must be given");
+        REQUIRE(!(((uintptr_t)cu_seqlens_q | (uintptr_t)cu_seqlens_k) & 3),
+                "cu_seqlens_q and cu_seqlens_k must be 4-byte aligned device pointers");
+        REQUIRE(max_seqlen_q > 0, "max_seqlen_q must be positive (got %d)", max_seqlen_q);
+        REQUIRE(max_seqlen_k > 0, "max_seqlen_k must be positive (got %d): nothing to attend to", max_seqlen_k);
+        REQUIRE(total_q > 0 && total_k > 0, "total_q and total_k must be positive (%d, %d)", total_q, total_k);
+        if (!check_mla_strides(strides, 2, 1, max_seqlen_q, max_seqlen_k, num_heads, num_heads_k, true)) return;
+        run_bwd_mla(t, strides, total_q, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, batch_size,
+                    num_heads, num_heads_k, softmax_scale, window_size_left, window_size_right, is_fp16,
+                    stream, "MLA prefill varlen backward launch");
+    } catch (...) {
+        fail(9, "internal error in fmha_varlen_bwd_mla");
     }
 }
 

@@ -284,6 +284,10 @@ hipError_t launch_mla_decode_sparse(const MlaParams& p, bool fp8, bool fp16, hip
 // (p.num_splits = 1), none of the score features, p.d unused
 hipError_t launch_fwd_mla_bf16(const FwdParams& p, hipStream_t st);
 hipError_t launch_fwd_mla_f16(const FwdParams& p, hipStream_t st);
+// ... and its backward (fmha_bwd_mla.hip): preprocess -> dK/dV -> dQ, no atomics and no workspace
+// but p.dsum (fp32, laid out like the LSE); tokens: the query rows of the whole batch
+hipError_t launch_bwd_mla_bf16(const BwdParams& p, int64_t tokens, hipStream_t st);
+hipError_t launch_bwd_mla_f16(const BwdParams& p, int64_t tokens, hipStream_t st);
 
 // Append to an fp8 latent cache (fmha_append.hip): token t's 512 latent features, quantised per
 // 128-feature group, and its 64 rotary features, copied, into the 656-byte row slot[t] of the

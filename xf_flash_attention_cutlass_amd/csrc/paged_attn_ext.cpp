@@ -1318,6 +1318,101 @@ mha_varlen_fwd_mla(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v
     return {out, lse};
 }
 
+namespace {
+
+// ---- `bwd_mla` / `varlen_bwd_mla`: the gradient of the two above.  out and dout are like the
+// forward's out, dq / dk / dv like q / k / v (the caller's, written in place by their own strides,
+// or new contiguous ones); nothing is padded or copied.
+void check_mla_bwd_like(const at::Tensor& t, const at::Tensor& q, std::vector<int64_t> shape, int width,
+                        const char* name) {
+    shape.back() = width;
+    TORCH_CHECK(t.sizes() == at::IntArrayRef(shape), name, " must have shape ", at::IntArrayRef(shape));
+    check_mla_prefill_tensor(t, q, name);
+}
+at::Tensor take_mla_grad(const OptTensor& g_, const at::Tensor& like, const at::Tensor& q, const char* name) {
+    if (!g_.has_value()) return torch::empty(like.sizes(), like.options());
+    check_mla_bwd_like(g_.value(), q, like.sizes().vec(), (int)like.size(-1), name);
+    return g_.value();
+}
+void check_mla_lse(const at::Tensor& lse, const at::Tensor& q, at::IntArrayRef shape) {
+    TORCH_CHECK(lse.dtype() == torch::kFloat32, "softmax_lse must be fp32");
+    TORCH_CHECK(lse.is_cuda() && lse.device() == q.device(), "softmax_lse must be on q's device");
+    TORCH_CHECK(lse.sizes() == shape, "softmax_lse must have shape ", shape);
+    TORCH_CHECK(lse.is_contiguous(), "softmax_lse must be contiguous");
+}
+// the first `per` strides ({batch, row, head} dense, {row, head} packed) of the eight tensors, in
+// the C entries' order
+std::vector<int64_t> mla_bwd_strides(const at::Tensor* const (&t)[8], int per) {
+    std::vector<int64_t> st;
+    for (const at::Tensor* x : t)
+        for (int i = 0; i < per; ++i) st.push_back(x->stride(i));
+    return st;
+}
+
+}  // namespace
+
+// MLA prefill backward, dense (fmha_bwd_mla).  Returns {dq, dk, dv, softmax_d [batch, heads, seqlen_q]}.
+std::vector<at::Tensor>
+mha_bwd_mla(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+            const at::Tensor& out, const at::Tensor& softmax_lse, const OptTensor& dq_, const OptTensor& dk_,
+            const OptTensor& dv_, const float softmax_scale, const bool is_causal, int window_size_left,
+            int window_size_right) {
+    check_mla_prefill(q, k, v, 4);
+    const int batch = q.size(0), seqlen_q = q.size(1), heads = q.size(2);
+    const int seqlen_k = k.size(1), heads_k = k.size(2);
+    TORCH_CHECK(batch > 0, "batch size must be positive");
+    TORCH_CHECK(k.size(0) == batch && v.size(0) == batch, "k and v must have q's batch size");
+    TORCH_CHECK(seqlen_q > 0 && seqlen_k > 0, "seqlen_q and seqlen_k must be positive");
+    check_mla_bwd_like(out, q, q.sizes().vec(), 128, "out");
+    check_mla_bwd_like(dout, q, q.sizes().vec(), 128, "dout");
+    check_mla_lse(softmax_lse, q, {batch, heads, seqlen_q});
+    normalize_window(is_causal, false, seqlen_k, false, window_size_left, window_size_right);
+    at::Tensor dq = take_mla_grad(dq_, q, q, "dq"), dk = take_mla_grad(dk_, k, q, "dk"), dv = take_mla_grad(dv_, v, q, "dv");
+    at::Tensor softmax_d = torch::empty({batch, heads, seqlen_q}, q.options().dtype(torch::kFloat32));
+    const c10::DeviceGuard device_guard(q.device());
+    const at::Tensor* const ts[8] = {&q, &k, &v, &out, &dout, &dq, &dk, &dv};
+    const std::vector<int64_t> st = mla_bwd_strides(ts, 3);
+    fmha_bwd_mla(dout.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), softmax_lse.data_ptr(),
+                 dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), softmax_d.data_ptr(), seqlen_q, seqlen_k, batch,
+                 heads, heads_k, 192, 128, st.data(), softmax_scale, window_size_left, window_size_right,
+                 q.dtype() == torch::kFloat16, cur_stream());
+    raise_if_failed("bwd_mla");
+    return {dq, dk, dv, softmax_d};
+}
+
+// MLA prefill backward, packed (fmha_varlen_bwd_mla).  Returns {dq, dk, dv, softmax_d [heads, total_q]}.
+std::vector<at::Tensor>
+mha_varlen_bwd_mla(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+                   const at::Tensor& out, const at::Tensor& softmax_lse, const OptTensor& dq_,
+                   const OptTensor& dk_, const OptTensor& dv_, const at::Tensor& cu_seqlens_q,
+                   const at::Tensor& cu_seqlens_k, const int max_seqlen_q, const int max_seqlen_k,
+                   const float softmax_scale, const bool is_causal, int window_size_left,
+                   int window_size_right) {
+    check_mla_prefill(q, k, v, 3);
+    const int batch = check_cu_seqlens(cu_seqlens_q, cu_seqlens_k);
+    TORCH_CHECK(cu_seqlens_q.device() == q.device() && cu_seqlens_k.device() == q.device(),
+                "cu_seqlens_q and cu_seqlens_k must be on q's device");
+    const int total_q = q.size(0), total_k = k.size(0), heads = q.size(1), heads_k = k.size(1);
+    TORCH_CHECK(total_q > 0 && max_seqlen_q > 0, "total_q and max_seqlen_q must be positive");
+    TORCH_CHECK(total_k > 0 && max_seqlen_k > 0, "total_k and max_seqlen_k must be positive: nothing to attend to");
+    check_mla_bwd_like(out, q, q.sizes().vec(), 128, "out");
+    check_mla_bwd_like(dout, q, q.sizes().vec(), 128, "dout");
+    check_mla_lse(softmax_lse, q, {heads, total_q});
+    normalize_window(is_causal, false, max_seqlen_k, false, window_size_left, window_size_right);
+    at::Tensor dq = take_mla_grad(dq_, q, q, "dq"), dk = take_mla_grad(dk_, k, q, "dk"), dv = take_mla_grad(dv_, v, q, "dv");
+    at::Tensor softmax_d = torch::empty({heads, total_q}, q.options().dtype(torch::kFloat32));
+    const c10::DeviceGuard device_guard(q.device());
+    const at::Tensor* const ts[8] = {&q, &k, &v, &out, &dout, &dq, &dk, &dv};
+    const std::vector<int64_t> st = mla_bwd_strides(ts, 2);
+    fmha_varlen_bwd_mla(dout.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(),
+                        softmax_lse.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), softmax_d.data_ptr(),
+                        cu_seqlens_q.data_ptr(), cu_seqlens_k.data_ptr(), max_seqlen_q, max_seqlen_k, total_q,
+                        total_k, batch, heads, heads_k, 192, 128, st.data(), softmax_scale, window_size_left,
+                        window_size_right, q.dtype() == torch::kFloat16, cur_stream());
+    raise_if_failed("varlen_bwd_mla");
+    return {dq, dk, dv, softmax_d};
+}
+
 PYBIND11_MODULE(paged_attn, m) {
     m.doc() = "FlashAttention for MI355X (gfx950): hand-written HIP kernels behind the paged_attn C ABI";
     m.def("fwd", without_sink(&mha_fwd), "Forward pass");
@@ -1383,6 +1478,16 @@ PYBIND11_MODULE(paged_attn, m) {
           py::arg("cu_seqlens_k"), py::arg("seqused_k"), py::arg("max_seqlen_q"), py::arg("max_seqlen_k"),
           py::arg("softmax_scale") = 0.07216878364870322f, py::arg("is_causal") = false,
           py::arg("window_size_left") = -1, py::arg("window_size_right") = -1);
+    // ... and its backward
+    m.def("_bwd_mla", &mha_bwd_mla, "MLA prefill backward (d_qk 192, d_v 128)", py::arg("dout"), py::arg("q"),
+          py::arg("k"), py::arg("v"), py::arg("out"), py::arg("softmax_lse"), py::arg("dq") = py::none(),
+          py::arg("dk") = py::none(), py::arg("dv") = py::none(), py::arg("softmax_scale") = 0.07216878364870322f,
+          py::arg("is_causal") = false, py::arg("window_size_left") = -1, py::arg("window_size_right") = -1);
+    m.def("_varlen_bwd_mla", &mha_varlen_bwd_mla, "MLA prefill backward over packed sequences (d_qk 192, d_v 128)",
+          py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"), py::arg("out"), py::arg("softmax_lse"),
+          py::arg("dq"), py::arg("dk"), py::arg("dv"), py::arg("cu_seqlens_q"), py::arg("cu_seqlens_k"),
+          py::arg("max_seqlen_q"), py::arg("max_seqlen_k"), py::arg("softmax_scale") = 0.07216878364870322f,
+          py::arg("is_causal") = false, py::arg("window_size_left") = -1, py::arg("window_size_right") = -1);
     const py::handle self = m;
     m.def("__getattr__", [self](const std::string& name) -> py::object {
         if (name == "merge_states") return self.attr("_merge_states");
@@ -1393,6 +1498,8 @@ PYBIND11_MODULE(paged_attn, m) {
         if (name == "mla_decode_sparse_fp8") return self.attr("_mla_decode_sparse_fp8");
         if (name == "fwd_mla") return self.attr("_fwd_mla");
         if (name == "varlen_fwd_mla") return self.attr("_varlen_fwd_mla");
+        if (name == "bwd_mla") return self.attr("_bwd_mla");
+        if (name == "varlen_bwd_mla") return self.attr("_varlen_bwd_mla");
         PyErr_SetString(PyExc_AttributeError, ("module 'paged_attn' has no attribute '" + name + "'").c_str());
         throw py::error_already_set();
     });

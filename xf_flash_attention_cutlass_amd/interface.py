@@ -104,12 +104,93 @@ def _mla_prefill(q, k, v, packed, dropout_p, softmax_scale, causal, window_size,
         for name, x in (("q", q), ("k", k), ("v", v)):
             if x.requires_grad:
                 raise NotImplementedError(f"{name}.requires_grad: MLA prefill (192, 128) has no backward "
-                                          "(call it under torch.no_grad() or detach the inputs)")
+                                          "here (use flash_attn_mla_func / flash_attn_mla_varlen_func, "
+                                          "or call it under torch.no_grad())")
     op = paged_attn.varlen_fwd_mla if packed else paged_attn.fwd_mla
     with torch.no_grad():
         out, lse = op(q.detach(), k.detach(), v.detach(), None, *packed, float(softmax_scale),
                       bool(causal), int(window_size[0]), int(window_size[1]))
     return out, lse
+
+
+def _mla_dout(dout):
+    """dout as the backward kernels read it: unit-stride last dimension, 16-byte aligned rows"""
+    ok = (dout.stride(-1) == 1 and dout.data_ptr() % 16 == 0 and
+          all(s % 8 == 0 for n, s in zip(dout.shape[:-1], dout.stride()[:-1]) if n != 1))
+    return dout if ok else dout.contiguous()
+
+
+def _check_mla_func(q, k, v):
+    pair = (q.shape[-1], k.shape[-1], v.shape[-1])
+    if pair != (192, 192, 128):
+        raise NotImplementedError("flash_attn_mla_func: head sizes (q, k, v) = (192, 192, 128) only "
+                                  f"(got {pair})")
+    if q.dtype not in (torch.bfloat16, torch.float16):
+        raise NotImplementedError(f"q.dtype={q.dtype}: MLA prefill (192, 128) takes bf16 or fp16")
+
+
+class _FlashAttnMlaFunc(torch.autograd.Function):
+    """MLA prefill (192, 128) with its gradient, dense or packed: the unchanged `fwd_mla` /
+    `varlen_fwd_mla` forward, `bwd_mla` / `varlen_bwd_mla` by the tensors' own strides.
+    `packed`: () or (cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k)."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, packed, softmax_scale, causal, window_size):
+        if packed:
+            cu_q, cu_k, max_q, max_k = packed
+            out, lse = paged_attn.varlen_fwd_mla(q, k, v, None, cu_q, cu_k, None, max_q, max_k,
+                                                 softmax_scale, causal, *window_size)
+            ctx.save_for_backward(q, k, v, out, lse, cu_q, cu_k)
+        else:
+            out, lse = paged_attn.fwd_mla(q, k, v, None, softmax_scale, causal, *window_size)
+            ctx.save_for_backward(q, k, v, out, lse)
+        ctx.args = (packed[2:], softmax_scale, causal, window_size)
+        ctx.mark_non_differentiable(lse)
+        return out, lse
+
+    @staticmethod
+    def backward(ctx, dout, *_):
+        q, k, v, out, lse, *cu = ctx.saved_tensors
+        maxes, scale, causal, window = ctx.args
+        op = paged_attn.varlen_bwd_mla if cu else paged_attn.bwd_mla
+        dq, dk, dv, _ = op(_mla_dout(dout), q, k, v, out, lse, None, None, None, *cu, *maxes, scale,
+                           causal, *window)
+        return dq, dk, dv, None, None, None, None
+
+
+def flash_attn_mla_func(q, k, v, causal=False, window_size=(-1, -1), softmax_scale=None,
+                        deterministic=False, return_attn_probs=False):
+    """MLA prefill in its un-absorbed form, differentiable: q [b, sq, h, 192], k [b, sk, hk, 192]
+    (128 "nope" + 64 rotary features a head), v [b, sk, hk, 128] -> out [b, sq, h, 128]; bf16 or
+    fp16, views are fine (last dimension contiguous, 16-byte aligned, no copies).
+
+    The forward is `flash_attn_func`'s at this shape, bit for bit.  The backward is three HIP
+    launches without atomics (`paged_attn.bwd_mla`): dq, dk [.., 192] and dv [.., 128], no padding
+    of v / out / dout to 192 and no slices.  deterministic is accepted and has no effect: every
+    gradient element has one writer and one summation order, so results are always bitwise
+    reproducible.  softmax_scale defaults to q.shape[-1] ** -0.5.  With return_attn_probs the
+    result is (out, lse, None); the LSE carries no gradient."""
+    _check_mla_func(q, k, v)
+    if softmax_scale is None:
+        softmax_scale = q.shape[-1] ** (-0.5)
+    out, lse = _FlashAttnMlaFunc.apply(q, k, v, (), float(softmax_scale), bool(causal),
+                                       tuple(int(w) for w in window_size))
+    return out if not return_attn_probs else (out, lse, None)
+
+
+def flash_attn_mla_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k,
+                               causal=False, window_size=(-1, -1), softmax_scale=None,
+                               deterministic=False, return_attn_probs=False):
+    """`flash_attn_mla_func` over packed sequences: q [total_q, h, 192], k [total_k, hk, 192],
+    v [total_k, hk, 128], cu_seqlens int32 [b + 1] -> out [total_q, h, 128]; the LSE is
+    [h, total_q].  Backward: `paged_attn.varlen_bwd_mla`."""
+    _check_mla_func(q, k, v)
+    if softmax_scale is None:
+        softmax_scale = q.shape[-1] ** (-0.5)
+    packed = (cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), int(max_seqlen_k))
+    out, lse = _FlashAttnMlaFunc.apply(q, k, v, packed, float(softmax_scale), bool(causal),
+                                       tuple(int(w) for w in window_size))
+    return out if not return_attn_probs else (out, lse, None)
 
 
 def flash_attn_func(q, k, v, dropout_p=0.0, causal=False, window_size=(-1, -1), softcap=0.0,
