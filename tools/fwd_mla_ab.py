@@ -11,7 +11,9 @@ Contenders, alternating within every round, bf16, packed:
   (b') the D = 192 forward alone over a V padded once outside the timing, its [.., 192] output kept.
 --ab-lib PATH adds the fmha_varlen_fwd_mla entry of another build of the library (e.g. one compiled
 with -DXFA_MLA_WAVES=4), both builds called through the C ABI so that the two differ in nothing but
-the library.
+the library; its O and LSE are compared with this build's (max |a - b| / max |b|).  The option may
+be repeated: a build and a byte copy of it under another name make a control pair.  The C ABI
+contenders rotate their order from round to round.
 
 Shapes (DeepSeek-V3 has 128 heads; 16 is its tensor-parallel-8 share), causal unless said:
   h128_1x8192   128 heads, one sequence of 8192 tokens
@@ -81,14 +83,30 @@ def measure(a, name):
                              o_c.stride(0), o_c.stride(1))
         stream = capi.stream_handle()
 
-        def c_abi(L):
-            args = (q.data_ptr(), k.data_ptr(), v.data_ptr(), o_c.data_ptr(), None, cq.data_ptr(), ck.data_ptr(),
+        def c_abi(L, lse=None):
+            args = (q.data_ptr(), k.data_ptr(), v.data_ptr(), o_c.data_ptr(), lse, cq.data_ptr(), ck.data_ptr(),
                     None, mq, mk, sum(lq), len(lq), h, h, DQK, DV, st, DQK ** -0.5, -1, 0 if causal else -1, False,
                     stream)
             return lambda: L.fmha_varlen_fwd_mla(*args)
 
-        runs["(a) C ABI, this build"] = c_abi(capi.lib())
-        runs[f"(a) C ABI, {a.ab_lib}"] = c_abi(capi.load(a.ab_lib, strict=False))
+        builds = {"this build": capi.lib(), **{path: capi.load(path, strict=False) for path in a.ab_lib}}
+        # O and LSE of the other builds against this one's (lib_ab.py's check line)
+        lse_c = torch.empty(h, sum(lq), device="cuda", dtype=torch.float32)
+        ref = None
+        for path, L in builds.items():
+            runs[f"(a) C ABI, {path}"] = c_abi(L)
+            o_c.zero_()
+            lse_c.zero_()
+            c_abi(L, lse_c.data_ptr())()
+            torch.cuda.synchronize()
+            outs = (o_c.float().clone(), lse_c.clone())
+            if ref is None:
+                ref = outs
+                continue
+            print(f"check {os.path.basename(path)} vs this build: " + " ".join(
+                f"{n}:{(x - r).abs().max().item():.3e}/{r.abs().max().item():.2e}"
+                for n, x, r in zip(("o", "lse"), outs, ref)))
+        del ref, outs, lse_c
     kern = {}
     with torch.no_grad():
         o_a = runs[ka]()
@@ -115,8 +133,13 @@ def measure(a, name):
                 if e0.elapsed_time(e1) > 1000:
                     break
         times = {nm: [] for nm in runs}
-        for _ in range(a.rounds):
-            for nm, run in runs.items():
+        cabi = [nm for nm in runs if nm.startswith("(a) C ABI")]
+        for r in range(a.rounds):
+            # the C ABI builds take turns at the place behind (b'): the call that follows the slower
+            # D = 192 kernel measures 1 - 2 % longer whichever build it is
+            turn = cabi[r % len(cabi):] + cabi[:r % len(cabi)] if cabi else []
+            for nm in [nm for nm in runs if nm not in cabi] + turn:
+                run = runs[nm]
                 s0, s1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 s0.record()
                 for _ in range(a.iters):
@@ -143,7 +166,9 @@ def main():
     ap.add_argument("--shapes", nargs="+", default=["all"], help="names of SHAPES, or all")
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--iters", type=int, default=5)
-    ap.add_argument("--ab-lib", default="", help="another build of the library to time fmha_varlen_fwd_mla of")
+    ap.add_argument("--ab-lib", action="append", default=[],
+                    help="another build of the library to time fmha_varlen_fwd_mla of (may be repeated, e.g. the "
+                         "parent's build and a byte copy of it as the control pair)")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "fwd_mla_ab.py measures on the GPU"
     prop = torch.cuda.get_device_properties(0)

@@ -24,12 +24,15 @@
 //  * K / V tiles (64 keys x 128 B) arrive by LDS-DMA into a double buffer; the images XOR the
 //    16-byte chunk by the row so both the 32-byte row reads of K and the transposed reads of V
 //    are bank-conflict-free (K: chunk ^ ((row >> 1) & 7); V: chunk ^ (((row >> 1) & 3) << 1)).
-// This file's own: the compiler-scheduled item body (fwd8_item).  The loop over a workgroup's
-// items is fmha_fwd_sched.h's fwd_walk.
+// This file's own: the compiler-scheduled item body (fwd8_item): the fp8 operands, images and
+// softmax, and its pipeline.  The row geometry and the O / LSE store are fmha_fwd_tile.h's,
+// shared with fwd_item and fwd_mla_item; the loop over a workgroup's items is fmha_fwd_sched.h's
+// fwd_walk.
 #pragma once
 
 #include "fmha_common.h"
 #include "fmha_fwd_sched.h"
+#include "fmha_fwd_tile.h"
 
 namespace xfa {
 
@@ -75,31 +78,10 @@ __device__ __forceinline__ void fwd8_item(const FwdParams& p, char* smem, const 
     // varlen / seqused_k: this sequence's rows of the packed tensors (dense: q_off = k_off = 0)
     const SeqRange sr = seq_range<VARLEN>(p, bidx);
     const int q_off = sr.q_off, sq = sr.sq, k_off = sr.k_off, sk = sr.sk;
-    const int G = p.group;
-    const int rows_total = sq * G;
     const int row0 = m_block * BM;
-    if (row0 >= rows_total) return;          // workgroup-uniform (also sq <= 0)
-    const int diag = sk - sq;
-    auto lim_r = [&](int pos) { return (MASK && p.wr >= 0) ? min(sk, pos + diag + p.wr + 1) : sk; };
-    auto lim_l = [&](int pos) { return (MASK && p.wl >= 0) ? max(0, pos + diag - p.wl) : 0; };
-    const int pos_lo = row0 / G;
-    const int pos_hi = (min(row0 + BM, rows_total) - 1) / G;
-    const int n_lo = lim_l(pos_lo);
-    const int n_hi = lim_r(pos_hi);
-    const int nb_lo = n_lo / kBlockN;
-    const int nb_hi = n_hi > n_lo ? (n_hi + kBlockN - 1) / kBlockN : nb_lo;
-
-    const int wrow0 = row0 + wave * 32;
-    const int row = wrow0 + lr;
-    const bool row_ok = row < rows_total;
-    const int pos = row_ok ? row / G : 0;
-    const int head = hk_i * G + (row_ok ? row - pos * G : 0);
-    const bool wave_ok = wrow0 < rows_total;
-    const int wp_lo = wrow0 / G;
-    const int wp_hi = (min(wrow0 + 32, rows_total) - 1) / G;
-    const int w_lr_min = lim_r(wp_lo), w_lr_max = lim_r(wp_hi);
-    const int w_ll_min = lim_l(wp_lo), w_ll_max = lim_l(wp_hi);
-    const int my_lr = lim_r(pos), my_ll = lim_l(pos);
+    if (row0 >= sq * p.group) return;        // workgroup-uniform (also sq <= 0)
+    const RowGeom<MASK> g(p, sq, sk, p.group, hk_i, row0, BM, wave, lr, kNoFloor);
+    const int pos = g.pos, head = g.head;
     // scores arrive in q8.k8 units: fold both descales into the exp2 scale
     const float c = p.scale_log2 * ds.q * ds.k;
 
@@ -110,7 +92,7 @@ __device__ __forceinline__ void fwd8_item(const FwdParams& p, char* smem, const 
         const char* qseq = reinterpret_cast<const char*>(p.q) + (int64_t)bidx * p.q_batch + (int64_t)q_off * p.q_row;
         const uint32_t qbytes = (uint32_t)((int64_t)(sq - 1) * p.q_row + (int64_t)(p.h - 1) * p.q_head + HD);
         const __amdgpu_buffer_rsrc_t qr = make_rsrc(qseq, qbytes);
-        const int qo = row_ok ? (int)((int64_t)pos * p.q_row + (int64_t)head * p.q_head) + 32 * hh : kOOB;
+        const int qo = g.row_ok ? (int)((int64_t)pos * p.q_row + (int64_t)head * p.q_head) + 32 * hh : kOOB;
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
             const u32x4 a = buf_load16(qr, qo + 64 * s), b = buf_load16(qr, qo + 64 * s + 16);
@@ -130,8 +112,8 @@ __device__ __forceinline__ void fwd8_item(const FwdParams& p, char* smem, const 
     int dma_k[IPW], dma_v[IPW];
 #pragma unroll
     for (int i = 0; i < IPW; ++i) {
-        const int g = wave * IPW + i;
-        const int r = 8 * g + (lane >> 3);
+        const int piece = wave * IPW + i;
+        const int r = 8 * piece + (lane >> 3);
         dma_k[i] = r * (int)p.k_row + 16 * ((lane & 7) ^ ((r >> 1) & 7));
         dma_v[i] = r * (int)p.v_row + 16 * ((lane & 7) ^ (((r >> 1) & 3) << 1));
     }
@@ -141,9 +123,9 @@ __device__ __forceinline__ void fwd8_item(const FwdParams& p, char* smem, const 
         const int kso = nb * kBlockN * (int)p.k_row, vso = nb * kBlockN * (int)p.v_row;
 #pragma unroll
         for (int i = 0; i < IPW; ++i) {
-            const int g = wave_u * IPW + i;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(krs, (lds_void*)(smem + buf * TILE + g * 1024), 16, dma_k[i], kso, 0, 0);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(vrs, (lds_void*)(smem + VREG + buf * TILE + g * 1024), 16, dma_v[i], vso, 0, 0);
+            const int piece = wave_u * IPW + i;
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(krs, (lds_void*)(smem + buf * TILE + piece * 1024), 16, dma_k[i], kso, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(vrs, (lds_void*)(smem + VREG + buf * TILE + piece * 1024), 16, dma_v[i], vso, 0, 0);
         }
     };
     // counted vmcnt (the DMA writes are invisible to the compiler's waitcnt tracking): all of
@@ -164,11 +146,11 @@ __device__ __forceinline__ void fwd8_item(const FwdParams& p, char* smem, const 
 #pragma unroll
         for (int u = 0; u < 2; ++u) kaddr[s][u] = (int)(size_t)smem + k8_off(lr, 4 * s + 2 * hh + u);
     {
-        const int i = lane & 15, q = i >> 1, pb8 = i & 1, g = (lane >> 4) & 1;
+        const int i = lane & 15, q = i >> 1, pb8 = i & 1, grp = (lane >> 4) & 1;
         const int r = 32 * hh + q;                       // + 8 kb (an immediate: the swizzle
 #pragma unroll                                            //   only sees row bits 1-2)
         for (int dt = 0; dt < ND; ++dt)
-            vaddr[dt] = (int)(size_t)smem + VREG + v8_off(r, 2 * dt + g) + 8 * pb8;
+            vaddr[dt] = (int)(size_t)smem + VREG + v8_off(r, 2 * dt + grp) + 8 * pb8;
     }
     typedef __attribute__((address_space(3))) u32x4 lds_u32x4;
     typedef __attribute__((address_space(3))) i32x2 lds_i32x2;
@@ -206,14 +188,7 @@ __device__ __forceinline__ void fwd8_item(const FwdParams& p, char* smem, const 
 #pragma unroll
             for (int s = 0; s < 2; ++s) st[kt] = mfma_fp8(rd_k(buf, kt, s), qf[s], st[kt]);
         // mask where a window edge / the end of the keys crosses this wave's rows
-        if ((n0 + kBlockN > w_lr_min) || (n0 < w_ll_max)) {
-#pragma unroll
-            for (int v = 0; v < 32; ++v) {
-                const int kt = v >> 4, r = v & 15;
-                const int key = n0 + 4 * hh + 32 * kt + (r & 3) + 8 * (r >> 2);
-                if (key >= my_lr || key < my_ll) st[kt][r] = -INFINITY;
-            }
-        }
+        if (g.edge(n0)) edge_mask(st, n0, hh, g.my_lr, g.my_ll);
         float mx = st[0][0];
 #pragma unroll
         for (int r = 1; r < 16; ++r) mx = fmaxf(mx, st[0][r]);
@@ -271,8 +246,7 @@ __device__ __forceinline__ void fwd8_item(const FwdParams& p, char* smem, const 
         int buf = 0;
         for (int nb = lo; nb < hi; ++nb) {
             if (nb + 1 < hi) dma_tile(nb + 1, buf ^ 1);
-            const int n0 = nb * kBlockN;
-            if (wave_ok && n0 < w_lr_max && n0 + kBlockN > w_ll_min) tile(buf, nb);
+            if (g.active(nb * kBlockN)) tile(buf, nb);
             publish();
             buf ^= 1;
         }
@@ -299,7 +273,7 @@ __device__ __forceinline__ void fwd8_item(const FwdParams& p, char* smem, const 
         __builtin_amdgcn_s_waitcnt(0xC07F | (n << 8));
         __builtin_amdgcn_sched_barrier(0);
     };
-    const int lim_e = my_lr - 4 * hh;
+    const int lim_e = g.my_lr - 4 * hh;
     // Pipeline softmax without a row max per tile (the 4-wave bf16 kernel's scheme,
     // fmha_fwd4_kernel.h): P = exp2(X) against the running max m_sc; a tile whose per-lane
     // partial row sum passes 2^slack (slack <= 8: every P <= 256 < 448, the e4m3 maximum)
@@ -468,8 +442,7 @@ __device__ __forceinline__ void fwd8_item(const FwdParams& p, char* smem, const 
         // per-wave early exit past the causal diagonal / right window edge, as
         // fmha_fwd_kernel.h: a wave stops after the last tile any of its rows sees, drains it,
         // then keeps only its DMA share and the barriers (bit-identical results)
-        const int t_w = __builtin_amdgcn_readfirstlane((w_lr_max + kBlockN - 1) / kBlockN - 1);
-        const int nsteps_w = __builtin_amdgcn_readfirstlane(wave_ok ? max(0, min(nsteps, t_w - lo)) : nsteps);
+        const int nsteps_w = g.steps_w(nsteps, lo);
         int r = 0;
         while (r < nsteps_w) {
             step(I1{}, I0{}, I3{}, lo + r, sa, sb);
@@ -531,29 +504,19 @@ __device__ __forceinline__ void fwd8_item(const FwdParams& p, char* smem, const 
         __syncthreads();
     };
 
-    // tile ranges as fmha_fwd_kernel.h: [nb_lo, f_lo) cross the left window edge (simple loop);
+    // tile ranges (RowGeom::pipe_split): [nb_lo, f_lo) cross the left window edge (simple loop);
     // [f_lo, nb_hi) run through the pipeline, [f_hi, nb_hi) masked on the way
-    int f_lo = nb_hi, f_hi = nb_hi;
-    {
-        const int ll_max = lim_l(pos_hi), lr_min = lim_r(pos_lo);
-        f_lo = max(nb_lo, (ll_max + kBlockN - 1) / kBlockN);
-        f_hi = max(f_lo, min(nb_hi, lr_min / kBlockN));
-        if (nb_hi - f_lo < 2) f_lo = f_hi = nb_hi;
-    }
-    simple_range(nb_lo, f_lo);
-    if (f_lo < nb_hi) pipe_range(f_lo, f_hi, nb_hi);
+    int f_lo, f_hi;
+    g.pipe_split(g.nb_lo, g.nb_hi, f_lo, f_hi);
+    simple_range(g.nb_lo, f_lo);
+    if (f_lo < g.nb_hi) pipe_range(f_lo, f_hi, g.nb_hi);
 
     // ---- epilogue: O = v_scale * acc / l, LSE in natural units of the dequantised scores
     const float l_full = wave_sum_halves(l_run);
     const bool empty = (l_full == 0.f) || (l_full != l_full);
     const float inv = empty ? 1.f : ds.v / l_full;
-    if (!row_ok) return;
-    T* orow = reinterpret_cast<T*>(p.o) + (int64_t)bidx * p.o_batch + (int64_t)(q_off + pos) * p.o_row +
-              (int64_t)head * p.o_head;
-    store_o_row16<T, ND>(orow, acc_o, inv, HD, hh);
-    if (p.lse && hh == 0)
-        p.lse[(int64_t)bidx * p.lse_batch + (int64_t)head * p.lse_head + q_off + pos] =
-            empty ? INFINITY : (m_sc + __log2f(l_full)) * kLn2;
+    if (!g.row_ok) return;
+    store_row<T, ND>(p, bidx, q_off, pos, head, hh, acc_o, inv, HD, empty ? INFINITY : (m_sc + __log2f(l_full)) * kLn2);
 }
 
 // The schedules of a dense launch are static; a packed one may also take one dynamic queue, last

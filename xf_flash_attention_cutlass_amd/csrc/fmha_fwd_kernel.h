@@ -20,14 +20,17 @@
 //    ds_read_b64_tr_b16 — both conflict-free on the same image;
 //  * masking runs only on the tiles that cross a window edge; tiles a wave cannot see are
 //    skipped by that wave (wave-uniform branch); the heaviest causal row blocks launch first.
-// This file's own: the item body (fwd_item), the dropout key write-back and the split-KV
-// combines.  The item schedules and the loop over a workgroup's items are fmha_fwd_sched.h's.
+// This file's own: the item body's schedules (fwd_item: the register-staged and LDS-DMA masked
+// loops, the 4-buffer pipeline), the score features, leftpad, split-KV, sink and dropout, the
+// dropout key write-back and the split-KV combines.  The row geometry, the softmax state, the
+// tile pieces, the asm V^T read ring, the DMA piece offsets and the epilogue under the schedules
+// are fmha_fwd_tile.h's (shared with fwd_mla_item); the item schedules and the loop over a
+// workgroup's items are fmha_fwd_sched.h's.
 #pragma once
 
 #include "fmha_common.h"
 #include "fmha_fwd_sched.h"
-
-#include <type_traits>
+#include "fmha_fwd_tile.h"
 
 namespace xfa {
 
@@ -58,11 +61,16 @@ __device__ __forceinline__ void fwd_item(const FwdParams& p, char* smem, const i
     constexpr int NS = HD / 16;                 // k-steps of the QK^T product
     constexpr int ND = HD / 32;                 // 32-wide d tiles of O^T
     static_assert(NLD >= 1 && (NT % CPR) == 0, "tile/thread geometry");
+    // Pieces the FEAT instances keep a copy of.  These instances spill (92 - 224 bytes a lane),
+    // and through fmha_fwd_tile.h's edge_mask + raise_max (D <= 128) or qk (D = 256) ten of them
+    // spilled 4 - 16 bytes more than before the header existed, part of it inside the tile loops;
+    // with the copies none does (profiles/fwd_tile_isa_diff.txt).  The other instances take the
+    // shared pieces: with these copies their D = 128 4-wave builds spill up to 76 bytes more.
+    constexpr bool OWN_MASK_MAX = FEAT && PIPE, OWN_QK = FEAT && !PIPE;
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = tid >> 6;
-    const int lr = lane & 31;
     const int hh = lane >> 5;
 
     const int bidx = bh / p.hk;
@@ -76,23 +84,12 @@ __device__ __forceinline__ void fwd_item(const FwdParams& p, char* smem, const i
     // cache_leftpad (block_info.h leftpad_k): the sequence is cache rows [lp, sk)
     const int lp = p.leftpad_k ? p.leftpad_k[bidx] : 0;
     sk -= lp;
-    const int G = p.group;
-    const int rows_total = sq * G;
     const int row0 = m_block * BM;
-    if (row0 >= rows_total) return;
-
-    const int diag = sk - sq;
-    // Window limits for query position `pos`: keys [lim_l, lim_r).
-    auto lim_r = [&](int pos) { return (MASK && p.wr >= 0) ? min(sk, pos + diag + p.wr + 1) : sk; };
-    auto lim_l = [&](int pos) { return (MASK && p.wl >= 0) ? max(0, pos + diag - p.wl) : 0; };
-
-    // Key-tile range of the whole workgroup (and of this split).
-    const int pos_lo = row0 / G;
-    const int pos_hi = (min(row0 + BM, rows_total) - 1) / G;
-    const int n_lo = lim_l(pos_lo);
-    const int n_hi = lim_r(pos_hi);
-    int nb_lo = n_lo / kBlockN;
-    int nb_hi = n_hi > n_lo ? (n_hi + kBlockN - 1) / kBlockN : nb_lo;
+    if (row0 >= sq * p.group) return;
+    const RowGeom<MASK> g(p, sq, sk, p.group, hk_i, row0, BM, wave, lane & 31, kNoFloor);
+    const int pos = g.pos, head = g.head, diag = g.diag;
+    // Key-tile range of the workgroup, and of this split.
+    int nb_lo = g.nb_lo, nb_hi = g.nb_hi;
     const bool is_split = p.num_splits > 1;
     if (is_split) {
         const int per = (nb_hi - nb_lo + p.num_splits - 1) / p.num_splits;
@@ -101,41 +98,12 @@ __device__ __forceinline__ void fwd_item(const FwdParams& p, char* smem, const i
         nb_lo = min(s_lo, nb_hi);
     }
 
-    // This lane's query row.
-    const int wrow0 = row0 + wave * 32;
-    const int row = wrow0 + lr;
-    const bool row_ok = row < rows_total;
-    const int pos = row_ok ? row / G : 0;
-    const int head = hk_i * G + (row_ok ? row - pos * G : 0);
-    const bool wave_ok = wrow0 < rows_total;
-    const int wp_lo = wrow0 / G;
-    const int wp_hi = (min(wrow0 + 32, rows_total) - 1) / G;
-    const int w_lr_min = lim_r(wp_lo), w_lr_max = lim_r(wp_hi);
-    const int w_ll_min = lim_l(wp_lo), w_ll_max = lim_l(wp_hi);
-    const int my_lr = lim_r(pos), my_ll = lim_l(pos);
-
     float alibi_w = 0.f;
     if (FEAT && p.alibi) alibi_w = p.alibi[bidx * p.alibi_bstride + head] * p.alibi_mul;
     const float c = p.scale_log2;
 
-    // ---- Q fragments (B operand of S^T = K Q^T): lane holds Q[row][16s + 8hh .. +7]
     V8 qf[NS];
-    {
-        const T* qseq = reinterpret_cast<const T*>(p.q) + (int64_t)bidx * p.q_batch + (int64_t)q_off * p.q_row;
-        const uint32_t qbytes = (uint32_t)(((int64_t)(sq - 1) * p.q_row + (int64_t)(p.h - 1) * p.q_head + p.d) * 2);
-        const __amdgpu_buffer_rsrc_t qr = make_rsrc(qseq, qbytes);
-        // column part as an immediate offset; the asm keeps per-column offsets from being
-        // hoisted out of the persistent item loop (and spilled)
-        int hh_q = hh;
-        asm volatile("" : "+v"(hh_q));
-        const int qrow_off = row_ok ? (int)(((int64_t)pos * p.q_row + (int64_t)head * p.q_head) * 2) + 16 * hh_q : kOOB;
-        const bool full_d = p.d == HD;
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            const int off = (full_d || 16 * s + 8 * hh_q < p.d) ? qrow_off : kOOB;
-            qf[s] = __builtin_bit_cast(V8, buf_load16(qr, off + 32 * s));
-        }
-    }
+    q_frags(q_row<T>(p, bidx, q_off, sq, p.d, g.row_ok, pos, head, hh), qf, p.d);
 
     // ---- K/V tile loader (register staged: issue early, write to LDS late)
     const int lc = tid % CPR;
@@ -206,35 +174,13 @@ __device__ __forceinline__ void fwd_item(const FwdParams& p, char* smem, const i
         }
     };
 
-    // Per-lane LDS read addresses (kv_off image): the K row read of k-step s, 32-key half kt
-    // is kb[s & 1] + RB*4*kt + 512*(s >> 1) (RB = bytes of an 8-row block); the V^T transposed
-    // read (kt, sp, dt, part) is vb[part] + RB*(4 kt + 2 sp) + 512 dt.  Everything but the
-    // two base registers of each operand is an immediate offset of the ds_read.
-    constexpr int RB = HD * 16;                 // bytes of one 8-row block of the image
-    const int q4 = (lane & 15) >> 2;
-    int kb[2], vb[2];
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-        kb[u] = (int)(size_t)smem + kv_off<HD>(lr, 2 * u + hh);
-        const int r = 8 * u + 4 * hh + q4;
-        const int col = 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
-        vb[u] = (int)(size_t)smem + VREG + kv_off<HD>(r, col >> 3) + 8 * ((col >> 2) & 1);
-    }
-    typedef __attribute__((address_space(3))) V8 lds_v8;
-    f32x16 acc_o[ND];
-#pragma unroll
-    for (int dt = 0; dt < ND; ++dt) acc_o[dt] = f32x16{};
-    // running row max in scaled (log2) units: P = exp2(S c - m_sc); -inf until the row's first
-    // visible key
-    float m_sc = -INFINITY;
-    float l_run = 0.f;
+    constexpr int RB = HD * 16;                 // bytes of one 8-row block of the kv_off image
+    int kb[2], vb[2];                           // per-lane LDS read bases
+    k_read_bases<HD>((int)(size_t)smem, lane, kb);
+    v_read_bases<HD>((int)(size_t)smem + VREG, lane, vb);
+    SoftmaxRow<ND> sm;
 
-    // ---- the pieces of one 64-key tile
-    // K operand of S^T = K Q^T for k-step s, 32-key half `kt`, read row-wise from the LDS image
-    // of buffer `buf`
-    auto rd_k = [&](const int buf, const int s, const int kt) {
-        return *(const lds_v8*)(size_t)(kb[s & 1] + buf * TILE + kt * 4 * RB + 512 * (s >> 1));
-    };
+    // ---- the pieces of one 64-key tile (K / V in buffer `buf`)
     // V^T operand of O^T += V^T P^T for (kt, sp, dt) through the transposing LDS read
     auto rd_v = [&](const int buf, const int i) {
         const int kt = i / (2 * ND), sp = (i / ND) & 1, dt = i % ND;
@@ -244,60 +190,30 @@ __device__ __forceinline__ void fwd_item(const FwdParams& p, char* smem, const i
         const s16x8 av = {t0[0], t0[1], t0[2], t0[3], t1[0], t1[1], t1[2], t1[3]};
         return __builtin_bit_cast(V8, av);
     };
-    // score transforms of values [v0, v0 + n) (flattened st[kt][r], v = 16 kt + r); masking
-    // only where a window edge crosses the tile
+    // score features of values [v0, v0 + n) (flattened st[kt][r], v = 16 kt + r), then the edge
+    // mask where a window edge crosses the tile
     auto transform_part = [&](f32x16 (&st)[2], const int n0, const bool need_mask, const int v0,
                               const int n) {
+        if constexpr (OWN_MASK_MAX) {         // (edge_mask, fused into the feature loop)
 #pragma unroll
-        for (int v = v0; v < v0 + n; ++v) {
-            const int kt = v >> 4, r = v & 15;
-            const int key = n0 + 4 * hh + 32 * kt + (r & 3) + 8 * (r >> 2);
-            if (FEAT && p.softcap_pre > 0.f) st[kt][r] = fast_tanh(st[kt][r] * p.softcap_pre);
-            if (FEAT && p.alibi) st[kt][r] -= alibi_w * (float)abs(pos + diag - key);
-            if (need_mask && (key >= my_lr || key < my_ll)) st[kt][r] = -INFINITY;
+            for (int v = v0; v < v0 + n; ++v) {
+                const int kt = v >> 4, r = v & 15;
+                const int key = n0 + 4 * hh + key_of(v);
+                if (p.softcap_pre > 0.f) st[kt][r] = fast_tanh(st[kt][r] * p.softcap_pre);
+                if (p.alibi) st[kt][r] -= alibi_w * (float)abs(pos + diag - key);
+                if (need_mask && (key >= g.my_lr || key < g.my_ll)) st[kt][r] = -INFINITY;
+            }
+            return;
         }
-    };
-    // Deferred rescale: the running max m_sc (the exp reference) only moves once some row's
-    // true max exceeds it by more than max_slack (log2 units), so P = exp2(S c - m_sc) stays
-    // below 2^max_slack; O, l and the LSE are all relative to the same m_sc, so the result is
-    // unchanged up to rounding (the relative rounding of P in T does not depend on the scale).
-    auto rescale_o = [&](const float alpha) {
-        l_run *= alpha;
+        if (FEAT) {
 #pragma unroll
-        for (int dt = 0; dt < ND; ++dt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc_o[dt][r] *= alpha;
-    };
-    auto raise_max = [&](const float mx) {
-        const float m_new = fmaxf(m_sc, mx * c);
-        if (__any(m_new > m_sc + p.max_slack)) {
-            rescale_o(m_new == -INFINITY ? 1.f : fast_exp2(m_sc - m_new));
-            m_sc = m_new;
+            for (int v = v0; v < v0 + n; ++v) {
+                const int kt = v >> 4, r = v & 15;
+                if (p.softcap_pre > 0.f) st[kt][r] = fast_tanh(st[kt][r] * p.softcap_pre);
+                if (p.alibi) st[kt][r] -= alibi_w * (float)abs(pos + diag - (n0 + 4 * hh + key_of(v)));
+            }
         }
-    };
-    // P = exp2(S c - m c) -> T (the B operand of the PV product) for values [v0, v0 + n);
-    // the row sum accumulates the fp32 P values, as the reference's softmax does
-    // (softmax_hip.h:129-189), so the LSE is the fp32 log-sum-exp of the scores.  (Summing the
-    // rounded bf16 pairs with v_dot2c instead costs ~14 cycles a pair beside the MFMAs and moves
-    // the LSE by up to the bf16 unit roundoff, 2^-9; the fp32 adds fit the register budget only
-    // with the two-base kv_off image.)
-    typedef __attribute__((ext_vector_type(2))) float f2;
-    typedef typename DT<T>::v2 T2;
-    auto exp_part = [&](const f32x16 (&st)[2], V8 (&pb)[4], const f2 m2, float (&rs)[2],
-                        const int v0, const int n) {
-        const f2 c2 = {c, c};
-#pragma unroll
-        for (int v = v0; v < v0 + n; v += 2) {
-            const int kt = v >> 4, r = v & 15;
-            f2 x = {st[kt][r], st[kt][r + 1]};
-            x = __builtin_elementwise_fma(x, c2, -m2);
-            const float e0 = fast_exp2(x[0]), e1 = fast_exp2(x[1]);
-            rs[0] += e0;
-            rs[1] += e1;
-            const T2 e = {(T)e0, (T)e1};
-            pb[2 * kt + (r >> 3)][r & 7] = e[0];
-            pb[2 * kt + (r >> 3)][(r & 7) + 1] = e[1];
-        }
+        if (need_mask) edge_mask(st, n0, hh, g.my_lr, g.my_ll, v0, n);
     };
     // dropout on the P operand of PV (the row sums keep the undropped P, as the reference's
     // softmax does before apply_dropout, flash_fwd_kernel_hip.h): each run of 4 keys of this
@@ -318,25 +234,6 @@ __device__ __forceinline__ void fwd_item(const FwdParams& p, char* smem, const i
                     if (!drop_keep(word, i, p.keep_thr)) pb[2 * kt + (j >> 1)][(j & 1) * 4 + i] = (T)0.f;
             }
     };
-    auto exp_ref = [&]() {
-        const float mref = (m_sc == -INFINITY) ? 0.f : m_sc;
-        return f2{mref, mref};
-    };
-    // S^T = K Q^T (LDS reads one k-step ahead of the MFMAs)
-    auto qk = [&](const int ks, f32x16 (&st)[2]) {
-        st[0] = f32x16{};
-        st[1] = f32x16{};
-        V8 a0 = rd_k(ks, 0, 0), a1 = rd_k(ks, 0, 1);
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            V8 n0 = a0, n1 = a1;
-            if (s + 1 < NS) { n0 = rd_k(ks, s + 1, 0); n1 = rd_k(ks, s + 1, 1); }
-            st[0] = DT<T>::mfma32(a0, qf[s], st[0]);
-            st[1] = DT<T>::mfma32(a1, qf[s], st[1]);
-            a0 = n0;
-            a1 = n1;
-        }
-    };
     // O^T += V^T P^T (V^T reads one MFMA ahead)
     constexpr int NPV = 4 * ND;                 // PV MFMAs per tile
     auto pv = [&](const int vs, const V8 (&pb)[4]) {
@@ -345,55 +242,49 @@ __device__ __forceinline__ void fwd_item(const FwdParams& p, char* smem, const i
         for (int i = 0; i < NPV; ++i) {
             V8 nx = a;
             if (i + 1 < NPV) nx = rd_v(vs, i + 1);
-            acc_o[i % ND] = DT<T>::mfma32(a, pb[i / ND], acc_o[i % ND]);
+            sm.acc_o[i % ND] = DT<T>::mfma32(a, pb[i / ND], sm.acc_o[i % ND]);
             a = nx;
         }
     };
-    auto row_max = [&](const f32x16 (&st)[2]) {
-        float mx = st[0][0];
+    // one tile of the per-wave masked loops
+    auto masked_tile = [&](const int buf, const int n0) {
+        f32x16 st[2];
+        if constexpr (OWN_QK) {
+            st[0] = f32x16{};
+            st[1] = f32x16{};
+            V8 a0 = rd_k<T, HD>(kb, buf * TILE, 0, 0), a1 = rd_k<T, HD>(kb, buf * TILE, 0, 1);
 #pragma unroll
-        for (int r = 1; r < 16; ++r) mx = fmaxf(mx, st[0][r]);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) mx = fmaxf(mx, st[1][r]);
-        return wave_max_halves(mx);
-    };
-    auto exp_tile = [&](const f32x16 (&st)[2], V8 (&pb)[4]) {
-        float rs[2] = {0.f, 0.f};
-        exp_part(st, pb, exp_ref(), rs, 0, 32);
-        l_run += rs[0] + rs[1];
-    };
-    // The pipeline's scores are X = S c - m_sc already: P = exp2(X) -> T for values [v0, v0 + n)
-    auto expx_part = [&](const f32x16 (&st)[2], V8 (&pb)[4], float& rs, const int v0, const int n) {
-#pragma unroll
-        for (int v = v0; v < v0 + n; v += 2) {
-            const int kt = v >> 4, r = v & 15;
-            const float e0 = fast_exp2(st[kt][r]), e1 = fast_exp2(st[kt][r + 1]);
-            rs += e0;
-            rs += e1;
-            const T2 e = {(T)e0, (T)e1};
-            pb[2 * kt + (r >> 3)][r & 7] = e[0];
-            pb[2 * kt + (r >> 3)][(r & 7) + 1] = e[1];
+            for (int s = 0; s < NS; ++s) {
+                V8 n0_ = a0, n1_ = a1;
+                if (s + 1 < NS) { n0_ = rd_k<T, HD>(kb, buf * TILE, s + 1, 0); n1_ = rd_k<T, HD>(kb, buf * TILE, s + 1, 1); }
+                st[0] = DT<T>::mfma32(a0, qf[s], st[0]);
+                st[1] = DT<T>::mfma32(a1, qf[s], st[1]);
+                a0 = n0_;
+                a1 = n1_;
+            }
+        } else {
+            qk<T, HD>(kb, buf * TILE, qf, st);
         }
-    };
-    auto expx_tile = [&](const f32x16 (&st)[2], V8 (&pb)[4]) {
-        float rs = 0.f;
-        expx_part(st, pb, rs, 0, 32);
-        l_run += rs;
-    };
-    // Deferred rescale on pipeline scores: mx = this row's max of X = S c - m_sc over the new
-    // tile.  Rows still at m_sc = -inf had X computed against 0 (exp_ref) and take m_sc = mx.
-    auto rescale_x = [&](const float mx, f32x16 (&sx)[2]) {
-        const bool fresh = m_sc == -INFINITY;
-        if (__any(mx > p.max_slack || (fresh && mx != -INFINITY))) {
-            // a volatile asm cannot be speculated: keeps the rare rescale a real branch
-            // (if-converted it costs 64 VALU on every tile)
-            asm volatile("; rescale_x");
-            const float delta = fresh ? (mx == -INFINITY ? 0.f : mx) : fmaxf(mx, 0.f);
-            rescale_o(fresh ? 1.f : fast_exp2(-delta));
+        transform_part(st, n0, g.edge(n0), 0, 32);
+        if constexpr (OWN_MASK_MAX) {         // (SoftmaxRow::raise_max)
+            const float mx = row_max(st);
+            const float m_new = fmaxf(sm.m_sc, mx * c);
+            if (__any(m_new > sm.m_sc + p.max_slack)) {
+                const float alpha = m_new == -INFINITY ? 1.f : fast_exp2(sm.m_sc - m_new);
+                sm.l_run *= alpha;
 #pragma unroll
-            for (int v = 0; v < 32; ++v) sx[v >> 4][v & 15] -= delta;
-            m_sc = fresh ? (mx == -INFINITY ? -INFINITY : mx) : m_sc + delta;
+                for (int dt = 0; dt < ND; ++dt)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) sm.acc_o[dt][r] *= alpha;
+                sm.m_sc = m_new;
+            }
+        } else {
+            sm.raise_max(row_max(st), c, p.max_slack);
         }
+        V8 pb[4];
+        exp_tile<T>(sm, st, pb, c);
+        drop_tile(pb, n0);
+        pv(buf, pb);
     };
 
     // ---- tiles that need per-wave masking / skipping: one tile in flight, two LDS buffers
@@ -410,41 +301,11 @@ __device__ __forceinline__ void fwd_item(const FwdParams& p, char* smem, const i
         for (int nb = lo; nb < hi; ++nb) {
             const bool more = nb + 1 < hi;
             if (more) load_to(nb + 1, kr, vr);
-            const int n0 = nb * kBlockN;
-            const bool active = wave_ok && n0 < w_lr_max && n0 + kBlockN > w_ll_min;
-            if (active) {
-                f32x16 st[2];
-                qk(buf, st);
-                transform_part(st, n0, (n0 + kBlockN > w_lr_min) || (n0 < w_ll_max), 0, 32);
-                raise_max(row_max(st));
-                V8 pb[4];
-                exp_tile(st, pb);
-                drop_tile(pb, n0);
-                pv(buf, pb);
-            }
+            if (g.active(nb * kBlockN)) masked_tile(buf, nb * kBlockN);
             if (more) store_from(buf ^ 1, kr, vr);
             __syncthreads();
             buf ^= 1;
         }
-    };
-
-    // V^T operand through inline-asm transposing reads: the compiler's waitcnt pass treats
-    // the ds_read_tr builtin as aliasing every in-flight LDS-DMA and would drain the DMA queue
-    // (vmcnt(0)) before it; the asm reads are covered by explicit lgkmcnt waits instead.
-    // Byte offset OFF (buffer + row block) is an immediate.
-    auto rd_v_asm = [&](auto OFF) {
-        constexpr int off = decltype(OFF)::value;
-        s16x4 t0, t1;
-        asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(t0) : "v"(vb[0]), "i"(off));
-        asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(t1) : "v"(vb[1]), "i"(off));
-        const s16x8 av = {t0[0], t0[1], t0[2], t0[3], t1[0], t1[1], t1[2], t1[3]};
-        return __builtin_bit_cast(V8, av);
-    };
-    auto lgkm_wait = [&](auto N) {
-        constexpr int n = decltype(N)::value;
-        __builtin_amdgcn_s_waitcnt(0xC07F | (n << 8));
-        // the MFMA consuming the asm-read registers must not be scheduled above the wait
-        __builtin_amdgcn_sched_barrier(0);
     };
 
     // ---- tiles every row of the workgroup sees in full: two-stage software pipeline.
@@ -461,16 +322,10 @@ __device__ __forceinline__ void fwd_item(const FwdParams& p, char* smem, const i
     static_assert(IPW >= 1 && IPW * 1024 * NW == TILE, "DMA geometry");
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
     int dma_k[IPW], dma_v[IPW];                    // per-lane byte offsets within a tile
-    constexpr int PPB = CPR / 8;                   // DMA pieces per 8-row block
 #pragma unroll
     for (int i = 0; i < IPW; ++i) {
-        // piece g = 8 rows x 8 chunks of the kv_off image: lane l lands at g KiB + 16 l
-        const int g = wave * IPW + i;
-        const int r = 8 * (g / PPB) + (lane & 31) / 4;
-        const int cch = 8 * (g % PPB) + 4 * (lane >> 5) + ((lane & 3) ^ ((r >> 2) & 3));
-        const bool ok = cch * 8 < p.d;
-        dma_k[i] = ok ? r * (int)p.k_row * 2 + cch * 16 : kOOB;
-        dma_v[i] = ok ? r * (int)p.v_row * 2 + cch * 16 : kOOB;
+        dma_k[i] = dma_piece_d<HD>(wave * IPW + i, lane, (int)p.k_row * 2, p.d);
+        dma_v[i] = dma_piece_d<HD>(wave * IPW + i, lane, (int)p.v_row * 2, p.d);
     }
     typedef __attribute__((address_space(3))) void lds_void;
     auto dma_tile = [&](const int nb, const int buf) {
@@ -480,46 +335,26 @@ __device__ __forceinline__ void fwd_item(const FwdParams& p, char* smem, const i
         const int vso = __builtin_amdgcn_readfirstlane(nb * kBlockN * (int)p.v_row * 2);
 #pragma unroll
         for (int i = 0; i < IPW; ++i) {
-            const int g = wave_u * IPW + i;
+            const int piece = wave_u * IPW + i;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(
-                krs, (lds_void*)(smem + buf * TILE + g * 1024), 16, dma_k[i], kso, 0, 0);
+                krs, (lds_void*)(smem + buf * TILE + piece * 1024), 16, dma_k[i], kso, 0, 0);
             __builtin_amdgcn_raw_ptr_buffer_load_lds(
-                vrs, (lds_void*)(smem + VREG + buf * TILE + g * 1024), 16, dma_v[i], vso, 0, 0);
+                vrs, (lds_void*)(smem + VREG + buf * TILE + piece * 1024), 16, dma_v[i], vso, 0, 0);
         }
     };
-    // counted vmcnt (the DMA writes are invisible to the compiler's waitcnt tracking) + a
-    // barrier that the compiler may not move memory operations across
     constexpr int NDMA = 2 * IPW;                  // vmem instructions per tile per wave
-    auto publish = [&](const bool one_in_flight) {
-        if (one_in_flight) __builtin_amdgcn_s_waitcnt(waitcnt_vm(NDMA));
-        else __builtin_amdgcn_s_waitcnt(0x0F70);
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-    };
     // D = 256 (no pipeline, NBUF = 2): the per-wave masked loop with K/V by LDS-DMA, tile
     // j+1 in flight while tile j computes (no staging registers: the 512-register budget is
     // taken by the Q fragments and the O accumulator)
     auto dma_range = [&](const int lo, const int hi) {
         if (lo >= hi) return;
         dma_tile(lo, 0);
-        publish(false);
+        publish();
         int buf = 0;
         for (int nb = lo; nb < hi; ++nb) {
             if (nb + 1 < hi) dma_tile(nb + 1, buf ^ 1);
-            const int n0 = nb * kBlockN;
-            const bool active = wave_ok && n0 < w_lr_max && n0 + kBlockN > w_ll_min;
-            if (active) {
-                f32x16 st[2];
-                qk(buf, st);
-                transform_part(st, n0, (n0 + kBlockN > w_lr_min) || (n0 < w_ll_max), 0, 32);
-                raise_max(row_max(st));
-                V8 pb[4];
-                exp_tile(st, pb);
-                drop_tile(pb, n0);
-                pv(buf, pb);
-            }
-            publish(false);
+            if (g.active(nb * kBlockN)) masked_tile(buf, nb * kBlockN);
+            publish();
             buf ^= 1;
         }
     };
@@ -533,24 +368,20 @@ __device__ __forceinline__ void fwd_item(const FwdParams& p, char* smem, const i
     // only; the VALU of a tile splits evenly between the two MFMA phases (per wave and tile:
     // a = 32 v_exp + 32 fp32 row-sum adds + 16 cvt beside 16 QK^T MFMAs, b = 32 fma + 16 max3
     // beside 16 PV MFMAs), each within the MFMA gaps.  The edge mask runs after phase b on the edge tiles only.
-    const int lim_e = my_lr - 4 * hh;            // right edge of this lane's keys, minus its offset
+    const int lim_e = g.my_lr - 4 * hh;           // right edge of this lane's keys, minus its offset
     auto pipe_range = [&](const int lo, const int hm, const int hi) {
         const bool third = lo + 2 < hi;
         dma_tile(lo, 0);
         dma_tile(lo + 1, 1);
         if (third) dma_tile(lo + 2, 2);
-        publish(third);
+        publish<NDMA>(third ? NDMA : 0);
         // scores ping-pong between sa and sb from step to step (st: this tile, sn: the next),
         // so the QK^T accumulators never need a register copy onto a loop-carried value
         f32x16 sa[2], sb[2];
-        qk(0, sa);
+        qk<T, HD>(kb, 0, qf, sa);
         transform_part(sa, lo * kBlockN, lo >= hm, 0, 32);
-        raise_max(row_max(sa));
-        {
-            const float mr = exp_ref()[0];
-#pragma unroll
-            for (int v = 0; v < 32; ++v) sa[v >> 4][v & 15] = __builtin_fmaf(sa[v >> 4][v & 15], c, -mr);
-        }
+        sm.raise_max(row_max(sa), c, p.max_slack);
+        scale_shift(sa, c, sm.exp_ref());
         const int nsteps = hi - lo - 1;
         auto step = [&](auto KB, auto VB, auto WB, const int j, f32x16 (&st)[2], f32x16 (&sn)[2]) {
             constexpr int ks = decltype(KB)::value, vs = decltype(VB)::value, wb = decltype(WB)::value;
@@ -563,15 +394,15 @@ __device__ __forceinline__ void fwd_item(const FwdParams& p, char* smem, const i
             V8 pb[4];
             float rs = 0.f;                       // fp32 row sum of P_j
             constexpr int EV = 32 / (2 * NS);     // exp values per QK^T MFMA
-            V8 a0 = rd_k(ks, 0, 0), a1 = rd_k(ks, 0, 1);
+            V8 a0 = rd_k<T, HD>(kb, ks * TILE, 0, 0), a1 = rd_k<T, HD>(kb, ks * TILE, 0, 1);
 #pragma unroll
             for (int s = 0; s < NS; ++s) {
                 V8 n0 = a0, n1 = a1;
-                if (s + 1 < NS) { n0 = rd_k(ks, s + 1, 0); n1 = rd_k(ks, s + 1, 1); }
+                if (s + 1 < NS) { n0 = rd_k<T, HD>(kb, ks * TILE, s + 1, 0); n1 = rd_k<T, HD>(kb, ks * TILE, s + 1, 1); }
                 sn[0] = DT<T>::mfma32(a0, qf[s], sn[0]);
-                expx_part(st, pb, rs, (2 * s) * EV, EV);
+                expx_part<T>(st, pb, rs, (2 * s) * EV, EV);
                 sn[1] = DT<T>::mfma32(a1, qf[s], sn[1]);
-                expx_part(st, pb, rs, (2 * s + 1) * EV, EV);
+                expx_part<T>(st, pb, rs, (2 * s + 1) * EV, EV);
                 // pins the row-sum adds into this MFMA gap: unpinned, the compiler sinks them
                 // below phase b (rs is only read there) into a VALU-only run of 32 adds
                 // (+1.5-2 % C2, same-box A/B)
@@ -581,29 +412,12 @@ __device__ __forceinline__ void fwd_item(const FwdParams& p, char* smem, const i
                 if (SCHED_FENCE) __builtin_amdgcn_sched_barrier(0);
             }
             // phase b: O += V_j^T P_j on the MFMA pipe; on the VALU X_{j+1} = S_{j+1} c - m_sc
-            // (transforms and edge mask first) and its row max; V^T read two MFMAs ahead (asm
-            // reads, explicit lgkmcnt)
+            // (transforms and edge mask first) and its row max, beside the asm V^T read ring
             constexpr int MV = 32 / NPV;          // score values per PV MFMA
-            auto voffs = [&](auto I) {             // immediate offset of PV operand I
-                constexpr int i = decltype(I)::value;
-                return std::integral_constant<int, vs * TILE + (4 * (i / (2 * ND)) + 2 * ((i / ND) & 1)) * RB + 512 * (i % ND)>{};
-            };
-            const float mr = exp_ref()[0];
+            const float mr = sm.exp_ref();
             float mx = -INFINITY;
-            V8 ring[3];
-            ring[0] = rd_v_asm(voffs(std::integral_constant<int, 0>{}));
-            ring[1] = rd_v_asm(voffs(std::integral_constant<int, 1>{}));
-            static_for<NPV>([&](auto I) {
+            pv_ring<T, HD, vs * TILE>(sm.acc_o, vb, pb, [&](auto I) {
                 constexpr int i = decltype(I)::value;
-                if constexpr (i + 2 < NPV) {
-                    ring[(i + 2) % 3] = rd_v_asm(voffs(std::integral_constant<int, i + 2>{}));
-                    lgkm_wait(std::integral_constant<int, 4>{});
-                } else if constexpr (i + 1 < NPV) {
-                    lgkm_wait(std::integral_constant<int, 2>{});
-                } else {
-                    lgkm_wait(std::integral_constant<int, 0>{});
-                }
-                acc_o[i % ND] = DT<T>::mfma32(ring[i % 3], pb[i / ND], acc_o[i % ND]);
                 if (FEAT) transform_part(sn, (j + 1) * kBlockN, false, i * MV, MV);
 #pragma unroll
                 for (int v = i * MV; v < (i + 1) * MV; ++v)
@@ -618,36 +432,19 @@ __device__ __forceinline__ void fwd_item(const FwdParams& p, char* smem, const i
             // an opaque use pins the max chain inside phase b (else it is sunk below the edge
             // branch, out of the MFMA gaps)
             asm volatile("" : "+v"(mx));
-            l_run += rs;
-            if (j + 1 >= hm) {                    // edge tile: mask, then the row max again
-                const int lim_t = lim_e - (j + 1) * kBlockN;
-                float mm = -INFINITY;
-#pragma unroll
-                for (int v = 0; v < 32; ++v) {
-                    const int off = 32 * (v >> 4) + ((v & 15) & 3) + 8 * ((v & 15) >> 2);
-                    if (off >= lim_t) sn[v >> 4][v & 15] = -INFINITY;
-                    mm = fmaxf(mm, sn[v >> 4][v & 15]);
-                }
-                mx = mm;
-            }
-            // the decision needs no row max: some lane's half-row max passes the slack iff some
-            // row's does, so the halves are combined only on the (rare) rescale path
-            if (__any(mx > p.max_slack || (m_sc == -INFINITY && mx != -INFINITY)))
-                rescale_x(wave_max_halves(mx), sn);
-            publish(issue);                       // tile j+2 landed everywhere
+            sm.l_run += rs;
+            // edge tile: mask, then the row max again
+            if (j + 1 >= hm) mx = right_mask_max(sn, lim_e - (j + 1) * kBlockN);
+            sm.rescale_x_halves(mx, sn, p.max_slack);
+            publish<NDMA>(issue ? NDMA : 0);      // tile j+2 landed everywhere
         };
         typedef std::integral_constant<int, 0> I0;
         typedef std::integral_constant<int, 1> I1;
         typedef std::integral_constant<int, 2> I2;
         typedef std::integral_constant<int, 3> I3;
-        // step r (tile j = lo + r) reads K of j+1 from buffer (r+1)%4 and V of j from r%4.
-        // Causal diagonal / right window edge: a wave stops after the last tile any of its rows
-        // sees (visible keys are contiguous) — drains it, then only issues its DMA share and
-        // joins the barriers for the rest of the workgroup's steps (the same barrier count).
-        // The skipped tiles would add exact zeros, so results are bit-identical, and the
-        // wave's SIMD partner gets the whole issue port meanwhile.
-        const int t_w = __builtin_amdgcn_readfirstlane((w_lr_max + kBlockN - 1) / kBlockN - 1);
-        const int nsteps_w = __builtin_amdgcn_readfirstlane(wave_ok ? max(0, min(nsteps, t_w - lo)) : nsteps);
+        // step r (tile j = lo + r) reads K of j+1 from buffer (r+1)%4 and V of j from r%4; a
+        // wave runs the steps up to the last tile any of its rows sees (RowGeom::steps_w)
+        const int nsteps_w = g.steps_w(nsteps, lo);
         int r = 0;
         while (r < nsteps_w) {
             step(I1{}, I0{}, I3{}, lo + r, sa, sb);
@@ -663,54 +460,29 @@ __device__ __forceinline__ void fwd_item(const FwdParams& p, char* smem, const i
         // leaves early still has its DMA share of tile j+3 in flight, and the builtin
         // transposing read would make the compiler drain it (vmcnt(0)) first
         V8 pb[4];
-        if (nsteps_w & 1) expx_tile(sb, pb);
-        else expx_tile(sa, pb);
-        auto pv_asm = [&](auto VB) {
-            constexpr int vs = decltype(VB)::value;
-            auto voffs = [&](auto I) {
-                constexpr int i = decltype(I)::value;
-                return std::integral_constant<int, vs * TILE + (4 * (i / (2 * ND)) + 2 * ((i / ND) & 1)) * RB + 512 * (i % ND)>{};
-            };
-            V8 ring[3];
-            ring[0] = rd_v_asm(voffs(std::integral_constant<int, 0>{}));
-            ring[1] = rd_v_asm(voffs(std::integral_constant<int, 1>{}));
-            static_for<NPV>([&](auto I) {
-                constexpr int i = decltype(I)::value;
-                if constexpr (i + 2 < NPV) {
-                    ring[(i + 2) % 3] = rd_v_asm(voffs(std::integral_constant<int, i + 2>{}));
-                    lgkm_wait(std::integral_constant<int, 4>{});
-                } else if constexpr (i + 1 < NPV) {
-                    lgkm_wait(std::integral_constant<int, 2>{});
-                } else {
-                    lgkm_wait(std::integral_constant<int, 0>{});
-                }
-                acc_o[i % ND] = DT<T>::mfma32(ring[i % 3], pb[i / ND], acc_o[i % ND]);
-            });
-        };
+        if (nsteps_w & 1) expx_tile<T>(sm, sb, pb);
+        else expx_tile<T>(sm, sa, pb);
         switch (nsteps_w & 3) {
-            case 0: pv_asm(I0{}); break;
-            case 1: pv_asm(I1{}); break;
-            case 2: pv_asm(I2{}); break;
-            default: pv_asm(I3{}); break;
+            case 0: pv_ring<T, HD, 0 * TILE>(sm.acc_o, vb, pb, [](auto) {}); break;
+            case 1: pv_ring<T, HD, 1 * TILE>(sm.acc_o, vb, pb, [](auto) {}); break;
+            case 2: pv_ring<T, HD, 2 * TILE>(sm.acc_o, vb, pb, [](auto) {}); break;
+            default: pv_ring<T, HD, 3 * TILE>(sm.acc_o, vb, pb, [](auto) {}); break;
         }
         // the steps this wave skips: its DMA share and the barriers only
         for (; r < nsteps; ++r) {
             const int j = lo + r;
             const bool issue = j + 3 < hi;
             if (issue) dma_tile(j + 3, (r + 3) & 3);
-            publish(issue);
+            publish<NDMA>(issue ? NDMA : 0);
         }
         __syncthreads();
     };
-    // Key tiles: [nb_lo, f_lo) cross the left window edge (per-wave masked loop);
-    // [f_lo, f_hi) every row of the workgroup sees in full; [f_hi, nb_hi) cross the right
-    // window edge / the end of the keys.  The last two ranges run through the pipeline.
+    // Key tiles (RowGeom::pipe_split): [nb_lo, f_lo) run through the per-wave masked loop, the
+    // rest through the pipeline, [f_hi, nb_hi) of them masked on the way.
     int f_lo = nb_hi, f_hi = nb_hi;
     if (PIPE && p.pipe && !paged && !kv8 && !(FEAT && p.drop)) {
-        const int ll_max = lim_l(pos_hi), lr_min = lim_r(pos_lo);
-        f_lo = max(nb_lo, (ll_max + kBlockN - 1) / kBlockN);
-        f_hi = max(f_lo, min(nb_hi, lr_min / kBlockN));
-        if (nb_hi - f_lo < 2 || (p.pipe == 2 && f_hi - f_lo < 2)) f_lo = f_hi = nb_hi;
+        g.pipe_split(nb_lo, nb_hi, f_lo, f_hi);
+        if (p.pipe == 2 && f_hi - f_lo < 2) f_lo = f_hi = nb_hi;
     }
     if (p.prio_hi && __builtin_amdgcn_readfirstlane(wave) >= NW / 2) __builtin_amdgcn_s_setprio(1);
     // (fwd_pipe=2: edge tiles through the per-wave masked loop instead - A/B knob)
@@ -723,46 +495,37 @@ __device__ __forceinline__ void fwd_item(const FwdParams& p, char* smem, const i
     masked_range(p_hi, nb_hi);
 
     // ---- epilogue: normalise, write O (or the split partial) and LSE
-    const float l_full = wave_sum_halves(l_run);
-    const bool empty = (l_full == 0.f) || (l_full != l_full);
-    const float inv = empty ? 1.f : 1.f / l_full;
-    if (!row_ok) return;
+    const RowNorm n = sm.norm();
+    const float inv = n.inv;
+    if (!g.row_ok) return;
     if (is_split) {
         const int64_t rid = (((int64_t)split * p.b + bidx) * p.h + head) * p.seqlen_q + pos;
         float* oa = p.oaccum + rid * HD;
 #pragma unroll
         for (int dt = 0; dt < ND; ++dt)
 #pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int d = 32 * dt + 8 * g + 4 * hh;
-                f32x4 v = {acc_o[dt][4 * g] * inv, acc_o[dt][4 * g + 1] * inv,
-                           acc_o[dt][4 * g + 2] * inv, acc_o[dt][4 * g + 3] * inv};
+            for (int q = 0; q < 4; ++q) {
+                const int d = 32 * dt + 8 * q + 4 * hh;
+                f32x4 v = {sm.acc_o[dt][4 * q] * inv, sm.acc_o[dt][4 * q + 1] * inv,
+                           sm.acc_o[dt][4 * q + 2] * inv, sm.acc_o[dt][4 * q + 3] * inv};
                 *reinterpret_cast<f32x4*>(oa + d) = v;
             }
-        if (hh == 0) p.lseaccum[rid] = empty ? -INFINITY : (m_sc + __log2f(l_full)) * kLn2;
+        if (hh == 0) p.lseaccum[rid] = n.empty ? -INFINITY : sm.lse(n);
         return;
     }
-    T* orow = reinterpret_cast<T*>(p.o) + (int64_t)bidx * p.o_batch +
-              (int64_t)(q_off + pos) * p.o_row + (int64_t)head * p.o_head;
     if constexpr (SINK) {
         // attention sink, once per row, outside the key loop: `head` is the query head (GQA rows
         // are packed per kv head); the entries refuse dropout with a sink, so no rp_keep here
         float inv_o = inv, lse_o = INFINITY;
-        if (!empty) {
-            const SinkMerge sm = sink_merge((m_sc + __log2f(l_full)) * kLn2, p.sink[head]);
-            inv_o = inv * sm.f;
-            lse_o = sm.lse;
+        if (!n.empty) {
+            const SinkMerge sk_m = sink_merge(sm.lse(n), p.sink[head]);
+            inv_o = inv * sk_m.f;
+            lse_o = sk_m.lse;
         }
-        store_o_row16<T, ND>(orow, acc_o, inv_o, p.d, hh);
-        if (p.lse && hh == 0)
-            p.lse[(int64_t)bidx * p.lse_batch + (int64_t)head * p.lse_head + q_off + pos] = lse_o;
+        store_row<T, ND>(p, bidx, q_off, pos, head, hh, sm.acc_o, inv_o, p.d, lse_o);
         return;
     }
-    store_o_row16<T, ND>(orow, acc_o, (FEAT && p.drop) ? inv * p.rp_keep : inv, p.d, hh);
-    if (p.lse && hh == 0) {
-        p.lse[(int64_t)bidx * p.lse_batch + (int64_t)head * p.lse_head + q_off + pos] =
-            empty ? INFINITY : (m_sc + __log2f(l_full)) * kLn2;
-    }
+    store_row<T, ND>(p, bidx, q_off, pos, head, hh, sm.acc_o, (FEAT && p.drop) ? inv * p.rp_keep : inv, p.d, sm.lse(n));
 }
 
 // Grid: one workgroup per item or persistent, as plan_fwd chose; fwd_walk (fmha_fwd_sched.h)
