@@ -127,7 +127,7 @@ void fmha_set_rng_state(uint64_t seed, uint64_t offset);
 void fmha_set_rng_state_device(const int64_t* seed_ptr, const int64_t* offset_ptr,
                                uint64_t offset_add, int64_t* rng_out);
 
-/* Library version / build identification, e.g. "xf-fmha-gfx950 2.13".  2.0 (round 3) changed
+/* Library version / build identification, e.g. "xf-fmha-gfx950 2.14".  2.0 (round 3) changed
  * argument lists of existing symbols; 2.1 exports those under _v2 names (see INTEGRATION.md
  * "ABI history"). */
 const char* fmha_version(void);
@@ -598,6 +598,69 @@ void fmha_mla_decode_sparse_fp8(void* q, void* kv_cache8, void* o, void* softmax
                                 int32_t num_blocks, int32_t page_block_size,
                                 const int64_t* strides /* q then o: batch,row,head */,
                                 float softmax_scale, int32_t num_splits, bool is_fp16, hipStream_t stream);
+
+/* --------------------------- MLA indexer: fp8 index-key cache, its append, index logits (2.14) */
+
+/* DeepSeek-V3.2's "lightning indexer" chooses the tokens fmha_mla_decode_sparse attends over:
+ *   logit[t, s] = sum_h w[t, h] * relu( q_idx[t, h, :] . k_idx[s, :] )      (64 heads x 128 features)
+ * (DeepGEMM's fp8_paged_mqa_logits; the cache is what vLLM's indexer_k_quant_and_cache writes).
+ *
+ * THE INDEX-KEY CACHE: bytes [num_blocks, page_block_size * 132], contiguous, 16-byte aligned,
+ * page_block_size % 16 == 0.  One block: bytes [0, page * 128) are `page` rows of 128 OCP e4m3fn
+ * features, bytes [page * 128, page * 132) `page` fp32 descales, one per row.  Slot s = block *
+ * page + row, the latent cache's numbering: the two caches share block table and slot mapping.
+ * The key the logits are defined over is k[s, d] = float(e4m3[s, d]); descale[s] (> 0) multiplies
+ * the head sum once, which is the same thing because ReLU is positively homogeneous.
+ *
+ * fmha_mla_index_cache_append_fp8: one launch, no scratch, no host sync (capturable in a graph).
+ *   k [num_tokens, 128] bf16 (fp16 for is_fp16) by its row stride in ELEMENTS
+ *   slot_mapping int64 [num_tokens]; a negative slot, or one >= num_blocks * page_block_size,
+ *          writes nothing
+ *   scale_fmt 0: per row amax = max |float(x)|, descale = amax / 448.0f (1.0f when amax == 0),
+ *          byte = e4m3fn round-to-nearest-even of clamp(float(x) * (1.0f / descale), -448, 448):
+ *          fmha_mla_cache_append_fp8's quantiser with one scale for the row;
+ *          1 ("ue8m0"): the descale is first replaced by the smallest power of two >= amax / 448.0f,
+ *          at least 2^-126, computed on the fp32 exponent bits.
+ * num_tokens == 0 launches nothing and succeeds.  Refused with an error, the cache untouched: a
+ * NULL pointer, a row stride that is negative or no multiple of 8, k / index_cache not 16-byte
+ * aligned or slot_mapping not 8-byte aligned, a page size that is no positive multiple of 16, a
+ * negative count, a scale_fmt other than 0 and 1. */
+void fmha_mla_index_cache_append_fp8(const void* k, int64_t k_row_stride, void* index_cache,
+                                     const void* slot_mapping, int32_t num_tokens, int32_t num_blocks,
+                                     int32_t page_block_size, int32_t scale_fmt, bool is_fp16,
+                                     hipStream_t stream);
+
+/* fmha_mla_index_logits: the fused logits, one launch of fmha_mla_index_logits_kernel<heads>
+ * (fmha_last_kernel() names it), no scratch, no split combine (every logit has one writer), no
+ * host sync (capturable in a graph).
+ *   q8      [batch, seqlen_q, heads, 128] e4m3fn bytes by q_strides = {batch, row, head} in
+ *           ELEMENTS (bytes), last dimension contiguous, every row 16-byte aligned; heads 32 or 64
+ *   weights fp32 [batch * seqlen_q, heads], contiguous: q's own quantisation scale, the softmax
+ *           scale and heads^-1/2 are folded in by the caller (DeepGEMM's convention); any sign
+ *   block_table int32 [batch, block_table_stride], context_lens int32 [batch]
+ *   logits  fp32 [batch * seqlen_q, logits_row_stride], logits_row_stride >= max_seqlen_k
+ *   max_seqlen_k <= block_table_stride * page_block_size: the columns written per row
+ * For row r = b * seqlen_q + i: n = min(context_lens[b], max_seqlen_k), vis = clamp(n - seqlen_q +
+ * i + 1, 0, n) (bottom-right causal, fmha_mla_decode's rule);
+ *   s < vis:                 logits[r, s] = descale[b, s] * sum_h weights[r, h] *
+ *                                           max(0, sum_d float(q8[b, i, h, d]) * float(k8[b, s, d]))
+ *   vis <= s < max_seqlen_k: logits[r, s] = -inf (so torch.topk over the row is valid as it is)
+ * and columns >= max_seqlen_k are never touched.  A block-table entry outside [0, num_blocks) is
+ * never turned into an address: its keys give -inf.  The grid is batch x ceil(max_seqlen_k /
+ * FMHA_MLA_INDEX_CHUNK) workgroups, sized from max_seqlen_k alone.
+ * batch_size == 0 validates, launches nothing and succeeds.  Refused with an error, outputs
+ * untouched: a NULL pointer, heads other than 32 and 64, head_size != 128, seqlen_q < 1, a negative
+ * batch, a page size that is no positive multiple of 16, num_blocks < 1, max_seqlen_k outside [0,
+ * block_table_stride * page_block_size], logits_row_stride < max_seqlen_k, q strides that are
+ * negative or no multiple of 16, q8 / index_cache not 16-byte aligned or another pointer not 4-byte
+ * aligned, a launch larger than one grid covers. */
+#define FMHA_MLA_INDEX_CHUNK 1024
+void fmha_mla_index_logits(const void* q8, const void* weights, const void* index_cache, void* logits,
+                           const void* block_table, int32_t block_table_stride, const void* context_lens,
+                           int32_t seqlen_q, int32_t max_seqlen_k, int32_t batch_size, int32_t num_heads,
+                           int32_t head_size /* 128 */, int32_t num_blocks, int32_t page_block_size,
+                           const int64_t* q_strides /* batch,row,head */, int64_t logits_row_stride,
+                           hipStream_t stream);
 
 /* ------------------------- MLA prefill: head size 192 for Q K^T, 128 for V (2.12) */
 

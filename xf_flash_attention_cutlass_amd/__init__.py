@@ -48,6 +48,10 @@ from .interface import (  # noqa: E402
     flash_mla_with_kvcache,
     merge_attn_states,
     mla_cache_append_fp8,
+    mla_index_cache_append_fp8,
+    mla_index_cache_block_bytes,
+    mla_index_logits,
+    mla_index_topk_slots,
     mla_fp8_cache_row_bytes,
     quantize_fp8,
 )
@@ -66,6 +70,10 @@ __all__ = [
     "flash_attn_mla_func",
     "flash_attn_mla_varlen_func",
     "mla_cache_append_fp8",
+    "mla_index_cache_append_fp8",
+    "mla_index_cache_block_bytes",
+    "mla_index_logits",
+    "mla_index_topk_slots",
     "mla_fp8_cache_row_bytes",
     "quantize_fp8",
     "merge_attn_states",

@@ -525,7 +525,7 @@ const char* fmha_last_error(void) { return g_err.c_str(); }
 int fmha_last_status(void) { return g_status; }
 int fmha_last_num_splits(void) { return g_last_splits; }
 const char* fmha_last_kernel(void) { return g_last_kernel; }
-const char* fmha_version(void) { return XFA_VARIANTS ? "xf-fmha-gfx950 2.13 (variants)" : "xf-fmha-gfx950 2.13"; }
+const char* fmha_version(void) { return XFA_VARIANTS ? "xf-fmha-gfx950 2.14 (variants)" : "xf-fmha-gfx950 2.14"; }
 
 void fmha_set_rng_state(uint64_t seed, uint64_t offset) {
     g_seed = seed;
@@ -1679,6 +1679,93 @@ void fmha_mla_decode_sparse_fp8(void* q, void* kv_cache8, void* o, void* softmax
     mla_sparse_run("fmha_mla_decode_sparse_fp8", true, q, kv_cache8, o, softmax_lse, indices,
                    indices_batch_stride, indices_row_stride, topk, seqlen_q, batch_size, num_heads, head_size,
                    head_size_v, num_blocks, page_block_size, strides, softmax_scale, num_splits, is_fp16, stream);
+}
+
+// ---- MLA indexer: the append into the fp8 index-key cache and the fused index logits ---------
+static_assert(FMHA_MLA_INDEX_CHUNK == kMlaIndexChunk || XFA_MLA_INDEX_CHUNK != 1024,
+              "the header's chunk is the kernel's (but for an A/B build that sets its own)");
+
+void fmha_mla_index_cache_append_fp8(const void* k, int64_t k_row_stride, void* index_cache,
+                                     const void* slot_mapping, int32_t num_tokens, int32_t num_blocks,
+                                     int32_t page_block_size, int32_t scale_fmt, bool is_fp16,
+                                     hipStream_t stream) {
+    try {
+        clear_error();
+        REQUIRE(k && index_cache && slot_mapping,
+                "k, index_cache and slot_mapping must be non-null device pointers");
+        REQUIRE(num_tokens >= 0 && num_blocks >= 0,
+                "num_tokens and num_blocks must be non-negative (got %d, %d)", num_tokens, num_blocks);
+        REQUIRE(page_block_size > 0 && page_block_size % 16 == 0,
+                "page_block_size must be a positive multiple of 16 (got %d)", page_block_size);
+        REQUIRE(scale_fmt == 0 || scale_fmt == 1, "scale_fmt must be 0 (fp32) or 1 (ue8m0) (got %d)", scale_fmt);
+        REQUIRE(k_row_stride >= 0 && k_row_stride % 8 == 0,
+                "the row stride must be a non-negative multiple of 8 elements (16 bytes): got %lld",
+                (long long)k_row_stride);
+        REQUIRE(!((((uintptr_t)k) | ((uintptr_t)index_cache)) & 15),
+                "k and index_cache must be 16-byte aligned device pointers");
+        REQUIRE(!(((uintptr_t)slot_mapping) & 7), "slot_mapping must be an 8-byte aligned device pointer (int64)");
+        if (num_tokens == 0) return;
+        MlaIndexAppendParams p{};
+        p.k = k; p.cache = index_cache; p.slot = (const int64_t*)slot_mapping;
+        p.k_row = k_row_stride;
+        p.slots = (int64_t)num_blocks * page_block_size;
+        p.page = page_block_size; p.tokens = num_tokens; p.ue8m0 = scale_fmt;
+        hip_ok(launch_mla_index_append_fp8(p, is_fp16, stream), "MLA index cache append launch");
+    } catch (...) {
+        fail(9, "internal error in fmha_mla_index_cache_append_fp8");
+    }
+}
+
+void fmha_mla_index_logits(const void* q8, const void* weights, const void* index_cache, void* logits,
+                           const void* block_table, int32_t block_table_stride, const void* context_lens,
+                           int32_t seqlen_q, int32_t max_seqlen_k, int32_t batch_size, int32_t num_heads,
+                           int32_t head_size, int32_t num_blocks, int32_t page_block_size,
+                           const int64_t* q_strides, int64_t logits_row_stride, hipStream_t stream) {
+    try {
+        begin_fwd();
+        REQUIRE(q8 && weights && index_cache && logits,
+                "q8, weights, index_cache and logits must be non-null device pointers");
+        REQUIRE(block_table && context_lens, "block_table and context_lens must be non-null device pointers");
+        REQUIRE(q_strides, "q_strides must be a non-null pointer (batch, row, head)");
+        REQUIRE(num_heads == 32 || num_heads == 64, "the index logits support 32 or 64 heads (got %d)", num_heads);
+        REQUIRE(head_size == 128, "the index logits support head_size 128 only (got %d)", head_size);
+        REQUIRE(seqlen_q >= 1, "seqlen_q must be at least 1 (got %d)", seqlen_q);
+        REQUIRE(batch_size >= 0, "batch size must be non-negative (got %d)", batch_size);
+        REQUIRE(page_block_size > 0 && page_block_size % 16 == 0,
+                "page_block_size must be a positive multiple of 16 (got %d)", page_block_size);
+        REQUIRE(num_blocks >= 1, "num_blocks must be at least 1 (got %d)", num_blocks);
+        REQUIRE(block_table_stride >= 0 && max_seqlen_k >= 0 &&
+                    (int64_t)max_seqlen_k <= (int64_t)block_table_stride * page_block_size,
+                "max_seqlen_k must lie in [0, block_table_stride * page_block_size] (got %d, table %d x page %d)",
+                max_seqlen_k, block_table_stride, page_block_size);
+        REQUIRE(logits_row_stride >= max_seqlen_k, "logits_row_stride must be at least max_seqlen_k (got %lld, %d)",
+                (long long)logits_row_stride, max_seqlen_k);
+        const int ext[3] = {batch_size, seqlen_q, num_heads};
+        for (int i = 0; i < 3; ++i)
+            REQUIRE(q_strides[i] >= 0 && (ext[i] <= 1 || q_strides[i] % 16 == 0),
+                    "q strides must be non-negative multiples of 16 elements (bytes): stride %d is %lld", i,
+                    (long long)q_strides[i]);
+        REQUIRE(!((((uintptr_t)q8) | ((uintptr_t)index_cache)) & 15),
+                "q8 and index_cache must be 16-byte aligned device pointers");
+        REQUIRE(!((((uintptr_t)weights) | ((uintptr_t)logits) | ((uintptr_t)block_table) | ((uintptr_t)context_lens)) & 3),
+                "weights, logits, block_table and context_lens must be 4-byte aligned device pointers");
+        const int64_t chunks = ((int64_t)max_seqlen_k + kMlaIndexChunk - 1) / kMlaIndexChunk;
+        REQUIRE((int64_t)batch_size * chunks <= 0x7fffffffLL && (int64_t)batch_size * seqlen_q <= 0x7fffffffLL,
+                "batch_size * seqlen_q = %lld rows over %d keys is more than one launch covers",
+                (long long)batch_size * seqlen_q, max_seqlen_k);
+        if (batch_size == 0 || max_seqlen_k == 0) return;
+        MlaIndexParams p{};
+        p.q8 = q8; p.weights = (const float*)weights; p.cache = index_cache; p.logits = (float*)logits;
+        p.block_table = (const int*)block_table; p.context_lens = (const int*)context_lens;
+        p.q_batch = q_strides[0]; p.q_row = q_strides[1]; p.q_head = q_strides[2];
+        p.logits_row = logits_row_stride;
+        p.bt_stride = block_table_stride; p.page = page_block_size; p.num_blocks = num_blocks;
+        p.max_seqlen_k = max_seqlen_k;
+        p.b = batch_size; p.seqlen_q = seqlen_q; p.heads = num_heads;
+        hip_ok(launch_mla_index_logits(p, stream), "MLA index logits launch");
+    } catch (...) {
+        fail(9, "internal error in fmha_mla_index_logits");
+    }
 }
 
 }  // extern "C"

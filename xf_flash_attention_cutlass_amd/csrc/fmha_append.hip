@@ -29,17 +29,11 @@
 #include <cstdint>
 
 #include "fmha_launch.h"
+#include "fmha_row8.h"
 
 namespace xfa {
 
 
-template <typename T>
-__device__ __forceinline__ void load8(const T* p, float (&x)[8]) {
-    typedef __attribute__((ext_vector_type(8))) T T8;
-    const T8 v = *reinterpret_cast<const T8*>(p);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) x[i] = (float)v[i];
-}
 template <typename T>
 __device__ __forceinline__ void store8(T* p, const float (&x)[8]) {
     typedef __attribute__((ext_vector_type(8))) T T8;
@@ -49,21 +43,6 @@ __device__ __forceinline__ void store8(T* p, const float (&x)[8]) {
     *reinterpret_cast<T8*>(p) = v;
 }
 
-// 8 fp32 values x inv -> 8 e4m3fn bytes (v_cvt_pk_fp8_f32: round to nearest even), one store
-__device__ __forceinline__ void store8(uint8_t* p, const float (&x)[8], const float inv) {
-    float f[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const float v = x[i] * inv;
-        f[i] = v < -448.f ? -448.f : (v > 448.f ? 448.f : v);
-    }
-    int lo = 0, hi = 0;
-    lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], lo, false);
-    lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], lo, true);
-    hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], hi, false);
-    hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], hi, true);
-    *reinterpret_cast<u32x2*>(p) = u32x2{(unsigned)lo, (unsigned)hi};
-}
 // (a cache in q's dtype: no scale)
 template <typename T>
 __device__ __forceinline__ void store8(T* p, const float (&x)[8], const float) { store8(p, x); }

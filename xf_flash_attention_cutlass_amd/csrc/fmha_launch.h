@@ -303,6 +303,38 @@ struct MlaAppendParams {
 };
 hipError_t launch_mla_append_fp8(const MlaAppendParams& p, bool fp16, hipStream_t st);
 
+// MLA indexer (fmha_mla_index.hip, fmha_mla_index_kernel.h): the fused index logits over the fp8
+// index-key cache (blocks of page * 132 bytes: page rows of 128 e4m3 features, then page fp32
+// descales) and the append into that cache.  Strides in elements (bytes for q8).
+#ifndef XFA_MLA_INDEX_CHUNK               // (an A/B build may set another: tools/mla_index_ab.py)
+#define XFA_MLA_INDEX_CHUNK 1024
+#endif
+constexpr int kMlaIndexChunk = XFA_MLA_INDEX_CHUNK;   // keys of one workgroup's item: FMHA_MLA_INDEX_CHUNK
+struct MlaIndexParams {
+    const void* q8;               // [b, seqlen_q, heads, 128] e4m3 bytes
+    const float* weights;         // [b * seqlen_q, heads]
+    const void* cache;            // [num_blocks, page * 132] bytes
+    const int* block_table;       // [b, bt_stride]
+    const int* context_lens;      // [b]
+    float* logits;                // [b * seqlen_q, logits_row]
+    int64_t q_batch, q_row, q_head;
+    int64_t logits_row;
+    int bt_stride, page, num_blocks, max_seqlen_k;
+    int b, seqlen_q, heads;
+};
+hipError_t launch_mla_index_logits(const MlaIndexParams& p, hipStream_t st);
+// token t's 128 features, quantised with one scale per row (ue8m0: the scale rounded up to a power
+// of two), into row slot[t] of the index cache; a slot outside [0, slots) writes nothing
+struct MlaIndexAppendParams {
+    const void* k;                // [tokens, 128]
+    void* cache;
+    const int64_t* slot;          // [tokens]
+    int64_t k_row;
+    int64_t slots;                // num_blocks * page
+    int page, tokens, ue8m0;
+};
+hipError_t launch_mla_index_append_fp8(const MlaIndexAppendParams& p, bool fp16, hipStream_t st);
+
 // D = 256 (bucket of 129..256): 4 waves x 32 rows, one wave per SIMD (512 registers:
 // Q fragments and the O accumulator alone are 192), no LDS-DMA pipeline
 inline int fwd_block_m(int d, int waves) { return d > 128 ? 128 : waves * 32; }

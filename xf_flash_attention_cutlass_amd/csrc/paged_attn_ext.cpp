@@ -1222,6 +1222,92 @@ void mha_mla_cache_append_fp8(const at::Tensor& latent, const at::Tensor& k_pe, 
     raise_if_failed("mla_cache_append_fp8");
 }
 
+// ---- the MLA indexer: the index-key cache [num_blocks, page * 132] bytes (uint8 or float8_e4m3fn)
+static void check_index_cache(const at::Tensor& cache, const at::Tensor& like) {
+    TORCH_CHECK(is_byte_cache(cache), "index_cache must be uint8 or float8_e4m3fn");
+    TORCH_CHECK(cache.is_cuda() && cache.device() == like.device(), "index_cache must be on the inputs' device");
+    TORCH_CHECK(cache.dim() == 2 && cache.size(0) >= 1 && cache.size(1) >= 16 * 132 && cache.size(1) % (16 * 132) == 0,
+                "index_cache must be (num_blocks, page_block_size * 132) with page_block_size a multiple of 16");
+    CHECK_CONTIGUOUS(cache);
+    TORCH_CHECK(aligned16(cache), "index_cache must be 16-byte aligned");
+    TORCH_CHECK(cache.size(0) <= 0x7fffffff, "index_cache too large");
+}
+
+// Append tokens to the index-key cache (fmha_mla_index_cache_append_fp8): k [tokens, 128] by its own
+// row stride, slot_mapping int64; scale_fmt 0 (fp32 descale) or 1 (ue8m0).
+void mha_mla_index_cache_append_fp8(const at::Tensor& k, at::Tensor& index_cache, const at::Tensor& slot_mapping,
+                                    const int scale_fmt) {
+    auto dt = k.dtype();
+    TORCH_CHECK(dt == torch::kFloat16 || dt == torch::kBFloat16, "k must be fp16 or bf16");
+    CHECK_DEVICE(k); CHECK_DEVICE(slot_mapping);
+    TORCH_CHECK(slot_mapping.device() == k.device(), "all tensors must be on one device");
+    TORCH_CHECK(k.dim() == 2 && k.size(1) == 128, "k must be (num_tokens, 128)");
+    TORCH_CHECK(k.stride(1) == 1, "k must have contiguous last dimension");
+    TORCH_CHECK(aligned16(k), "k must be 16-byte aligned with a row stride that is a multiple of 16 bytes");
+    check_index_cache(index_cache, k);
+    TORCH_CHECK(slot_mapping.dtype() == torch::kInt64 && slot_mapping.dim() == 1 &&
+                    slot_mapping.size(0) == k.size(0) && slot_mapping.is_contiguous(),
+                "slot_mapping must be a contiguous int64 (num_tokens)");
+    TORCH_CHECK(scale_fmt == 0 || scale_fmt == 1, "scale_fmt must be 0 or 1 (ue8m0)");
+    if (k.size(0) == 0) return;
+    const c10::DeviceGuard device_guard(k.device());
+    fmha_mla_index_cache_append_fp8(k.data_ptr(), k.stride(0), index_cache.data_ptr(), slot_mapping.data_ptr(),
+                                    (int)k.size(0), (int)index_cache.size(0), (int)(index_cache.size(1) / 132),
+                                    scale_fmt, dt == torch::kFloat16, cur_stream());
+    raise_if_failed("mla_index_cache_append_fp8");
+}
+
+// The index logits (fmha_mla_index_logits): q8 [batch, seqlen_q, heads, 128] bytes by its own strides,
+// weights fp32 [batch * seqlen_q, heads].  Returns logits fp32 [batch * seqlen_q, max_seqlen_k]: the
+// caller's `out` (a view of a wider buffer is fine: unit column stride) or a new one.
+at::Tensor mha_mla_index_logits(const at::Tensor& q8, const at::Tensor& weights, const at::Tensor& index_cache,
+                                const at::Tensor& block_table, const at::Tensor& context_lens,
+                                const int64_t max_seqlen_k, const OptTensor& out_) {
+    TORCH_CHECK(is_byte_cache(q8), "q8 must be uint8 or float8_e4m3fn");
+    CHECK_DEVICE(q8);
+    TORCH_CHECK(q8.dim() == 4 && q8.size(3) == 128, "q8 must be (batch_size, seqlen_q, heads, 128)");
+    TORCH_CHECK(q8.size(2) == 32 || q8.size(2) == 64, "the index logits support 32 or 64 heads, got ", q8.size(2));
+    TORCH_CHECK(q8.size(1) >= 1, "q8 must have at least one row");
+    TORCH_CHECK(q8.stride(3) == 1, "q8 must have contiguous last dimension");
+    TORCH_CHECK(aligned16(q8), "q8 must be 16-byte aligned with strides that are multiples of 16 bytes");
+    const int batch = q8.size(0), seqlen_q = q8.size(1), heads = q8.size(2);
+    const int64_t rows = (int64_t)batch * seqlen_q;
+    TORCH_CHECK(weights.dtype() == torch::kFloat32 && weights.is_cuda() && weights.device() == q8.device(),
+                "weights must be fp32 on q8's device");
+    TORCH_CHECK(weights.dim() == 2 && weights.size(0) == rows && weights.size(1) == heads && weights.is_contiguous(),
+                "weights must be a contiguous (batch_size * seqlen_q, heads)");
+    check_index_cache(index_cache, q8);
+    TORCH_CHECK(block_table.dim() == 2, "block_table must be (batch_size, max_num_blocks_per_seq)");
+    check_block_table(block_table, batch);
+    check_batch_int32(context_lens, batch, "context_lens");
+    TORCH_CHECK(block_table.device() == q8.device() && context_lens.device() == q8.device(),
+                "block_table and context_lens must be on q8's device");
+    const int64_t page = index_cache.size(1) / 132;
+    TORCH_CHECK(max_seqlen_k >= 0 && max_seqlen_k <= block_table.size(1) * page && max_seqlen_k <= 0x7fffffff,
+                "max_seqlen_k must lie in [0, max_num_blocks_per_seq * page_block_size]");
+    at::Tensor out;
+    if (out_.has_value()) {
+        out = out_.value();
+        TORCH_CHECK(out.dtype() == torch::kFloat32 && out.is_cuda() && out.device() == q8.device(),
+                    "out must be fp32 on q8's device");
+        TORCH_CHECK(out.dim() == 2 && out.size(0) == rows && out.size(1) == max_seqlen_k,
+                    "out must be (batch_size * seqlen_q, max_seqlen_k)");
+        TORCH_CHECK((out.stride(1) == 1 || out.size(1) <= 1) && (rows <= 1 || out.stride(0) >= max_seqlen_k),
+                    "out must have unit column stride and a row stride of at least max_seqlen_k");
+    } else {
+        out = torch::empty({rows, max_seqlen_k}, q8.options().dtype(torch::kFloat32));
+    }
+    if (batch == 0) return out;
+    const c10::DeviceGuard device_guard(q8.device());
+    const int64_t st[3] = {q8.stride(0), q8.stride(1), q8.stride(2)};
+    fmha_mla_index_logits(q8.data_ptr(), weights.data_ptr(), index_cache.data_ptr(), out.data_ptr(),
+                          block_table.data_ptr(), (int)block_table.stride(0), context_lens.data_ptr(), seqlen_q,
+                          (int)max_seqlen_k, batch, heads, 128, (int)index_cache.size(0), (int)page, st,
+                          rows <= 1 ? max_seqlen_k : out.stride(0), cur_stream());
+    raise_if_failed("mla_index_logits");
+    return out;
+}
+
 namespace {
 
 // ---- `fwd_mla` / `varlen_fwd_mla`: q and k with 192 features a head, v with 128, each by its own
@@ -1469,6 +1555,13 @@ PYBIND11_MODULE(paged_attn, m) {
     m.def("_mla_decode_sparse_fp8", &mha_mla_decode_sparse<true>, "MLA decode over index-selected tokens of an fp8 paged latent KV cache",
           py::arg("q"), py::arg("kv_cache"), py::arg("indices"), py::arg("head_dim_v") = 512,
           py::arg("softmax_scale") = 0.041666666666666664f, py::arg("num_splits") = 0, py::arg("out") = py::none());
+    // ... and the MLA indexer: the index-key cache append and the fused index logits
+    m.def("_mla_index_cache_append_fp8", &mha_mla_index_cache_append_fp8, "Append tokens to an fp8 paged index-key cache",
+          py::arg("k"), py::arg("index_cache"), py::arg("slot_mapping"), py::arg("scale_fmt") = 0);
+    m.def("_mla_index_logits", &mha_mla_index_logits, "Fused MLA index logits over an fp8 paged index-key cache",
+          py::arg("q8"), py::arg("weights"), py::arg("index_cache"), py::arg("block_table"),
+          py::arg("context_lens"), py::arg("max_seqlen_k"), py::arg("out") = py::none());
+    m.attr("_mla_index_chunk") = FMHA_MLA_INDEX_CHUNK;      // keys of one workgroup's item
     // ... and the MLA prefill (head size 192 for q / k, 128 for v), dense and packed
     m.def("_fwd_mla", &mha_fwd_mla, "MLA prefill forward (d_qk 192, d_v 128)", py::arg("q"), py::arg("k"),
           py::arg("v"), py::arg("out") = py::none(), py::arg("softmax_scale") = 0.07216878364870322f,
@@ -1496,6 +1589,8 @@ PYBIND11_MODULE(paged_attn, m) {
         if (name == "mla_cache_append_fp8") return self.attr("_mla_cache_append_fp8");
         if (name == "mla_decode_sparse") return self.attr("_mla_decode_sparse");
         if (name == "mla_decode_sparse_fp8") return self.attr("_mla_decode_sparse_fp8");
+        if (name == "mla_index_cache_append_fp8") return self.attr("_mla_index_cache_append_fp8");
+        if (name == "mla_index_logits") return self.attr("_mla_index_logits");
         if (name == "fwd_mla") return self.attr("_fwd_mla");
         if (name == "varlen_fwd_mla") return self.attr("_varlen_fwd_mla");
         if (name == "bwd_mla") return self.attr("_bwd_mla");

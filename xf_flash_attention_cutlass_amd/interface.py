@@ -335,6 +335,71 @@ def mla_cache_append_fp8(latent, k_pe, kv_cache, slot_mapping):
         paged_attn.mla_cache_append_fp8(latent.detach(), k_pe.detach(), kv_cache, slot_mapping)
 
 
+def mla_index_cache_block_bytes(page_block_size):
+    """Bytes of one block of the MLA index-key cache: `page_block_size` rows of 128 e4m3fn features,
+    then `page_block_size` fp32 descales (vLLM's and DeepGEMM's layout)."""
+    return 132 * int(page_block_size)
+
+
+_INDEX_SCALE_FMT = {None: 0, "ue8m0": 1}
+
+
+def mla_index_cache_append_fp8(k, index_cache, slot_mapping, scale_fmt=None):
+    """Append index keys to the fp8 paged index-key cache of DeepSeek-V3.2's lightning indexer
+    (vLLM's `indexer_k_quant_and_cache`), one HIP launch, no host sync.
+
+    k: [tokens, 128] bf16 or fp16 (a view is fine: last dimension contiguous, 16-byte aligned rows).
+    index_cache: uint8 or float8_e4m3fn [num_blocks, mla_index_cache_block_bytes(page)], page a
+    multiple of 16, written in place.  slot_mapping: int64 [tokens], slot = block * page + row - the
+    latent cache's slot mapping; a negative or out-of-range slot is skipped.  One scale per row:
+    descale = amax / 448 (1.0 for an all-zero row), bytes = e4m3fn(clamp(x * (1 / descale)));
+    scale_fmt="ue8m0" (what V3.2 ships) first rounds the descale up to a power of two."""
+    if scale_fmt not in _INDEX_SCALE_FMT:
+        raise ValueError(f"scale_fmt must be None or 'ue8m0' (got {scale_fmt!r})")
+    with torch.no_grad():
+        paged_attn.mla_index_cache_append_fp8(k.detach(), index_cache, slot_mapping, _INDEX_SCALE_FMT[scale_fmt])
+
+
+def mla_index_logits(q8, weights, index_cache, block_table, context_lens, max_seqlen_k, out=None):
+    """The lightning indexer's logits over the paged fp8 index-key cache (DeepGEMM's
+    `fp8_paged_mqa_logits`), one HIP launch (`paged_attn.mla_index_logits`), no scratch, no copies:
+
+        logits[b * seqlen_q + i, s] = descale[b, s] * sum_h weights[., h] * relu(q8[b, i, h] . k8[b, s])
+
+    for the keys s position i may see (bottom-right causal within context_lens[b]) and -inf for the
+    others up to max_seqlen_k, so `torch.topk` over a row is valid as it stands.
+
+    q8: [b, seqlen_q, heads, 128] float8_e4m3fn or uint8, heads 32 or 64 (a view is fine: last
+    dimension contiguous, 16-byte aligned rows); weights: fp32 [b * seqlen_q, heads] with q's own
+    quantisation scale, the softmax scale and heads ** -0.5 folded in (any sign); block_table: int32
+    [b, max_blocks_per_seq]; context_lens: int32 [b]; out: fp32 [b * seqlen_q, max_seqlen_k] with
+    unit column stride (a column slice of a wider buffer is fine; the rest of it is not touched).
+    Returns the logits.  Not differentiable."""
+    with torch.no_grad():
+        return paged_attn.mla_index_logits(q8.detach(), weights.detach(), index_cache, block_table,
+                                           context_lens, int(max_seqlen_k), out)
+
+
+def mla_index_topk_slots(logits, block_table, context_lens, topk, seqlen_q=1, page_block_size=64):
+    """The indexer's choice as `flash_mla_with_kvcache(indices=...)` takes it: int32 [b, seqlen_q,
+    topk] of physical slots, from `mla_index_logits`' result.  A few lines of torch glue, not a
+    kernel (the selection kernel is future work): `torch.topk` over each row (over all of it when
+    the row is shorter than topk, the rest padded), an entry whose logit is -inf becomes -1, the
+    others go through the block table, slot = block_table[b, s // page] * page + s % page with
+    page = page_block_size (the model's is 64).  context_lens is not read - the logits carry the
+    visibility - and is taken so that a selection kernel can replace this without a new signature."""
+    rows, width = logits.shape
+    b = rows // int(seqlen_q)
+    page = int(page_block_size)
+    val, pos = torch.topk(logits, min(int(topk), width), dim=1)
+    table = block_table.long().repeat_interleave(int(seqlen_q), dim=0)
+    slots = torch.gather(table, 1, pos // page) * page + pos % page
+    slots = torch.where(val == float("-inf"), torch.full_like(slots, -1), slots).int()
+    if slots.shape[1] < int(topk):
+        slots = torch.nn.functional.pad(slots, (0, int(topk) - slots.shape[1]), value=-1)
+    return slots.view(b, int(seqlen_q), int(topk))
+
+
 _GRANULARITY = {"tensor": 0, "head": 1}
 
 
