@@ -127,7 +127,7 @@ void fmha_set_rng_state(uint64_t seed, uint64_t offset);
 void fmha_set_rng_state_device(const int64_t* seed_ptr, const int64_t* offset_ptr,
                                uint64_t offset_add, int64_t* rng_out);
 
-/* Library version / build identification, e.g. "xf-fmha-gfx950 2.14".  2.0 (round 3) changed
+/* Library version / build identification, e.g. "xf-fmha-gfx950 2.15".  2.0 (round 3) changed
  * argument lists of existing symbols; 2.1 exports those under _v2 names (see INTEGRATION.md
  * "ABI history"). */
 const char* fmha_version(void);
@@ -661,6 +661,42 @@ void fmha_mla_index_logits(const void* q8, const void* weights, const void* inde
                            int32_t head_size /* 128 */, int32_t num_blocks, int32_t page_block_size,
                            const int64_t* q_strides /* batch,row,head */, int64_t logits_row_stride,
                            hipStream_t stream);
+
+/* --------------------------- MLA indexer: top-k selection, logits to slot indices (2.15) */
+
+/* fmha_mla_index_topk: the topk largest visible logits of every row of fmha_mla_index_logits'
+ * result, as the `indices` of fmha_mla_decode_sparse: one launch of fmha_mla_index_topk_kernel
+ * (fmha_last_kernel() names it and its grid, batch * seqlen_q workgroups), no scratch, no host
+ * sync (capturable in a graph), no atomics on global memory: bitwise reproducible.
+ *   logits  fp32 [batch * seqlen_q, logits_row_stride], logits_row_stride >= max_seqlen_k
+ *   block_table int32 [batch, block_table_stride], context_lens int32 [batch]
+ *   indices int32 [batch * seqlen_q, indices_row_stride], indices_row_stride >= topk
+ * For row r = b * seqlen_q + i, n and vis are those of fmha_mla_index_logits: n = min(context_lens[b],
+ * max_seqlen_k), vis = clamp(n - seqlen_q + i + 1, 0, n).  Only columns [0, vis) are read; whatever
+ * lies in [vis, logits_row_stride) is never loaded, and a short row costs what it holds.
+ * ORDER: the order on floats; -0.0 == +0.0; +inf is the largest value; -inf and NaN are
+ * unselectable (never chosen, whatever topk is); subnormals are ordinary values (no flush).
+ * SELECTED SET: with m selectable columns in [0, vis), c = min(m, topk) and T the c-th largest
+ * selectable value: every column > T, and of the columns == T the lowest positions until there are
+ * c.  The set is a function of the inputs alone.
+ * OUTPUT: indices[r, 0:c] = the selected columns in ASCENDING KEY POSITION, each position s as the
+ * physical slot block_table[b, s / page] * page + s % page (64-bit arithmetic); where the table
+ * entry is outside [0, num_blocks) or the slot does not fit an int32 the entry is -1, in place
+ * (fmha_mla_decode_sparse skips -1 anywhere); indices[r, c:topk] = -1; columns >= topk of
+ * `indices` are never touched.  Rows of at most FMHA_MLA_INDEX_TOPK_STAGE visible keys are kept in
+ * LDS between the radix passes, longer ones are read again from global memory; there is no upper
+ * limit on topk or on the row length.
+ * batch_size == 0 validates, launches nothing and succeeds; max_seqlen_k == 0 fills -1.  Refused
+ * with an error, outputs untouched: a NULL pointer, topk < 1, seqlen_q < 1, a negative batch, a
+ * page size that is no positive multiple of 16, num_blocks < 1, max_seqlen_k outside [0,
+ * block_table_stride * page_block_size], logits_row_stride < max_seqlen_k, indices_row_stride <
+ * topk, a pointer not 4-byte aligned, batch_size * seqlen_q beyond one grid. */
+#define FMHA_MLA_INDEX_TOPK_STAGE 32768
+void fmha_mla_index_topk(const void* logits, int64_t logits_row_stride,
+                         const void* block_table, int32_t block_table_stride,
+                         const void* context_lens, void* indices, int64_t indices_row_stride,
+                         int32_t topk, int32_t seqlen_q, int32_t max_seqlen_k, int32_t batch_size,
+                         int32_t num_blocks, int32_t page_block_size, hipStream_t stream);
 
 /* ------------------------- MLA prefill: head size 192 for Q K^T, 128 for V (2.12) */
 

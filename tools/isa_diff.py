@@ -48,6 +48,8 @@ def units(tree):
                 for dt in ("bf16", "f16")]
     if os.path.exists(os.path.join(b.CSRC, "fmha_mla_index.hip")):    # (trees from 2.14 on)
         tus += [("fmha_mla_index", "fmha_mla_index.hip", ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"])]
+    if os.path.exists(os.path.join(b.CSRC, "fmha_mla_index_topk.hip")):   # (trees from 2.15 on)
+        tus += [("fmha_mla_index_topk", "fmha_mla_index_topk.hip", ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"])]
     tus += [(n + "+variants", src, d + ["-DXFA_VARIANTS=1"]) for n, src, d in tus if n + ".o" in b.VARIANT_TUS]
     return b, tus
 

@@ -133,6 +133,9 @@ def build_lib(jobs: int = 8, force: bool = False, verbose: bool = False, variant
     # off: the epilogue's fma chain is scalar by design
     todo.append((os.path.join(CSRC, "fmha_mla_index.hip"), os.path.join(OBJ, "fmha_mla_index.o"),
                  ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]))
+    # ... and its top-k selection, a unit of its own (integer work; the same flag as above)
+    todo.append((os.path.join(CSRC, "fmha_mla_index_topk.hip"), os.path.join(OBJ, "fmha_mla_index_topk.o"),
+                 ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]))
     todo.append((os.path.join(CSRC, "fmha_api.cpp"), os.path.join(OBJ, "fmha_api.o"), []))
     if variants:
         todo = [(src, os.path.join(obj_dir, os.path.basename(out)), defs + ["-DXFA_VARIANTS=1"])

@@ -525,7 +525,7 @@ const char* fmha_last_error(void) { return g_err.c_str(); }
 int fmha_last_status(void) { return g_status; }
 int fmha_last_num_splits(void) { return g_last_splits; }
 const char* fmha_last_kernel(void) { return g_last_kernel; }
-const char* fmha_version(void) { return XFA_VARIANTS ? "xf-fmha-gfx950 2.14 (variants)" : "xf-fmha-gfx950 2.14"; }
+const char* fmha_version(void) { return XFA_VARIANTS ? "xf-fmha-gfx950 2.15 (variants)" : "xf-fmha-gfx950 2.15"; }
 
 void fmha_set_rng_state(uint64_t seed, uint64_t offset) {
     g_seed = seed;
@@ -1765,6 +1765,50 @@ void fmha_mla_index_logits(const void* q8, const void* weights, const void* inde
         hip_ok(launch_mla_index_logits(p, stream), "MLA index logits launch");
     } catch (...) {
         fail(9, "internal error in fmha_mla_index_logits");
+    }
+}
+
+// ---- MLA indexer: the top-k selection, logits to physical slots in ascending key position
+static_assert(FMHA_MLA_INDEX_TOPK_STAGE == kMlaTopkStage, "the header's staging threshold is the kernel's");
+
+void fmha_mla_index_topk(const void* logits, int64_t logits_row_stride, const void* block_table,
+                         int32_t block_table_stride, const void* context_lens, void* indices,
+                         int64_t indices_row_stride, int32_t topk, int32_t seqlen_q, int32_t max_seqlen_k,
+                         int32_t batch_size, int32_t num_blocks, int32_t page_block_size, hipStream_t stream) {
+    try {
+        begin_fwd();
+        REQUIRE(logits && indices, "logits and indices must be non-null device pointers");
+        REQUIRE(block_table && context_lens, "block_table and context_lens must be non-null device pointers");
+        REQUIRE(topk >= 1, "topk must be at least 1 (got %d)", topk);
+        REQUIRE(seqlen_q >= 1, "seqlen_q must be at least 1 (got %d)", seqlen_q);
+        REQUIRE(batch_size >= 0, "batch size must be non-negative (got %d)", batch_size);
+        REQUIRE(page_block_size > 0 && page_block_size % 16 == 0,
+                "page_block_size must be a positive multiple of 16 (got %d)", page_block_size);
+        REQUIRE(num_blocks >= 1, "num_blocks must be at least 1 (got %d)", num_blocks);
+        REQUIRE(block_table_stride >= 0 && max_seqlen_k >= 0 &&
+                    (int64_t)max_seqlen_k <= (int64_t)block_table_stride * page_block_size,
+                "max_seqlen_k must lie in [0, block_table_stride * page_block_size] (got %d, table %d x page %d)",
+                max_seqlen_k, block_table_stride, page_block_size);
+        REQUIRE(logits_row_stride >= max_seqlen_k, "logits_row_stride must be at least max_seqlen_k (got %lld, %d)",
+                (long long)logits_row_stride, max_seqlen_k);
+        REQUIRE(indices_row_stride >= topk, "indices_row_stride must be at least topk (got %lld, %d)",
+                (long long)indices_row_stride, topk);
+        REQUIRE(!((((uintptr_t)logits) | ((uintptr_t)indices) | ((uintptr_t)block_table) | ((uintptr_t)context_lens)) & 3),
+                "logits, indices, block_table and context_lens must be 4-byte aligned device pointers");
+        REQUIRE((int64_t)batch_size * seqlen_q <= 0x7fffffffLL,
+                "batch_size * seqlen_q = %lld rows is more than one launch covers", (long long)batch_size * seqlen_q);
+        if (batch_size == 0) return;
+        MlaIndexTopkParams p{};
+        p.logits = (const float*)logits; p.block_table = (const int*)block_table;
+        p.context_lens = (const int*)context_lens; p.indices = (int*)indices;
+        p.logits_row = logits_row_stride; p.indices_row = indices_row_stride;
+        p.bt_stride = block_table_stride; p.page = page_block_size; p.num_blocks = num_blocks;
+        p.max_seqlen_k = max_seqlen_k;
+        p.rows = batch_size * seqlen_q; p.seqlen_q = seqlen_q; p.topk = topk;
+        p.device = current_device();
+        hip_ok(launch_mla_index_topk(p, stream), "MLA index top-k launch");
+    } catch (...) {
+        fail(9, "internal error in fmha_mla_index_topk");
     }
 }
 

@@ -335,6 +335,21 @@ struct MlaIndexAppendParams {
 };
 hipError_t launch_mla_index_append_fp8(const MlaIndexAppendParams& p, bool fp16, hipStream_t st);
 
+// MLA indexer, the selection (fmha_mla_index_topk.hip, fmha_mla_index_topk_kernel.h): the top-k
+// keys of every logits row as physical slots in ascending key position.  One workgroup per row.
+constexpr int kMlaTopkStage = 32768;      // rows of at most this many visible keys are kept in LDS
+struct MlaIndexTopkParams {
+    const float* logits;          // [rows, logits_row]
+    const int* block_table;       // [b, bt_stride]
+    const int* context_lens;      // [b]
+    int* indices;                 // [rows, indices_row]
+    int64_t logits_row, indices_row;
+    int bt_stride, page, num_blocks, max_seqlen_k;
+    int rows, seqlen_q, topk;
+    int device;
+};
+hipError_t launch_mla_index_topk(const MlaIndexTopkParams& p, hipStream_t st);
+
 // D = 256 (bucket of 129..256): 4 waves x 32 rows, one wave per SIMD (512 registers:
 // Q fragments and the O accumulator alone are 192), no LDS-DMA pipeline
 inline int fwd_block_m(int d, int waves) { return d > 128 ? 128 : waves * 32; }

@@ -1308,6 +1308,58 @@ at::Tensor mha_mla_index_logits(const at::Tensor& q8, const at::Tensor& weights,
     return out;
 }
 
+// The indexer's selection (fmha_mla_index_topk): logits fp32 [batch * seqlen_q, >= max_seqlen_k] by
+// its own row stride.  Returns indices int32 [batch, seqlen_q, topk]: the caller's `out` (a view
+// with a longer row is fine: unit column stride, rows row_stride apart) or a new one.  num_blocks
+// < 0: unknown, only the int32 range bounds a table entry.
+at::Tensor mha_mla_index_topk(const at::Tensor& logits, const at::Tensor& block_table, const at::Tensor& context_lens,
+                              const int64_t topk, const int64_t seqlen_q, const int64_t page_block_size,
+                              const int64_t max_seqlen_k, const int64_t num_blocks, const OptTensor& out_) {
+    CHECK_DEVICE(logits);
+    TORCH_CHECK(logits.dtype() == torch::kFloat32, "logits must be fp32");
+    TORCH_CHECK(logits.dim() == 2, "logits must be (batch_size * seqlen_q, keys)");
+    TORCH_CHECK(logits.stride(1) == 1 || logits.size(1) <= 1, "logits must have contiguous last dimension");
+    TORCH_CHECK(topk >= 1 && topk <= 0x7fffffff, "topk must be at least 1");
+    TORCH_CHECK(seqlen_q >= 1 && logits.size(0) % seqlen_q == 0, "logits' rows must be batch_size * seqlen_q");
+    TORCH_CHECK(page_block_size >= 16 && page_block_size % 16 == 0 && page_block_size <= 0x7fffffff,
+                "page_block_size must be a positive multiple of 16");
+    const int64_t rows = logits.size(0);
+    const int batch = (int)(rows / seqlen_q);
+    TORCH_CHECK(rows <= 0x7fffffff, "too many rows");
+    TORCH_CHECK(block_table.dim() == 2, "block_table must be (batch_size, max_num_blocks_per_seq)");
+    check_block_table(block_table, batch);
+    check_batch_int32(context_lens, batch, "context_lens");
+    TORCH_CHECK(block_table.device() == logits.device() && context_lens.device() == logits.device(),
+                "block_table and context_lens must be on logits' device");
+    TORCH_CHECK(max_seqlen_k >= 0 && max_seqlen_k <= logits.size(1) && max_seqlen_k <= 0x7fffffff &&
+                    max_seqlen_k <= block_table.size(1) * page_block_size,
+                "max_seqlen_k must lie in [0, min(logits' columns, max_num_blocks_per_seq * page_block_size)]");
+    TORCH_CHECK(num_blocks != 0 && num_blocks <= 0x7fffffff, "num_blocks must be at least 1 (negative: unknown)");
+    at::Tensor out;
+    if (out_.has_value()) {
+        out = out_.value();
+        TORCH_CHECK(out.dtype() == torch::kInt32 && out.is_cuda() && out.device() == logits.device(),
+                    "out must be int32 on logits' device");
+        TORCH_CHECK(out.dim() == 3 && out.size(0) == batch && out.size(1) == seqlen_q && out.size(2) == topk,
+                    "out must be (batch_size, seqlen_q, topk)");
+        TORCH_CHECK(out.stride(2) == 1 || topk <= 1, "out must have contiguous last dimension");
+        TORCH_CHECK((seqlen_q <= 1 || out.stride(1) >= topk) && (batch <= 1 || out.stride(0) == seqlen_q * out.stride(1) || seqlen_q == 1 && out.stride(0) >= topk),
+                    "out's rows must lie one row stride (>= topk) apart");
+    } else {
+        out = torch::empty({batch, seqlen_q, topk}, logits.options().dtype(torch::kInt32));
+    }
+    if (batch == 0) return out;
+    const c10::DeviceGuard device_guard(logits.device());
+    const int64_t orow = seqlen_q > 1 ? out.stride(1) : batch > 1 ? out.stride(0) : topk;
+    fmha_mla_index_topk(logits.data_ptr(), rows <= 1 ? logits.size(1) : logits.stride(0), block_table.data_ptr(),
+                        (int)block_table.stride(0), context_lens.data_ptr(), out.data_ptr(), orow, (int)topk,
+                        (int)seqlen_q, (int)max_seqlen_k, batch,
+                        num_blocks < 0 ? (int)(0x7fffffff / page_block_size) : (int)num_blocks, (int)page_block_size,
+                        cur_stream());
+    raise_if_failed("mla_index_topk");
+    return out;
+}
+
 namespace {
 
 // ---- `fwd_mla` / `varlen_fwd_mla`: q and k with 192 features a head, v with 128, each by its own
@@ -1562,6 +1614,11 @@ PYBIND11_MODULE(paged_attn, m) {
           py::arg("q8"), py::arg("weights"), py::arg("index_cache"), py::arg("block_table"),
           py::arg("context_lens"), py::arg("max_seqlen_k"), py::arg("out") = py::none());
     m.attr("_mla_index_chunk") = FMHA_MLA_INDEX_CHUNK;      // keys of one workgroup's item
+    m.def("_mla_index_topk", &mha_mla_index_topk, "Top-k selection over the MLA index logits, as physical slots",
+          py::arg("logits"), py::arg("block_table"), py::arg("context_lens"), py::arg("topk"), py::arg("seqlen_q") = 1,
+          py::arg("page_block_size") = 64, py::arg("max_seqlen_k") = 0, py::arg("num_blocks") = -1,
+          py::arg("out") = py::none());
+    m.attr("_mla_index_topk_stage") = FMHA_MLA_INDEX_TOPK_STAGE;   // rows up to this many visible keys stay in LDS
     // ... and the MLA prefill (head size 192 for q / k, 128 for v), dense and packed
     m.def("_fwd_mla", &mha_fwd_mla, "MLA prefill forward (d_qk 192, d_v 128)", py::arg("q"), py::arg("k"),
           py::arg("v"), py::arg("out") = py::none(), py::arg("softmax_scale") = 0.07216878364870322f,
@@ -1591,6 +1648,7 @@ PYBIND11_MODULE(paged_attn, m) {
         if (name == "mla_decode_sparse_fp8") return self.attr("_mla_decode_sparse_fp8");
         if (name == "mla_index_cache_append_fp8") return self.attr("_mla_index_cache_append_fp8");
         if (name == "mla_index_logits") return self.attr("_mla_index_logits");
+        if (name == "mla_index_topk") return self.attr("_mla_index_topk");
         if (name == "fwd_mla") return self.attr("_fwd_mla");
         if (name == "varlen_fwd_mla") return self.attr("_varlen_fwd_mla");
         if (name == "bwd_mla") return self.attr("_bwd_mla");

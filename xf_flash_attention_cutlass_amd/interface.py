@@ -383,7 +383,8 @@ def mla_index_logits(q8, weights, index_cache, block_table, context_lens, max_se
 def mla_index_topk_slots(logits, block_table, context_lens, topk, seqlen_q=1, page_block_size=64):
     """The indexer's choice as `flash_mla_with_kvcache(indices=...)` takes it: int32 [b, seqlen_q,
     topk] of physical slots, from `mla_index_logits`' result.  A few lines of torch glue, not a
-    kernel (the selection kernel is future work): `torch.topk` over each row (over all of it when
+    kernel (the selection kernel is `mla_index_topk`, which returns the same set in ascending key
+    position; this one stays as the eager baseline): `torch.topk` over each row (over all of it when
     the row is shorter than topk, the rest padded), an entry whose logit is -inf becomes -1, the
     others go through the block table, slot = block_table[b, s // page] * page + s % page with
     page = page_block_size (the model's is 64).  context_lens is not read - the logits carry the
@@ -398,6 +399,33 @@ def mla_index_topk_slots(logits, block_table, context_lens, topk, seqlen_q=1, pa
     if slots.shape[1] < int(topk):
         slots = torch.nn.functional.pad(slots, (0, int(topk) - slots.shape[1]), value=-1)
     return slots.view(b, int(seqlen_q), int(topk))
+
+
+def mla_index_topk(logits, block_table, context_lens, topk, seqlen_q=1, page_block_size=64, max_seqlen_k=None,
+                   out=None, num_blocks=None):
+    """The indexer's choice as `flash_mla_with_kvcache(indices=...)` takes it, in one HIP launch
+    (`paged_attn.mla_index_topk`: an exact radix select, no scratch, no host sync, graph-capturable,
+    bitwise reproducible): int32 [b, seqlen_q, topk] of physical slots from `mla_index_logits`' result.
+
+    Row b * seqlen_q + i selects among the columns position i may see (bottom-right causal within
+    min(context_lens[b], max_seqlen_k); nothing behind them is read, so they need not hold -inf).
+    The order is the order on floats with -0.0 == +0.0 and +inf the largest; -inf and NaN are never
+    selected.  Of equal values at the threshold the lowest key positions win.  The selected
+    positions come in ASCENDING key position (not by descending logit, as `mla_index_topk_slots`
+    gives them), each as block_table[b, s // page] * page + s % page, then -1 up to topk; a table
+    entry outside [0, num_blocks) gives -1 in place.
+
+    logits: fp32 [b * seqlen_q, keys], last dimension contiguous (a view of a wider buffer is fine);
+    block_table: int32 [b, max_blocks_per_seq]; context_lens: int32 [b]; max_seqlen_k defaults to
+    logits.shape[1]; num_blocks: blocks of the cache, or None for "unknown" - then only the int32
+    range of a slot bounds a table entry (INT32_MAX // page_block_size is passed down); out: int32
+    [b, seqlen_q, topk], rows may lie further apart than topk (the rest of them is not touched).
+    Returns the indices.  Not differentiable."""
+    with torch.no_grad():
+        return paged_attn.mla_index_topk(logits.detach(), block_table, context_lens, int(topk), int(seqlen_q),
+                                         int(page_block_size),
+                                         int(logits.shape[1] if max_seqlen_k is None else max_seqlen_k),
+                                         -1 if num_blocks is None else int(num_blocks), out)
 
 
 _GRANULARITY = {"tensor": 0, "head": 1}
