@@ -127,7 +127,7 @@ void fmha_set_rng_state(uint64_t seed, uint64_t offset);
 void fmha_set_rng_state_device(const int64_t* seed_ptr, const int64_t* offset_ptr,
                                uint64_t offset_add, int64_t* rng_out);
 
-/* Library version / build identification, e.g. "xf-fmha-gfx950 2.15".  2.0 (round 3) changed
+/* Library version / build identification, e.g. "xf-fmha-gfx950 2.16".  2.0 (round 3) changed
  * argument lists of existing symbols; 2.1 exports those under _v2 names (see INTEGRATION.md
  * "ABI history"). */
 const char* fmha_version(void);
@@ -697,6 +697,43 @@ void fmha_mla_index_topk(const void* logits, int64_t logits_row_stride,
                          const void* context_lens, void* indices, int64_t indices_row_stride,
                          int32_t topk, int32_t seqlen_q, int32_t max_seqlen_k, int32_t batch_size,
                          int32_t num_blocks, int32_t page_block_size, hipStream_t stream);
+
+/* --------------------------- MLA indexer: logits for ragged prefill rows (2.16) */
+
+/* fmha_mla_index_logits_ragged: the prefill half of the indexer (DeepGEMM's fp8_mqa_logits): every
+ * new token's row against its own key range [ks, ke) of a packed, NON-PAGED fp8 key array - one
+ * causal sequence, several packed sequences, or new rows over cached keys.  One launch of
+ * fmha_mla_index_ragged_kernel<heads> (fmha_last_kernel() names it), no scratch, every logit has one
+ * writer, no host sync (capturable in a graph).
+ *   q8      [M, heads, 128] e4m3fn bytes by q_strides = {row, head} in BYTES, last dimension
+ *           contiguous, every row 16-byte aligned; heads 32 or 64
+ *   weights fp32 [M, heads], contiguous: q's own quantisation scale, the softmax scale and
+ *           heads^-1/2 folded in by the caller, as for fmha_mla_index_logits; any sign
+ *   k8      [N, 128] e4m3fn bytes by k_row_stride in BYTES (a multiple of 16, at least 128)
+ *   k_scale fp32 [N];  ks, ke int32 [M]
+ *   logits  fp32 [M, logits_row_stride], logits_row_stride >= N
+ * (A one-block index-key cache with page_block_size = N rounded up to 16, appended to with
+ * slot_mapping = 0 .. N - 1, is exactly k8 followed by k_scale: no other quantiser is needed.)
+ * For row r, lo = clamp(ks[r], 0, N) and hi = clamp(ke[r], 0, N):
+ *   lo <= s < hi:        logits[r, s] = k_scale[s] * sum_h weights[r, h] *
+ *                                       max(0, sum_d float(q8[r, h, d]) * float(k8[s, d]))
+ *   every other s < N:   logits[r, s] = -inf (hi <= lo too; torch.topk over the row is valid as it is)
+ * and columns >= N are never touched.  A key outside a row's range never reaches its result: the
+ * mask is a select, so NaN bytes or NaN scales there are harmless.  The grid is ceil(M /
+ * FMHA_MLA_INDEX_RAGGED_ROWS) x ceil(N / FMHA_MLA_INDEX_RAGGED_CHUNK) workgroups; a workgroup reads
+ * only the keys of the union of its rows' ranges.
+ * M == 0 or N == 0 validates, launches nothing and succeeds.  Refused with an error, outputs
+ * untouched: a NULL pointer, heads other than 32 and 64, head_size != 128, a negative count, strides
+ * that are negative or no multiple of 16 (a key row stride under 128), logits_row_stride < N, q8 /
+ * k8 not 16-byte aligned or another pointer not 4-byte aligned, a launch larger than one grid. */
+#define FMHA_MLA_INDEX_RAGGED_CHUNK 1024
+#define FMHA_MLA_INDEX_RAGGED_ROWS 16
+void fmha_mla_index_logits_ragged(const void* q8, const void* weights, const void* k8, const void* k_scale,
+                                  const void* ks, const void* ke, void* logits,
+                                  int32_t num_rows /* M */, int32_t num_keys /* N */, int32_t num_heads,
+                                  int32_t head_size /* 128 */, const int64_t* q_strides /* row,head; bytes */,
+                                  int64_t k_row_stride /* bytes */, int64_t logits_row_stride,
+                                  hipStream_t stream);
 
 /* ------------------------- MLA prefill: head size 192 for Q K^T, 128 for V (2.12) */
 

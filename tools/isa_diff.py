@@ -50,6 +50,9 @@ def units(tree):
         tus += [("fmha_mla_index", "fmha_mla_index.hip", ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"])]
     if os.path.exists(os.path.join(b.CSRC, "fmha_mla_index_topk.hip")):   # (trees from 2.15 on)
         tus += [("fmha_mla_index_topk", "fmha_mla_index_topk.hip", ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"])]
+    if os.path.exists(os.path.join(b.CSRC, "fmha_mla_index_ragged.hip")):   # (trees from 2.16 on)
+        tus += [("fmha_mla_index_ragged", "fmha_mla_index_ragged.hip",
+                 ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops", "-mllvm", "-amdgpu-mfma-vgpr-form"])]
     tus += [(n + "+variants", src, d + ["-DXFA_VARIANTS=1"]) for n, src, d in tus if n + ".o" in b.VARIANT_TUS]
     return b, tus
 

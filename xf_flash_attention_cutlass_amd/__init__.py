@@ -51,6 +51,7 @@ from .interface import (  # noqa: E402
     mla_index_cache_append_fp8,
     mla_index_cache_block_bytes,
     mla_index_logits,
+    mla_index_logits_ragged,
     mla_index_topk,
     mla_index_topk_slots,
     mla_fp8_cache_row_bytes,
@@ -74,6 +75,7 @@ __all__ = [
     "mla_index_cache_append_fp8",
     "mla_index_cache_block_bytes",
     "mla_index_logits",
+    "mla_index_logits_ragged",
     "mla_index_topk",
     "mla_index_topk_slots",
     "mla_fp8_cache_row_bytes",

@@ -136,6 +136,11 @@ def build_lib(jobs: int = 8, force: bool = False, verbose: bool = False, variant
     # ... and its top-k selection, a unit of its own (integer work; the same flag as above)
     todo.append((os.path.join(CSRC, "fmha_mla_index_topk.hip"), os.path.join(OBJ, "fmha_mla_index_topk.o"),
                  ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]))
+    # ... and its prefill logits over per-row key ranges, likewise; VGPR-form MFMAs keep the
+    # accumulators where the relu / fma epilogue reads them (the 4-row instance
+    # otherwise pays one v_accvgpr_read per accumulator element)
+    todo.append((os.path.join(CSRC, "fmha_mla_index_ragged.hip"), os.path.join(OBJ, "fmha_mla_index_ragged.o"),
+                 ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops", "-mllvm", "-amdgpu-mfma-vgpr-form"]))
     todo.append((os.path.join(CSRC, "fmha_api.cpp"), os.path.join(OBJ, "fmha_api.o"), []))
     if variants:
         todo = [(src, os.path.join(obj_dir, os.path.basename(out)), defs + ["-DXFA_VARIANTS=1"])

@@ -77,6 +77,8 @@ _SIGS = {
     "fmha_mla_index_cache_append_fp8": [vp, C.c_int64, vp, vp, i32, i32, i32, i32, b_, vp],
     "fmha_mla_index_logits": [vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32,
                               C.POINTER(C.c_int64), C.c_int64, vp],
+    "fmha_mla_index_logits_ragged": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, C.POINTER(C.c_int64),
+                                     C.c_int64, C.c_int64, vp],
     "fmha_mla_index_topk": [vp, C.c_int64, vp, i32, vp, vp, C.c_int64, i32, i32, i32, i32, i32, i32, vp],
     "fmha_fwd_mla": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, C.POINTER(C.c_int64), f32,
                      C.c_int, C.c_int, b_, vp],

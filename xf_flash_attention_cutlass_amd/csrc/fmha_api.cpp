@@ -525,7 +525,7 @@ const char* fmha_last_error(void) { return g_err.c_str(); }
 int fmha_last_status(void) { return g_status; }
 int fmha_last_num_splits(void) { return g_last_splits; }
 const char* fmha_last_kernel(void) { return g_last_kernel; }
-const char* fmha_version(void) { return XFA_VARIANTS ? "xf-fmha-gfx950 2.15 (variants)" : "xf-fmha-gfx950 2.15"; }
+const char* fmha_version(void) { return XFA_VARIANTS ? "xf-fmha-gfx950 2.16 (variants)" : "xf-fmha-gfx950 2.16"; }
 
 void fmha_set_rng_state(uint64_t seed, uint64_t offset) {
     g_seed = seed;
@@ -1809,6 +1809,55 @@ void fmha_mla_index_topk(const void* logits, int64_t logits_row_stride, const vo
         hip_ok(launch_mla_index_topk(p, stream), "MLA index top-k launch");
     } catch (...) {
         fail(9, "internal error in fmha_mla_index_topk");
+    }
+}
+
+// ---- MLA indexer: the prefill logits, every row over its own key range ------------------------
+static_assert(FMHA_MLA_INDEX_RAGGED_CHUNK == kMlaRaggedChunk || XFA_MLA_RAGGED_CHUNK != 1024,
+              "the header's chunk is the kernel's (but for an A/B build that sets its own)");
+static_assert(FMHA_MLA_INDEX_RAGGED_ROWS == kMlaRaggedRows, "the header's row block is the kernel's");
+
+void fmha_mla_index_logits_ragged(const void* q8, const void* weights, const void* k8, const void* k_scale,
+                                  const void* ks, const void* ke, void* logits, int32_t num_rows,
+                                  int32_t num_keys, int32_t num_heads, int32_t head_size,
+                                  const int64_t* q_strides, int64_t k_row_stride, int64_t logits_row_stride,
+                                  hipStream_t stream) {
+    try {
+        begin_fwd();
+        REQUIRE(q8 && weights && k8 && k_scale && logits,
+                "q8, weights, k8, k_scale and logits must be non-null device pointers");
+        REQUIRE(ks && ke, "ks and ke must be non-null device pointers");
+        REQUIRE(q_strides, "q_strides must be a non-null pointer (row, head)");
+        REQUIRE(num_heads == 32 || num_heads == 64, "the index logits support 32 or 64 heads (got %d)", num_heads);
+        REQUIRE(head_size == 128, "the index logits support head_size 128 only (got %d)", head_size);
+        REQUIRE(num_rows >= 0 && num_keys >= 0, "num_rows and num_keys must be non-negative (got %d, %d)",
+                num_rows, num_keys);
+        REQUIRE(logits_row_stride >= num_keys, "logits_row_stride must be at least num_keys (got %lld, %d)",
+                (long long)logits_row_stride, num_keys);
+        const int ext[2] = {num_rows, num_heads};
+        for (int i = 0; i < 2; ++i)
+            REQUIRE(q_strides[i] >= 0 && (ext[i] <= 1 || q_strides[i] % 16 == 0),
+                    "q strides must be non-negative multiples of 16 elements (bytes): stride %d is %lld", i,
+                    (long long)q_strides[i]);
+        REQUIRE(k_row_stride >= 0 && (num_keys <= 1 || (k_row_stride % 16 == 0 && k_row_stride >= 128)),
+                "the key row stride must be a multiple of 16 bytes, at least 128 (got %lld)", (long long)k_row_stride);
+        REQUIRE(!((((uintptr_t)q8) | ((uintptr_t)k8)) & 15), "q8 and k8 must be 16-byte aligned device pointers");
+        REQUIRE(!((((uintptr_t)weights) | ((uintptr_t)k_scale) | ((uintptr_t)ks) | ((uintptr_t)ke) | ((uintptr_t)logits)) & 3),
+                "weights, k_scale, ks, ke and logits must be 4-byte aligned device pointers");
+        const int64_t row_blocks = ((int64_t)num_rows + kMlaRaggedRows - 1) / kMlaRaggedRows;
+        const int64_t chunks = ((int64_t)num_keys + kMlaRaggedChunk - 1) / kMlaRaggedChunk;
+        REQUIRE(row_blocks * chunks <= 0x7fffffffLL, "%d rows over %d keys is more than one launch covers",
+                num_rows, num_keys);
+        if (num_rows == 0 || num_keys == 0) return;
+        MlaIndexRaggedParams p{};
+        p.q8 = q8; p.weights = (const float*)weights; p.k8 = k8; p.k_scale = (const float*)k_scale;
+        p.ks = (const int*)ks; p.ke = (const int*)ke; p.logits = (float*)logits;
+        p.q_row = q_strides[0]; p.q_head = q_strides[1]; p.k_row = k_row_stride;
+        p.logits_row = logits_row_stride;
+        p.m = num_rows; p.n = num_keys; p.heads = num_heads; p.row_blocks = (int)row_blocks;
+        hip_ok(launch_mla_index_logits_ragged(p, stream), "MLA ragged index logits launch");
+    } catch (...) {
+        fail(9, "internal error in fmha_mla_index_logits_ragged");
     }
 }
 

@@ -350,6 +350,28 @@ struct MlaIndexTopkParams {
 };
 hipError_t launch_mla_index_topk(const MlaIndexTopkParams& p, hipStream_t st);
 
+// MLA indexer, the prefill logits (fmha_mla_index_ragged.hip, fmha_mla_index_ragged_kernel.h): every
+// query row against its own key range [ks, ke) of a packed, non-paged fp8 key array.  Item = 16
+// rows x a chunk of keys; strides in bytes for q8 and k8, in elements for the logits.
+#ifndef XFA_MLA_RAGGED_CHUNK              // (an A/B build may set another: tools/mla_index_ragged_ab.py)
+#define XFA_MLA_RAGGED_CHUNK 1024
+#endif
+constexpr int kMlaRaggedChunk = XFA_MLA_RAGGED_CHUNK;   // keys of one workgroup's item
+constexpr int kMlaRaggedRows = 16;                      // query rows of one workgroup's item
+struct MlaIndexRaggedParams {
+    const void* q8;               // [m, heads, 128] e4m3 bytes
+    const float* weights;         // [m, heads]
+    const void* k8;               // [n, 128] e4m3 bytes
+    const float* k_scale;         // [n]
+    const int* ks;                // [m]
+    const int* ke;                // [m]
+    float* logits;                // [m, logits_row]
+    int64_t q_row, q_head, k_row;
+    int64_t logits_row;
+    int m, n, heads, row_blocks;  // row_blocks = ceil(m / kMlaRaggedRows)
+};
+hipError_t launch_mla_index_logits_ragged(const MlaIndexRaggedParams& p, hipStream_t st);
+
 // D = 256 (bucket of 129..256): 4 waves x 32 rows, one wave per SIMD (512 registers:
 // Q fragments and the O accumulator alone are 192), no LDS-DMA pipeline
 inline int fwd_block_m(int d, int waves) { return d > 128 ? 128 : waves * 32; }

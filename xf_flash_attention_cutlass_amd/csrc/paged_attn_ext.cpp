@@ -1360,6 +1360,54 @@ at::Tensor mha_mla_index_topk(const at::Tensor& logits, const at::Tensor& block_
     return out;
 }
 
+// The prefill logits (fmha_mla_index_logits_ragged): q8 [M, heads, 128] bytes by its own strides,
+// weights fp32 [M, heads], k8 [N, 128] bytes by its row stride, k_scale fp32 [N], ks / ke int32 [M].
+// Returns logits fp32 [M, N]: the caller's `out` (a column slice of a wider buffer is fine) or a new one.
+at::Tensor mha_mla_index_logits_ragged(const at::Tensor& q8, const at::Tensor& weights, const at::Tensor& k8,
+                                       const at::Tensor& k_scale, const at::Tensor& ks, const at::Tensor& ke,
+                                       const OptTensor& out_) {
+    TORCH_CHECK(is_byte_cache(q8) && is_byte_cache(k8), "q8 and k8 must be uint8 or float8_e4m3fn");
+    CHECK_DEVICE(q8); CHECK_DEVICE(k8);
+    TORCH_CHECK(q8.dim() == 3 && q8.size(2) == 128, "q8 must be (rows, heads, 128)");
+    TORCH_CHECK(q8.size(1) == 32 || q8.size(1) == 64, "the index logits support 32 or 64 heads, got ", q8.size(1));
+    TORCH_CHECK(q8.stride(2) == 1, "q8 must have contiguous last dimension");
+    TORCH_CHECK(aligned16(q8), "q8 must be 16-byte aligned with strides that are multiples of 16 bytes");
+    TORCH_CHECK(k8.dim() == 2 && k8.size(1) == 128 && k8.stride(1) == 1, "k8 must be (keys, 128) with contiguous last dimension");
+    TORCH_CHECK(aligned16(k8) && (k8.size(0) <= 1 || k8.stride(0) >= 128),
+                "k8 must be 16-byte aligned with a row stride that is a multiple of 16 bytes, at least 128");
+    const int64_t rows = q8.size(0), heads = q8.size(1), keys = k8.size(0);
+    TORCH_CHECK(rows <= 0x7fffffff && keys <= 0x7fffffff, "too many rows or keys");
+    TORCH_CHECK(weights.dtype() == torch::kFloat32 && weights.dim() == 2 && weights.size(0) == rows &&
+                    weights.size(1) == heads && weights.is_contiguous(),
+                "weights must be a contiguous fp32 (rows, heads)");
+    TORCH_CHECK(k_scale.dtype() == torch::kFloat32 && k_scale.dim() == 1 && k_scale.size(0) == keys &&
+                    (keys <= 1 || k_scale.stride(0) == 1),
+                "k_scale must be a contiguous fp32 (keys)");
+    check_batch_int32(ks, rows, "ks");
+    check_batch_int32(ke, rows, "ke");
+    for (const at::Tensor* t : {&weights, &k8, &k_scale, &ks, &ke})
+        TORCH_CHECK(t->is_cuda() && t->device() == q8.device(), "all tensors must be on q8's device");
+    at::Tensor out;
+    if (out_.has_value()) {
+        out = out_.value();
+        TORCH_CHECK(out.dtype() == torch::kFloat32 && out.is_cuda() && out.device() == q8.device(),
+                    "out must be fp32 on q8's device");
+        TORCH_CHECK(out.dim() == 2 && out.size(0) == rows && out.size(1) == keys, "out must be (rows, keys)");
+        TORCH_CHECK((out.stride(1) == 1 || out.size(1) <= 1) && (rows <= 1 || out.stride(0) >= keys),
+                    "out must have unit column stride and a row stride of at least keys");
+    } else {
+        out = torch::empty({rows, keys}, q8.options().dtype(torch::kFloat32));
+    }
+    if (rows == 0 || keys == 0) return out;
+    const c10::DeviceGuard device_guard(q8.device());
+    const int64_t st[2] = {q8.stride(0), q8.stride(1)};
+    fmha_mla_index_logits_ragged(q8.data_ptr(), weights.data_ptr(), k8.data_ptr(), k_scale.data_ptr(), ks.data_ptr(),
+                                 ke.data_ptr(), out.data_ptr(), (int)rows, (int)keys, (int)heads, 128, st,
+                                 keys <= 1 ? 128 : k8.stride(0), rows <= 1 ? keys : out.stride(0), cur_stream());
+    raise_if_failed("mla_index_logits_ragged");
+    return out;
+}
+
 namespace {
 
 // ---- `fwd_mla` / `varlen_fwd_mla`: q and k with 192 features a head, v with 128, each by its own
@@ -1618,6 +1666,12 @@ PYBIND11_MODULE(paged_attn, m) {
           py::arg("logits"), py::arg("block_table"), py::arg("context_lens"), py::arg("topk"), py::arg("seqlen_q") = 1,
           py::arg("page_block_size") = 64, py::arg("max_seqlen_k") = 0, py::arg("num_blocks") = -1,
           py::arg("out") = py::none());
+    m.def("_mla_index_logits_ragged", &mha_mla_index_logits_ragged,
+          "Fused MLA index logits of prefill rows, each over its own key range of a packed fp8 key array",
+          py::arg("q8"), py::arg("weights"), py::arg("k8"), py::arg("k_scale"), py::arg("ks"), py::arg("ke"),
+          py::arg("out") = py::none());
+    m.attr("_mla_index_ragged_chunk") = FMHA_MLA_INDEX_RAGGED_CHUNK;   // keys of one workgroup's item
+    m.attr("_mla_index_ragged_rows") = FMHA_MLA_INDEX_RAGGED_ROWS;     // ... and its query rows
     m.attr("_mla_index_topk_stage") = FMHA_MLA_INDEX_TOPK_STAGE;   // rows up to this many visible keys stay in LDS
     // ... and the MLA prefill (head size 192 for q / k, 128 for v), dense and packed
     m.def("_fwd_mla", &mha_fwd_mla, "MLA prefill forward (d_qk 192, d_v 128)", py::arg("q"), py::arg("k"),
@@ -1649,6 +1703,7 @@ PYBIND11_MODULE(paged_attn, m) {
         if (name == "mla_index_cache_append_fp8") return self.attr("_mla_index_cache_append_fp8");
         if (name == "mla_index_logits") return self.attr("_mla_index_logits");
         if (name == "mla_index_topk") return self.attr("_mla_index_topk");
+        if (name == "mla_index_logits_ragged") return self.attr("_mla_index_logits_ragged");
         if (name == "fwd_mla") return self.attr("_fwd_mla");
         if (name == "varlen_fwd_mla") return self.attr("_varlen_fwd_mla");
         if (name == "bwd_mla") return self.attr("_bwd_mla");

@@ -380,6 +380,33 @@ def mla_index_logits(q8, weights, index_cache, block_table, context_lens, max_se
                                            context_lens, int(max_seqlen_k), out)
 
 
+def mla_index_logits_ragged(q8, weights, k8, k_scale, ks, ke, out=None):
+    """The lightning indexer's logits for prefill and chunked prefill (DeepGEMM's `fp8_mqa_logits`),
+    one HIP launch (`paged_attn.mla_index_logits_ragged`), no scratch, no [rows, heads, keys] tensor:
+
+        logits[r, s] = k_scale[s] * sum_h weights[r, h] * relu(q8[r, h] . k8[s])    ks[r] <= s < ke[r]
+
+    with ks / ke clamped to [0, N], and -inf for every other s < N (a row with ke <= ks is all -inf),
+    so `torch.topk` over a row is valid as it stands.  Rows are new tokens of one causal sequence
+    (ks = 0, ke = position + 1), of several packed sequences (each row the range of its own
+    sequence's keys) or of a chunk over cached keys; a key outside a row's range never reaches it.
+
+    q8: [M, heads, 128] float8_e4m3fn or uint8, heads 32 or 64 (a view is fine: last dimension
+    contiguous, 16-byte aligned rows); weights: fp32 [M, heads] with q's quantisation scale, the
+    softmax scale and heads ** -0.5 folded in (any sign); k8: [N, 128] float8_e4m3fn or uint8 (row
+    stride a multiple of 16 bytes); k_scale: fp32 [N]; ks, ke: int32 [M]; out: fp32 [M, N] with unit
+    column stride (a column slice of a wider buffer is fine; the rest of it is not touched).
+
+    k8 and k_scale need no quantiser of their own: `mla_index_cache_append_fp8(k, cache, arange(N))`
+    into a one-block cache `[1, mla_index_cache_block_bytes(page)]` with page = N rounded up to 16
+    leaves `page * 128` key bytes followed by `page` fp32 descales, so
+    `k8 = cache[0, :N * 128].view(N, 128)` and
+    `k_scale = cache[0, page * 128:].view(torch.float32)[:N]` are views of it.
+    Returns the logits.  Not differentiable."""
+    with torch.no_grad():
+        return paged_attn.mla_index_logits_ragged(q8.detach(), weights.detach(), k8, k_scale, ks, ke, out)
+
+
 def mla_index_topk_slots(logits, block_table, context_lens, topk, seqlen_q=1, page_block_size=64):
     """The indexer's choice as `flash_mla_with_kvcache(indices=...)` takes it: int32 [b, seqlen_q,
     topk] of physical slots, from `mla_index_logits`' result.  A few lines of torch glue, not a
