@@ -127,7 +127,7 @@ void fmha_set_rng_state(uint64_t seed, uint64_t offset);
 void fmha_set_rng_state_device(const int64_t* seed_ptr, const int64_t* offset_ptr,
                                uint64_t offset_add, int64_t* rng_out);
 
-/* Library version / build identification, e.g. "xf-fmha-gfx950 2.16".  2.0 (round 3) changed
+/* Library version / build identification, e.g. "xf-fmha-gfx950 2.17".  2.0 (round 3) changed
  * argument lists of existing symbols; 2.1 exports those under _v2 names (see INTEGRATION.md
  * "ABI history"). */
 const char* fmha_version(void);
@@ -734,6 +734,43 @@ void fmha_mla_index_logits_ragged(const void* q8, const void* weights, const voi
                                   int32_t head_size /* 128 */, const int64_t* q_strides /* row,head; bytes */,
                                   int64_t k_row_stride /* bytes */, int64_t logits_row_stride,
                                   hipStream_t stream);
+
+/* --------------------------- MLA indexer: top-k selection for ragged prefill rows (2.17) */
+
+/* fmha_mla_index_topk_ragged: the stage between fmha_mla_index_logits_ragged and
+ * fmha_mla_decode_sparse for prefill and chunked prefill: the topk largest logits of every row
+ * within its own column range, as cache slots.  One launch of fmha_mla_index_topk_ragged_kernel
+ * (fmha_last_kernel() names it and its grid, num_rows workgroups of 256 threads), no scratch, no
+ * host sync (capturable in a graph), no atomics on global memory: the result is a function of the
+ * inputs alone.
+ *   logits  fp32 [M, logits_row_stride], unit column stride; any row stride >= N (rows may lie at
+ *           every offset from a 16-byte boundary)
+ *   ks, ke  int32 [M];  slots int64 [N], or NULL
+ *   indices int32 [M, indices_row_stride], indices_row_stride >= topk
+ * For row r, lo = clamp(ks[r], 0, N) and hi = clamp(ke[r], 0, N); its candidates are the columns
+ * lo <= s < hi.  Nothing outside [lo, hi) is read: it need not hold -inf, and whatever lies there
+ * does not reach the result.  hi <= lo gives a row of -1.
+ * ORDER, SELECTED SET, OUTPUT ORDER: those of fmha_mla_index_topk - the order on floats with
+ * -0.0 == +0.0 and +inf the largest; -inf and NaN unselectable, subnormals ordinary values; with
+ * m selectable candidates, c = min(m, topk) and T the c-th largest: every candidate > T and of the
+ * candidates == T the lowest columns until there are c; indices[r, 0:c] = the selected columns in
+ * ASCENDING COLUMN ORDER, indices[r, c:topk] = -1, columns >= topk of `indices` never touched.
+ * ENTRY: with slots, column s is emitted as slots[s] where that lies in [0, 2^31), else as -1 in
+ * place (slots is the append's slot_mapping for new tokens and the gather list for cached ones);
+ * with slots == NULL as s itself (an index into k8, or into an un-paged [N, 576] latent tensor).
+ * Rows of at most topk candidates skip the selection; for longer ones the keys of the first radix
+ * pass' threshold bin are kept in LDS where they are at most FMHA_MLA_INDEX_TOPK_RAGGED_STAGE,
+ * else the row is read again from global memory; there is no upper limit on topk or N.
+ * M == 0 validates, launches nothing and succeeds; N == 0 fills -1.  Refused with an error,
+ * outputs untouched: NULL logits, ks, ke or indices; topk < 1; a negative count;
+ * indices_row_stride < topk; a negative logits_row_stride, or one below N when M > 1; logits,
+ * ks, ke or indices not 4-byte aligned, slots not 8-byte aligned; M * 256 threads beyond 2^32 - 1
+ * (one grid). */
+#define FMHA_MLA_INDEX_TOPK_RAGGED_STAGE 2048
+void fmha_mla_index_topk_ragged(const void* logits, int64_t logits_row_stride, const void* ks, const void* ke,
+                                const void* slots /* may be NULL */, void* indices, int64_t indices_row_stride,
+                                int32_t topk, int32_t num_rows /* M */, int32_t num_keys /* N */,
+                                hipStream_t stream);
 
 /* ------------------------- MLA prefill: head size 192 for Q K^T, 128 for V (2.12) */
 

@@ -53,6 +53,9 @@ def units(tree):
     if os.path.exists(os.path.join(b.CSRC, "fmha_mla_index_ragged.hip")):   # (trees from 2.16 on)
         tus += [("fmha_mla_index_ragged", "fmha_mla_index_ragged.hip",
                  ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops", "-mllvm", "-amdgpu-mfma-vgpr-form"])]
+    if os.path.exists(os.path.join(b.CSRC, "fmha_mla_index_topk_ragged.hip")):   # (trees from 2.17 on)
+        tus += [("fmha_mla_index_topk_ragged", "fmha_mla_index_topk_ragged.hip",
+                 ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"])]
     tus += [(n + "+variants", src, d + ["-DXFA_VARIANTS=1"]) for n, src, d in tus if n + ".o" in b.VARIANT_TUS]
     return b, tus
 

@@ -53,6 +53,7 @@ from .interface import (  # noqa: E402
     mla_index_logits,
     mla_index_logits_ragged,
     mla_index_topk,
+    mla_index_topk_ragged,
     mla_index_topk_slots,
     mla_fp8_cache_row_bytes,
     quantize_fp8,
@@ -77,6 +78,7 @@ __all__ = [
     "mla_index_logits",
     "mla_index_logits_ragged",
     "mla_index_topk",
+    "mla_index_topk_ragged",
     "mla_index_topk_slots",
     "mla_fp8_cache_row_bytes",
     "quantize_fp8",

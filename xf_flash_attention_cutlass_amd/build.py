@@ -141,6 +141,9 @@ def build_lib(jobs: int = 8, force: bool = False, verbose: bool = False, variant
     # otherwise pays one v_accvgpr_read per accumulator element)
     todo.append((os.path.join(CSRC, "fmha_mla_index_ragged.hip"), os.path.join(OBJ, "fmha_mla_index_ragged.o"),
                  ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops", "-mllvm", "-amdgpu-mfma-vgpr-form"]))
+    # ... and its top-k selection for those rows, a unit of its own (integer work)
+    todo.append((os.path.join(CSRC, "fmha_mla_index_topk_ragged.hip"), os.path.join(OBJ, "fmha_mla_index_topk_ragged.o"),
+                 ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]))
     todo.append((os.path.join(CSRC, "fmha_api.cpp"), os.path.join(OBJ, "fmha_api.o"), []))
     if variants:
         todo = [(src, os.path.join(obj_dir, os.path.basename(out)), defs + ["-DXFA_VARIANTS=1"])

@@ -80,6 +80,7 @@ _SIGS = {
     "fmha_mla_index_logits_ragged": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, C.POINTER(C.c_int64),
                                      C.c_int64, C.c_int64, vp],
     "fmha_mla_index_topk": [vp, C.c_int64, vp, i32, vp, vp, C.c_int64, i32, i32, i32, i32, i32, i32, vp],
+    "fmha_mla_index_topk_ragged": [vp, C.c_int64, vp, vp, vp, vp, C.c_int64, i32, i32, i32, vp],
     "fmha_fwd_mla": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, C.POINTER(C.c_int64), f32,
                      C.c_int, C.c_int, b_, vp],
     "fmha_varlen_fwd_mla": [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32,

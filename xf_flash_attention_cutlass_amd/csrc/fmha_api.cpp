@@ -525,7 +525,7 @@ const char* fmha_last_error(void) { return g_err.c_str(); }
 int fmha_last_status(void) { return g_status; }
 int fmha_last_num_splits(void) { return g_last_splits; }
 const char* fmha_last_kernel(void) { return g_last_kernel; }
-const char* fmha_version(void) { return XFA_VARIANTS ? "xf-fmha-gfx950 2.16 (variants)" : "xf-fmha-gfx950 2.16"; }
+const char* fmha_version(void) { return XFA_VARIANTS ? "xf-fmha-gfx950 2.17 (variants)" : "xf-fmha-gfx950 2.17"; }
 
 void fmha_set_rng_state(uint64_t seed, uint64_t offset) {
     g_seed = seed;
@@ -1858,6 +1858,41 @@ void fmha_mla_index_logits_ragged(const void* q8, const void* weights, const voi
         hip_ok(launch_mla_index_logits_ragged(p, stream), "MLA ragged index logits launch");
     } catch (...) {
         fail(9, "internal error in fmha_mla_index_logits_ragged");
+    }
+}
+
+// ---- MLA indexer: the top-k selection of prefill rows, every row within its own key range -----
+static_assert(FMHA_MLA_INDEX_TOPK_RAGGED_STAGE == kMlaTopkRaggedStage, "the header's list limit is the kernel's");
+
+void fmha_mla_index_topk_ragged(const void* logits, int64_t logits_row_stride, const void* ks, const void* ke,
+                                const void* slots, void* indices, int64_t indices_row_stride, int32_t topk,
+                                int32_t num_rows, int32_t num_keys, hipStream_t stream) {
+    try {
+        begin_fwd();
+        REQUIRE(logits && indices, "logits and indices must be non-null device pointers");
+        REQUIRE(ks && ke, "ks and ke must be non-null device pointers");
+        REQUIRE(topk >= 1, "topk must be at least 1 (got %d)", topk);
+        REQUIRE(num_rows >= 0 && num_keys >= 0, "num_rows and num_keys must be non-negative (got %d, %d)",
+                num_rows, num_keys);
+        REQUIRE(logits_row_stride >= 0 && (num_rows <= 1 || logits_row_stride >= num_keys),
+                "logits_row_stride must be non-negative, and at least num_keys (got %lld, %d)",
+                (long long)logits_row_stride, num_keys);
+        REQUIRE(indices_row_stride >= topk, "indices_row_stride must be at least topk (got %lld, %d)",
+                (long long)indices_row_stride, topk);
+        REQUIRE(!((((uintptr_t)logits) | ((uintptr_t)indices) | ((uintptr_t)ks) | ((uintptr_t)ke)) & 3),
+                "logits, indices, ks and ke must be 4-byte aligned device pointers");
+        REQUIRE(!(((uintptr_t)slots) & 7), "slots must be an 8-byte aligned device pointer (or NULL)");
+        REQUIRE((int64_t)num_rows * kMlaTopkRaggedThreads <= 0xffffffffLL,
+                "%d rows is more than one launch covers", num_rows);
+        if (num_rows == 0) return;
+        MlaIndexTopkRaggedParams p{};
+        p.logits = (const float*)logits; p.ks = (const int*)ks; p.ke = (const int*)ke;
+        p.slots = (const int64_t*)slots; p.indices = (int*)indices;
+        p.logits_row = logits_row_stride; p.indices_row = indices_row_stride;
+        p.rows = num_rows; p.keys = num_keys; p.topk = topk;
+        hip_ok(launch_mla_index_topk_ragged(p, stream), "MLA ragged index top-k launch");
+    } catch (...) {
+        fail(9, "internal error in fmha_mla_index_topk_ragged");
     }
 }
 

@@ -372,6 +372,27 @@ struct MlaIndexRaggedParams {
 };
 hipError_t launch_mla_index_logits_ragged(const MlaIndexRaggedParams& p, hipStream_t st);
 
+// MLA indexer, the selection for prefill rows (fmha_mla_index_topk_ragged.hip,
+// fmha_mla_index_topk_ragged_kernel.h): the top-k keys of every logits row within its own column
+// range [ks, ke), as slots[column] (or the column) in ascending column order.  One workgroup of 4
+// waves per row, the last row first.
+#ifndef XFA_RAGTOPK_WAVES                 // (an A/B build may set another: tools/mla_index_topk_ragged_ab.py)
+#define XFA_RAGTOPK_WAVES 4
+#endif
+constexpr int kMlaTopkRaggedThreads = 64 * XFA_RAGTOPK_WAVES;
+constexpr int kMlaTopkRaggedStage = 2048;  // a threshold bin of at most this many keys is kept in LDS
+struct MlaIndexTopkRaggedParams {
+    const float* logits;          // [rows, logits_row]
+    const int* ks;                // [rows]
+    const int* ke;                // [rows]
+    const int64_t* slots;         // [keys], or null: the column itself
+    int* indices;                 // [rows, indices_row]
+    int64_t logits_row, indices_row;
+    int rows, keys, topk;
+    int cap;                      // the LDS list's entries (set by the launcher)
+};
+hipError_t launch_mla_index_topk_ragged(const MlaIndexTopkRaggedParams& p, hipStream_t st);
+
 // D = 256 (bucket of 129..256): 4 waves x 32 rows, one wave per SIMD (512 registers:
 // Q fragments and the O accumulator alone are 192), no LDS-DMA pipeline
 inline int fwd_block_m(int d, int waves) { return d > 128 ? 128 : waves * 32; }

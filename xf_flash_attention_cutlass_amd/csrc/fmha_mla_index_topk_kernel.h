@@ -135,6 +135,7 @@ __device__ __forceinline__ void topk_hist(unsigned* h, const unsigned k[4], unsi
     }
 }
 
+#ifndef XFA_TOPK_HELPERS_ONLY        // (fmha_mla_index_topk_ragged_kernel.h takes the helpers above only)
 __global__ void __launch_bounds__(kTopkThreads) fmha_mla_index_topk_kernel(const MlaIndexTopkParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     unsigned* const lds = reinterpret_cast<unsigned*>(smem);
@@ -267,5 +268,6 @@ __global__ void __launch_bounds__(kTopkThreads) fmha_mla_index_topk_kernel(const
     });
     for (int t = count + tid; t < topk; t += kTopkThreads) out[t] = -1;
 }
+#endif
 
 }  // namespace xfa

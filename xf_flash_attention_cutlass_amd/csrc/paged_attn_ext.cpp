@@ -1408,6 +1408,50 @@ at::Tensor mha_mla_index_logits_ragged(const at::Tensor& q8, const at::Tensor& w
     return out;
 }
 
+// The prefill selection (fmha_mla_index_topk_ragged): logits fp32 [M, N] by its own row stride, ks /
+// ke int32 [M], slots int64 [N] or none.  Returns indices int32 [M, topk]: the caller's `out` (a
+// column slice of a wider buffer is fine) or a new one.
+at::Tensor mha_mla_index_topk_ragged(const at::Tensor& logits, const at::Tensor& ks, const at::Tensor& ke,
+                                     const int64_t topk, const OptTensor& slots_, const OptTensor& out_) {
+    CHECK_DEVICE(logits);
+    TORCH_CHECK(logits.dtype() == torch::kFloat32, "logits must be fp32");
+    TORCH_CHECK(logits.dim() == 2, "logits must be (rows, keys)");
+    TORCH_CHECK(logits.stride(1) == 1 || logits.size(1) <= 1, "logits must have contiguous last dimension");
+    TORCH_CHECK(topk >= 1 && topk <= 0x7fffffff, "topk must be at least 1");
+    const int64_t rows = logits.size(0), keys = logits.size(1);
+    TORCH_CHECK(rows <= 0x7fffffff && keys <= 0x7fffffff, "too many rows or keys");
+    TORCH_CHECK(rows <= 1 || logits.stride(0) >= keys, "logits' rows must lie at least keys apart");
+    check_batch_int32(ks, rows, "ks");
+    check_batch_int32(ke, rows, "ke");
+    TORCH_CHECK(ks.device() == logits.device() && ke.device() == logits.device(), "ks and ke must be on logits' device");
+    const void* slots = nullptr;
+    if (slots_.has_value()) {
+        const at::Tensor& s = slots_.value();
+        TORCH_CHECK(s.dtype() == torch::kInt64 && s.is_cuda() && s.device() == logits.device() && s.dim() == 1 &&
+                        s.size(0) == keys && (keys <= 1 || s.stride(0) == 1),
+                    "slots must be a contiguous int64 (keys) on logits' device");
+        slots = s.data_ptr();
+    }
+    at::Tensor out;
+    if (out_.has_value()) {
+        out = out_.value();
+        TORCH_CHECK(out.dtype() == torch::kInt32 && out.is_cuda() && out.device() == logits.device(),
+                    "out must be int32 on logits' device");
+        TORCH_CHECK(out.dim() == 2 && out.size(0) == rows && out.size(1) == topk, "out must be (rows, topk)");
+        TORCH_CHECK((out.stride(1) == 1 || topk <= 1) && (rows <= 1 || out.stride(0) >= topk),
+                    "out must have unit column stride and a row stride of at least topk");
+    } else {
+        out = torch::empty({rows, topk}, logits.options().dtype(torch::kInt32));
+    }
+    if (rows == 0) return out;
+    const c10::DeviceGuard device_guard(logits.device());
+    fmha_mla_index_topk_ragged(logits.data_ptr(), rows <= 1 ? keys : logits.stride(0), ks.data_ptr(), ke.data_ptr(), slots,
+                               out.data_ptr(), rows <= 1 ? topk : out.stride(0), (int)topk, (int)rows, (int)keys,
+                               cur_stream());
+    raise_if_failed("mla_index_topk_ragged");
+    return out;
+}
+
 namespace {
 
 // ---- `fwd_mla` / `varlen_fwd_mla`: q and k with 192 features a head, v with 128, each by its own
@@ -1673,6 +1717,11 @@ PYBIND11_MODULE(paged_attn, m) {
     m.attr("_mla_index_ragged_chunk") = FMHA_MLA_INDEX_RAGGED_CHUNK;   // keys of one workgroup's item
     m.attr("_mla_index_ragged_rows") = FMHA_MLA_INDEX_RAGGED_ROWS;     // ... and its query rows
     m.attr("_mla_index_topk_stage") = FMHA_MLA_INDEX_TOPK_STAGE;   // rows up to this many visible keys stay in LDS
+    m.def("_mla_index_topk_ragged", &mha_mla_index_topk_ragged,
+          "Top-k selection over the MLA index logits of prefill rows, each within its own key range",
+          py::arg("logits"), py::arg("ks"), py::arg("ke"), py::arg("topk"), py::arg("slots") = py::none(),
+          py::arg("out") = py::none());
+    m.attr("_mla_index_topk_ragged_stage") = FMHA_MLA_INDEX_TOPK_RAGGED_STAGE;   // a threshold bin up to this many keys stays in LDS
     // ... and the MLA prefill (head size 192 for q / k, 128 for v), dense and packed
     m.def("_fwd_mla", &mha_fwd_mla, "MLA prefill forward (d_qk 192, d_v 128)", py::arg("q"), py::arg("k"),
           py::arg("v"), py::arg("out") = py::none(), py::arg("softmax_scale") = 0.07216878364870322f,
@@ -1704,6 +1753,7 @@ PYBIND11_MODULE(paged_attn, m) {
         if (name == "mla_index_logits") return self.attr("_mla_index_logits");
         if (name == "mla_index_topk") return self.attr("_mla_index_topk");
         if (name == "mla_index_logits_ragged") return self.attr("_mla_index_logits_ragged");
+        if (name == "mla_index_topk_ragged") return self.attr("_mla_index_topk_ragged");
         if (name == "fwd_mla") return self.attr("_fwd_mla");
         if (name == "varlen_fwd_mla") return self.attr("_varlen_fwd_mla");
         if (name == "bwd_mla") return self.attr("_bwd_mla");

@@ -455,6 +455,36 @@ def mla_index_topk(logits, block_table, context_lens, topk, seqlen_q=1, page_blo
                                          -1 if num_blocks is None else int(num_blocks), out)
 
 
+def mla_index_topk_ragged(logits, ks, ke, topk, slots=None, out=None):
+    """The indexer's choice for prefill and chunked prefill, in one HIP launch
+    (`paged_attn.mla_index_topk_ragged`: an exact radix select, one workgroup of 4 waves per row, no
+    scratch, no host sync, graph-capturable, bitwise reproducible): int32 [M, topk] from
+    `mla_index_logits_ragged`'s result.
+
+    Row r selects among the columns clamp(ks[r], 0, N) <= s < clamp(ke[r], 0, N) and reads nothing
+    outside them (they need not hold -inf); ke <= ks gives a row of -1.  Order, ties and output order
+    are `mla_index_topk`'s: the order on floats with -0.0 == +0.0 and +inf the largest; -inf and NaN
+    are never selected; of equal values at the threshold the lowest columns win; the selected columns
+    come in ASCENDING column order, then -1 up to topk.  With `slots` (int64 [N]: the physical cache
+    slot of key column s - the append's slot_mapping for new tokens, the gather list for cached
+    ones) column s is emitted as slots[s], or as -1 in place where that is outside [0, 2^31);
+    without it as s itself (an index into k8 or into an un-paged [N, 576] latent tensor).
+
+    logits: fp32 [M, N], last dimension contiguous, any row stride >= N (a view of a wider buffer is
+    fine); ks, ke: int32 [M]; out: int32 [M, topk] with unit column stride (a column slice of a wider
+    buffer is fine; the rest of it is not touched).
+
+    A chunked-prefill step over a paged latent cache, HIP end to end:
+
+        logits = mla_index_logits_ragged(q8, weights, k8, k_scale, ks, ke)
+        idx = mla_index_topk_ragged(logits, ks, ke, topk, slots=slots)
+        out, lse = flash_mla_with_kvcache(q[None], kv_cache, None, None, indices=idx[None])
+
+    Returns the indices.  Not differentiable."""
+    with torch.no_grad():
+        return paged_attn.mla_index_topk_ragged(logits.detach(), ks, ke, int(topk), slots, out)
+
+
 _GRANULARITY = {"tensor": 0, "head": 1}
 
 
