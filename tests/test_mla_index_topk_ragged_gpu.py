@@ -61,7 +61,7 @@ def test_topk_ragged_equals_the_reference(topk, with_slots, family):
     assert torch.equal(got, ref), f"rows {bad.tolist()} of ranges {list(zip(ks.tolist(), ke.tolist()))} differ"
 
 
-@pytest.mark.parametrize("family", ["randn", "three"])
+@pytest.mark.parametrize("family", ["randn", "three", "equal", "dense", "mixed"])
 def test_agrees_with_the_decode_selection_on_one_causal_sequence(family):
     """ks = 0, ke = N - M + r + 1, slots = the block table expanded: bit-equal to mla_index_topk at
     batch 1, seqlen_q M."""
