@@ -127,7 +127,7 @@ void fmha_set_rng_state(uint64_t seed, uint64_t offset);
 void fmha_set_rng_state_device(const int64_t* seed_ptr, const int64_t* offset_ptr,
                                uint64_t offset_add, int64_t* rng_out);
 
-/* Library version / build identification, e.g. "xf-fmha-gfx950 2.17".  2.0 (round 3) changed
+/* Library version / build identification, e.g. "xf-fmha-gfx950 2.18".  2.0 (round 3) changed
  * argument lists of existing symbols; 2.1 exports those under _v2 names (see INTEGRATION.md
  * "ABI history"). */
 const char* fmha_version(void);
@@ -697,6 +697,36 @@ void fmha_mla_index_topk(const void* logits, int64_t logits_row_stride,
                          const void* context_lens, void* indices, int64_t indices_row_stride,
                          int32_t topk, int32_t seqlen_q, int32_t max_seqlen_k, int32_t batch_size,
                          int32_t num_blocks, int32_t page_block_size, hipStream_t stream);
+
+/* --------------------------- MLA indexer: top-k selection, long rows split over workgroups (2.18) */
+
+/* fmha_mla_index_topk_split: fmha_mla_index_topk's result, bit for bit (the same set, ties, output
+ * order, -1 entries and untouched columns), with every row cut into `splits` chunks of
+ *   L = ceil(max_seqlen_k / splits), rounded up to a multiple of 4
+ * consecutive columns.  Two launches: fmha_mla_index_topk_part_kernel, batch * seqlen_q * splits
+ * workgroups, selects the topk of chunk c of row r within the row's visible columns [c L, min((c +
+ * 1) L, vis)) - the chunk is read once and kept in LDS - and writes them in ascending position as
+ * (key, column) pairs to scratch; fmha_mla_index_topk_merge_kernel, batch * seqlen_q workgroups,
+ * runs the same select over the row's splits * topk candidates in chunk order, reading of the
+ * scratch only what the first launch wrote.  fmha_last_kernel() names the last launch, the merge
+ * kernel and its grid.  A selected column has fewer than topk columns ahead of it in the row's
+ * order, so also within its chunk: no chunk drops it.  No host sync (capturable in a graph), no
+ * atomics on global memory, one writer per scratch and output word: a function of the inputs alone.
+ * Scratch: fmha_mla_index_topk_split_workspace_size(batch * seqlen_q, topk, splits) bytes =
+ * rows * splits * (8 topk + 4), rounded up to 16: the caller's `workspace` (16-byte aligned, at
+ * least that large, contents ignored), or with workspace == NULL the library's per-(device,
+ * stream) pool, which a launch on the same stream may reuse.
+ * Refused with an error, outputs untouched: whatever fmha_mla_index_topk refuses; splits outside
+ * [2, 16]; splits * topk > FMHA_MLA_INDEX_TOPK_STAGE (the candidates of a row are staged in
+ * LDS); L > FMHA_MLA_INDEX_TOPK_STAGE; a workspace that is too small or not 16-byte aligned. */
+size_t fmha_mla_index_topk_split_workspace_size(int64_t rows, int32_t topk, int32_t splits);
+void fmha_mla_index_topk_split(const void* logits, int64_t logits_row_stride,
+                               const void* block_table, int32_t block_table_stride,
+                               const void* context_lens, void* indices, int64_t indices_row_stride,
+                               int32_t topk, int32_t seqlen_q, int32_t max_seqlen_k, int32_t batch_size,
+                               int32_t num_blocks, int32_t page_block_size, int32_t splits,
+                               void* workspace /* may be NULL */, size_t workspace_bytes,
+                               hipStream_t stream);
 
 /* --------------------------- MLA indexer: logits for ragged prefill rows (2.16) */
 

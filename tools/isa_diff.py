@@ -56,6 +56,9 @@ def units(tree):
     if os.path.exists(os.path.join(b.CSRC, "fmha_mla_index_topk_ragged.hip")):   # (trees from 2.17 on)
         tus += [("fmha_mla_index_topk_ragged", "fmha_mla_index_topk_ragged.hip",
                  ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"])]
+    if os.path.exists(os.path.join(b.CSRC, "fmha_mla_index_topk_split.hip")):   # (trees from 2.18 on)
+        tus += [("fmha_mla_index_topk_split", "fmha_mla_index_topk_split.hip",
+                 ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"])]
     tus += [(n + "+variants", src, d + ["-DXFA_VARIANTS=1"]) for n, src, d in tus if n + ".o" in b.VARIANT_TUS]
     return b, tus
 

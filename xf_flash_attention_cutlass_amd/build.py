@@ -144,6 +144,9 @@ def build_lib(jobs: int = 8, force: bool = False, verbose: bool = False, variant
     # ... and its top-k selection for those rows, a unit of its own (integer work)
     todo.append((os.path.join(CSRC, "fmha_mla_index_topk_ragged.hip"), os.path.join(OBJ, "fmha_mla_index_topk_ragged.o"),
                  ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]))
+    # ... and the selection with a row split over several workgroups, likewise
+    todo.append((os.path.join(CSRC, "fmha_mla_index_topk_split.hip"), os.path.join(OBJ, "fmha_mla_index_topk_split.o"),
+                 ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]))
     todo.append((os.path.join(CSRC, "fmha_api.cpp"), os.path.join(OBJ, "fmha_api.o"), []))
     if variants:
         todo = [(src, os.path.join(obj_dir, os.path.basename(out)), defs + ["-DXFA_VARIANTS=1"])

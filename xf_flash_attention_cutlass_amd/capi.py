@@ -81,6 +81,9 @@ _SIGS = {
                                      C.c_int64, C.c_int64, vp],
     "fmha_mla_index_topk": [vp, C.c_int64, vp, i32, vp, vp, C.c_int64, i32, i32, i32, i32, i32, i32, vp],
     "fmha_mla_index_topk_ragged": [vp, C.c_int64, vp, vp, vp, vp, C.c_int64, i32, i32, i32, vp],
+    "fmha_mla_index_topk_split": [vp, C.c_int64, vp, i32, vp, vp, C.c_int64, i32, i32, i32, i32, i32, i32, i32,
+                                  vp, sz, vp],
+    "fmha_mla_index_topk_split_workspace_size": [C.c_int64, i32, i32],
     "fmha_fwd_mla": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, C.POINTER(C.c_int64), f32,
                      C.c_int, C.c_int, b_, vp],
     "fmha_varlen_fwd_mla": [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32,
@@ -102,7 +105,8 @@ _SIGS = {
 _RES = {"fmha_last_error": C.c_char_p, "fmha_last_kernel": C.c_char_p, "fmha_version": C.c_char_p, "fmha_last_status": C.c_int,
         "fmha_last_num_splits": C.c_int,
         "fmha_set_option": C.c_int, "fmha_get_option": C.c_int,
-        "fmha_bwd_workspace_size_v2": sz, "fmha_varlen_bwd_workspace_size_v2": sz}
+        "fmha_bwd_workspace_size_v2": sz, "fmha_varlen_bwd_workspace_size_v2": sz,
+        "fmha_mla_index_topk_split_workspace_size": sz}
 
 EXPORTED = tuple(_SIGS)
 

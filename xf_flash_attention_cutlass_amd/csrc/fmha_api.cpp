@@ -525,7 +525,7 @@ const char* fmha_last_error(void) { return g_err.c_str(); }
 int fmha_last_status(void) { return g_status; }
 int fmha_last_num_splits(void) { return g_last_splits; }
 const char* fmha_last_kernel(void) { return g_last_kernel; }
-const char* fmha_version(void) { return XFA_VARIANTS ? "xf-fmha-gfx950 2.17 (variants)" : "xf-fmha-gfx950 2.17"; }
+const char* fmha_version(void) { return XFA_VARIANTS ? "xf-fmha-gfx950 2.18 (variants)" : "xf-fmha-gfx950 2.18"; }
 
 void fmha_set_rng_state(uint64_t seed, uint64_t offset) {
     g_seed = seed;
@@ -1771,44 +1771,101 @@ void fmha_mla_index_logits(const void* q8, const void* weights, const void* inde
 // ---- MLA indexer: the top-k selection, logits to physical slots in ascending key position
 static_assert(FMHA_MLA_INDEX_TOPK_STAGE == kMlaTopkStage, "the header's staging threshold is the kernel's");
 
+// What both selection entries check alike, in the order and the words of 2.15, and the launch they
+// describe
+#define REQUIRE_OK(cond, ...) do { if (!(cond)) return fail(1, __VA_ARGS__); } while (0)
+static bool mla_index_topk_args(const void* logits, int64_t logits_row_stride, const void* block_table,
+                                int32_t block_table_stride, const void* context_lens, void* indices,
+                                int64_t indices_row_stride, int32_t topk, int32_t seqlen_q, int32_t max_seqlen_k,
+                                int32_t batch_size, int32_t num_blocks, int32_t page_block_size,
+                                MlaIndexTopkParams& p) {
+    REQUIRE_OK(logits && indices, "logits and indices must be non-null device pointers");
+    REQUIRE_OK(block_table && context_lens, "block_table and context_lens must be non-null device pointers");
+    REQUIRE_OK(topk >= 1, "topk must be at least 1 (got %d)", topk);
+    REQUIRE_OK(seqlen_q >= 1, "seqlen_q must be at least 1 (got %d)", seqlen_q);
+    REQUIRE_OK(batch_size >= 0, "batch size must be non-negative (got %d)", batch_size);
+    REQUIRE_OK(page_block_size > 0 && page_block_size % 16 == 0,
+            "page_block_size must be a positive multiple of 16 (got %d)", page_block_size);
+    REQUIRE_OK(num_blocks >= 1, "num_blocks must be at least 1 (got %d)", num_blocks);
+    REQUIRE_OK(block_table_stride >= 0 && max_seqlen_k >= 0 &&
+                (int64_t)max_seqlen_k <= (int64_t)block_table_stride * page_block_size,
+            "max_seqlen_k must lie in [0, block_table_stride * page_block_size] (got %d, table %d x page %d)",
+            max_seqlen_k, block_table_stride, page_block_size);
+    REQUIRE_OK(logits_row_stride >= max_seqlen_k, "logits_row_stride must be at least max_seqlen_k (got %lld, %d)",
+            (long long)logits_row_stride, max_seqlen_k);
+    REQUIRE_OK(indices_row_stride >= topk, "indices_row_stride must be at least topk (got %lld, %d)",
+            (long long)indices_row_stride, topk);
+    REQUIRE_OK(!((((uintptr_t)logits) | ((uintptr_t)indices) | ((uintptr_t)block_table) | ((uintptr_t)context_lens)) & 3),
+            "logits, indices, block_table and context_lens must be 4-byte aligned device pointers");
+    REQUIRE_OK((int64_t)batch_size * seqlen_q <= 0x7fffffffLL,
+            "batch_size * seqlen_q = %lld rows is more than one launch covers", (long long)batch_size * seqlen_q);
+    p.logits = (const float*)logits; p.block_table = (const int*)block_table;
+    p.context_lens = (const int*)context_lens; p.indices = (int*)indices;
+    p.logits_row = logits_row_stride; p.indices_row = indices_row_stride;
+    p.bt_stride = block_table_stride; p.page = page_block_size; p.num_blocks = num_blocks;
+    p.max_seqlen_k = max_seqlen_k;
+    p.rows = batch_size * seqlen_q; p.seqlen_q = seqlen_q; p.topk = topk;
+    return true;
+}
+#undef REQUIRE_OK
+
 void fmha_mla_index_topk(const void* logits, int64_t logits_row_stride, const void* block_table,
                          int32_t block_table_stride, const void* context_lens, void* indices,
                          int64_t indices_row_stride, int32_t topk, int32_t seqlen_q, int32_t max_seqlen_k,
                          int32_t batch_size, int32_t num_blocks, int32_t page_block_size, hipStream_t stream) {
     try {
         begin_fwd();
-        REQUIRE(logits && indices, "logits and indices must be non-null device pointers");
-        REQUIRE(block_table && context_lens, "block_table and context_lens must be non-null device pointers");
-        REQUIRE(topk >= 1, "topk must be at least 1 (got %d)", topk);
-        REQUIRE(seqlen_q >= 1, "seqlen_q must be at least 1 (got %d)", seqlen_q);
-        REQUIRE(batch_size >= 0, "batch size must be non-negative (got %d)", batch_size);
-        REQUIRE(page_block_size > 0 && page_block_size % 16 == 0,
-                "page_block_size must be a positive multiple of 16 (got %d)", page_block_size);
-        REQUIRE(num_blocks >= 1, "num_blocks must be at least 1 (got %d)", num_blocks);
-        REQUIRE(block_table_stride >= 0 && max_seqlen_k >= 0 &&
-                    (int64_t)max_seqlen_k <= (int64_t)block_table_stride * page_block_size,
-                "max_seqlen_k must lie in [0, block_table_stride * page_block_size] (got %d, table %d x page %d)",
-                max_seqlen_k, block_table_stride, page_block_size);
-        REQUIRE(logits_row_stride >= max_seqlen_k, "logits_row_stride must be at least max_seqlen_k (got %lld, %d)",
-                (long long)logits_row_stride, max_seqlen_k);
-        REQUIRE(indices_row_stride >= topk, "indices_row_stride must be at least topk (got %lld, %d)",
-                (long long)indices_row_stride, topk);
-        REQUIRE(!((((uintptr_t)logits) | ((uintptr_t)indices) | ((uintptr_t)block_table) | ((uintptr_t)context_lens)) & 3),
-                "logits, indices, block_table and context_lens must be 4-byte aligned device pointers");
-        REQUIRE((int64_t)batch_size * seqlen_q <= 0x7fffffffLL,
-                "batch_size * seqlen_q = %lld rows is more than one launch covers", (long long)batch_size * seqlen_q);
-        if (batch_size == 0) return;
         MlaIndexTopkParams p{};
-        p.logits = (const float*)logits; p.block_table = (const int*)block_table;
-        p.context_lens = (const int*)context_lens; p.indices = (int*)indices;
-        p.logits_row = logits_row_stride; p.indices_row = indices_row_stride;
-        p.bt_stride = block_table_stride; p.page = page_block_size; p.num_blocks = num_blocks;
-        p.max_seqlen_k = max_seqlen_k;
-        p.rows = batch_size * seqlen_q; p.seqlen_q = seqlen_q; p.topk = topk;
+        if (!mla_index_topk_args(logits, logits_row_stride, block_table, block_table_stride, context_lens, indices,
+                                 indices_row_stride, topk, seqlen_q, max_seqlen_k, batch_size, num_blocks,
+                                 page_block_size, p))
+            return;
+        if (batch_size == 0) return;
         p.device = current_device();
         hip_ok(launch_mla_index_topk(p, stream), "MLA index top-k launch");
     } catch (...) {
         fail(9, "internal error in fmha_mla_index_topk");
+    }
+}
+
+// ... with every row split over `splits` workgroups.  Scratch: [keys][columns][counts], a (key,
+// column) pair for each of topk places of every (row, chunk) and one count
+size_t fmha_mla_index_topk_split_workspace_size(int64_t rows, int32_t topk, int32_t splits) {
+    const size_t parts = (size_t)std::max<int64_t>(rows, 0) * (size_t)std::max(splits, 0);
+    return (parts * (size_t)std::max(topk, 0) * 8 + parts * 4 + 15) & ~(size_t)15;
+}
+
+void fmha_mla_index_topk_split(const void* logits, int64_t logits_row_stride, const void* block_table,
+                               int32_t block_table_stride, const void* context_lens, void* indices,
+                               int64_t indices_row_stride, int32_t topk, int32_t seqlen_q, int32_t max_seqlen_k,
+                               int32_t batch_size, int32_t num_blocks, int32_t page_block_size, int32_t splits,
+                               void* workspace, size_t workspace_bytes, hipStream_t stream) {
+    try {
+        begin_fwd();
+        MlaIndexTopkSplitParams p{};
+        if (!mla_index_topk_args(logits, logits_row_stride, block_table, block_table_stride, context_lens, indices,
+                                 indices_row_stride, topk, seqlen_q, max_seqlen_k, batch_size, num_blocks,
+                                 page_block_size, p))
+            return;
+        REQUIRE(splits >= kMlaTopkSplitsMin && splits <= kMlaTopkSplitsMax, "splits must lie in [%d, %d] (got %d)",
+                kMlaTopkSplitsMin, kMlaTopkSplitsMax, splits);
+        REQUIRE((int64_t)splits * topk <= kMlaTopkStage, "splits * topk must be at most %d (got %d x %d)",
+                kMlaTopkStage, splits, topk);
+        p.splits = splits; p.chunk = mla_topk_split_chunk(max_seqlen_k, splits);
+        REQUIRE(p.chunk <= kMlaTopkStage, "a chunk of ceil(max_seqlen_k / splits) = %d columns is more than %d",
+                p.chunk, kMlaTopkStage);
+        const size_t need = fmha_mla_index_topk_split_workspace_size(p.rows, topk, splits);
+        REQUIRE(!workspace || workspace_bytes >= need, "workspace too small (%zu < %zu bytes)", workspace_bytes, need);
+        REQUIRE(!(((uintptr_t)workspace) & 15), "workspace must be a 16-byte aligned device pointer (or NULL)");
+        if (batch_size == 0) return;
+        p.device = current_device();
+        char* ws = workspace ? (char*)workspace : (char*)pool_get(stream, need);
+        REQUIRE(ws, "could not allocate %zu bytes of selection scratch", need);
+        const size_t words = (size_t)p.rows * splits * topk;
+        p.keys = (unsigned*)ws; p.cols = (int*)(ws + 4 * words); p.counts = (int*)(ws + 8 * words);
+        hip_ok(launch_mla_index_topk_split(p, stream), "MLA split index top-k launch");
+    } catch (...) {
+        fail(9, "internal error in fmha_mla_index_topk_split");
     }
 }
 

@@ -349,6 +349,20 @@ struct MlaIndexTopkParams {
     int device;
 };
 hipError_t launch_mla_index_topk(const MlaIndexTopkParams& p, hipStream_t st);
+// ... with every row split over `splits` workgroups (fmha_mla_index_topk_split.hip,
+// fmha_mla_index_topk_split_kernel.h): the chunks' own selections into scratch, then one workgroup
+// per row over them.  The same result.
+constexpr int kMlaTopkSplitsMin = 2, kMlaTopkSplitsMax = 16;
+struct MlaIndexTopkSplitParams : MlaIndexTopkParams {
+    int splits, chunk;            // chunk: columns of one workgroup, a multiple of 4, <= kMlaTopkStage
+    unsigned* keys;               // [rows, splits, topk]: a chunk's selected keys, ascending position
+    int* cols;                    // [rows, splits, topk]: ... and their columns
+    int* counts;                  // [rows, splits]: how many a chunk selected
+};
+inline int mla_topk_split_chunk(int max_seqlen_k, int splits) {
+    return (int)((((int64_t)max_seqlen_k + splits - 1) / splits + 3) & ~(int64_t)3);
+}
+hipError_t launch_mla_index_topk_split(const MlaIndexTopkSplitParams& p, hipStream_t st);
 
 // MLA indexer, the prefill logits (fmha_mla_index_ragged.hip, fmha_mla_index_ragged_kernel.h): every
 // query row against its own key range [ks, ke) of a packed, non-paged fp8 key array.  Item = 16

@@ -1,6 +1,7 @@
-// fmha_mla_index_select.h — the exact radix select under both selection kernels of the MLA indexer
-// (fmha_mla_index_topk_kernel.h, fmha_mla_index_topk_ragged_kernel.h), gfx950 (CDNA4); DESIGN.md
-// §3.13.1.  The kernels differ in how they split a row over waves and in their pass structure;
+// fmha_mla_index_select.h — the exact radix select under the selection kernels of the MLA indexer
+// (fmha_mla_index_topk_kernel.h, fmha_mla_index_topk_ragged_kernel.h and the two kernels of
+// fmha_mla_index_topk_split_kernel.h), gfx950 (CDNA4); DESIGN.md §3.13.1.  The kernels differ in
+// what they walk, how they split it over waves and workgroups, and in their pass structure;
 // what a row's result is, is stated here once, and every piece of it has one text:
 //
 //  * Key: the logit's bits made order-preserving (negative: all bits flipped, else the sign bit
@@ -22,8 +23,8 @@
 //  * Ties: keys > T are selected, and of the keys == T the first need_eq in position order.
 //  * Output: a selected key goes to (# greater before it) + min(# equal before it, need_eq), so the
 //    entries stand in ascending position; -1 from the count to topk.  Every output word has one
-//    writer, there are no atomics on global memory and no scratch: the result is a function of
-//    the inputs alone.
+//    writer (every scratch word of the split kernels too) and there are no atomics on global
+//    memory: the result is a function of the inputs alone.
 #pragma once
 
 #include "fmha_common.h"

@@ -1312,9 +1312,12 @@ at::Tensor mha_mla_index_logits(const at::Tensor& q8, const at::Tensor& weights,
 // its own row stride.  Returns indices int32 [batch, seqlen_q, topk]: the caller's `out` (a view
 // with a longer row is fine: unit column stride, rows row_stride apart) or a new one.  num_blocks
 // < 0: unknown, only the int32 range bounds a table entry.
-at::Tensor mha_mla_index_topk(const at::Tensor& logits, const at::Tensor& block_table, const at::Tensor& context_lens,
-                              const int64_t topk, const int64_t seqlen_q, const int64_t page_block_size,
-                              const int64_t max_seqlen_k, const int64_t num_blocks, const OptTensor& out_) {
+// splits > 0: fmha_mla_index_topk_split with that many chunks a row, its scratch the caller's
+// `workspace` (any dtype, contiguous) or the library's pool.
+static at::Tensor mla_index_topk_run(const at::Tensor& logits, const at::Tensor& block_table, const at::Tensor& context_lens,
+                                     const int64_t topk, const int64_t seqlen_q, const int64_t page_block_size,
+                                     const int64_t max_seqlen_k, const int64_t num_blocks, const OptTensor& out_,
+                                     const int64_t splits, const OptTensor& workspace) {
     CHECK_DEVICE(logits);
     TORCH_CHECK(logits.dtype() == torch::kFloat32, "logits must be fp32");
     TORCH_CHECK(logits.dim() == 2, "logits must be (batch_size * seqlen_q, keys)");
@@ -1351,13 +1354,44 @@ at::Tensor mha_mla_index_topk(const at::Tensor& logits, const at::Tensor& block_
     if (batch == 0) return out;
     const c10::DeviceGuard device_guard(logits.device());
     const int64_t orow = seqlen_q > 1 ? out.stride(1) : batch > 1 ? out.stride(0) : topk;
-    fmha_mla_index_topk(logits.data_ptr(), rows <= 1 ? logits.size(1) : logits.stride(0), block_table.data_ptr(),
-                        (int)block_table.stride(0), context_lens.data_ptr(), out.data_ptr(), orow, (int)topk,
-                        (int)seqlen_q, (int)max_seqlen_k, batch,
-                        num_blocks < 0 ? (int)(0x7fffffff / page_block_size) : (int)num_blocks, (int)page_block_size,
-                        cur_stream());
-    raise_if_failed("mla_index_topk");
+    const int64_t lrow = rows <= 1 ? logits.size(1) : logits.stride(0);
+    const int blocks = num_blocks < 0 ? (int)(0x7fffffff / page_block_size) : (int)num_blocks;
+    if (splits > 0) {
+        TORCH_CHECK(splits <= 0x7fffffff, "splits is out of range");
+        void* ws = nullptr;
+        size_t ws_bytes = 0;
+        if (workspace.has_value()) {
+            const at::Tensor& w = workspace.value();
+            TORCH_CHECK(w.is_cuda() && w.device() == logits.device() && w.is_contiguous(),
+                        "workspace must be a contiguous tensor on logits' device");
+            ws = w.data_ptr();
+            ws_bytes = (size_t)w.numel() * w.element_size();
+        }
+        fmha_mla_index_topk_split(logits.data_ptr(), lrow, block_table.data_ptr(), (int)block_table.stride(0),
+                                  context_lens.data_ptr(), out.data_ptr(), orow, (int)topk, (int)seqlen_q,
+                                  (int)max_seqlen_k, batch, blocks, (int)page_block_size, (int)splits, ws, ws_bytes,
+                                  cur_stream());
+    } else {
+        fmha_mla_index_topk(logits.data_ptr(), lrow, block_table.data_ptr(), (int)block_table.stride(0),
+                            context_lens.data_ptr(), out.data_ptr(), orow, (int)topk, (int)seqlen_q, (int)max_seqlen_k,
+                            batch, blocks, (int)page_block_size, cur_stream());
+    }
+    raise_if_failed(splits > 0 ? "mla_index_topk_split" : "mla_index_topk");
     return out;
+}
+at::Tensor mha_mla_index_topk(const at::Tensor& logits, const at::Tensor& block_table, const at::Tensor& context_lens,
+                              const int64_t topk, const int64_t seqlen_q, const int64_t page_block_size,
+                              const int64_t max_seqlen_k, const int64_t num_blocks, const OptTensor& out_) {
+    return mla_index_topk_run(logits, block_table, context_lens, topk, seqlen_q, page_block_size, max_seqlen_k, num_blocks,
+                              out_, 0, c10::nullopt);
+}
+at::Tensor mha_mla_index_topk_split(const at::Tensor& logits, const at::Tensor& block_table, const at::Tensor& context_lens,
+                                    const int64_t topk, const int64_t seqlen_q, const int64_t page_block_size,
+                                    const int64_t max_seqlen_k, const int64_t num_blocks, const OptTensor& out_,
+                                    const int64_t splits, const OptTensor& workspace) {
+    TORCH_CHECK(splits >= 1, "splits must lie in [2, 16]");
+    return mla_index_topk_run(logits, block_table, context_lens, topk, seqlen_q, page_block_size, max_seqlen_k, num_blocks,
+                              out_, splits, workspace);
 }
 
 // The prefill logits (fmha_mla_index_logits_ragged): q8 [M, heads, 128] bytes by its own strides,
@@ -1710,6 +1744,11 @@ PYBIND11_MODULE(paged_attn, m) {
           py::arg("logits"), py::arg("block_table"), py::arg("context_lens"), py::arg("topk"), py::arg("seqlen_q") = 1,
           py::arg("page_block_size") = 64, py::arg("max_seqlen_k") = 0, py::arg("num_blocks") = -1,
           py::arg("out") = py::none());
+    m.def("_mla_index_topk_split", &mha_mla_index_topk_split,
+          "Top-k selection over the MLA index logits with every row split over several workgroups",
+          py::arg("logits"), py::arg("block_table"), py::arg("context_lens"), py::arg("topk"), py::arg("seqlen_q") = 1,
+          py::arg("page_block_size") = 64, py::arg("max_seqlen_k") = 0, py::arg("num_blocks") = -1,
+          py::arg("out") = py::none(), py::arg("splits") = 2, py::arg("workspace") = py::none());
     m.def("_mla_index_logits_ragged", &mha_mla_index_logits_ragged,
           "Fused MLA index logits of prefill rows, each over its own key range of a packed fp8 key array",
           py::arg("q8"), py::arg("weights"), py::arg("k8"), py::arg("k_scale"), py::arg("ks"), py::arg("ke"),
@@ -1752,6 +1791,7 @@ PYBIND11_MODULE(paged_attn, m) {
         if (name == "mla_index_cache_append_fp8") return self.attr("_mla_index_cache_append_fp8");
         if (name == "mla_index_logits") return self.attr("_mla_index_logits");
         if (name == "mla_index_topk") return self.attr("_mla_index_topk");
+        if (name == "mla_index_topk_split") return self.attr("_mla_index_topk_split");
         if (name == "mla_index_logits_ragged") return self.attr("_mla_index_logits_ragged");
         if (name == "mla_index_topk_ragged") return self.attr("_mla_index_topk_ragged");
         if (name == "fwd_mla") return self.attr("_fwd_mla");

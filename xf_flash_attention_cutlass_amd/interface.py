@@ -428,11 +428,34 @@ def mla_index_topk_slots(logits, block_table, context_lens, topk, seqlen_q=1, pa
     return slots.view(b, int(seqlen_q), int(topk))
 
 
+MLA_INDEX_TOPK_SPLIT_CHUNK = 16384      # columns of one workgroup the automatic split aims at
+MLA_INDEX_TOPK_SPLIT_WORKGROUPS = 256   # ... as long as the launch stays within this many workgroups (the MI355X's CUs)
+
+
+def mla_index_topk_splits(max_seqlen_k, topk, rows=1):
+    """The workgroups a row `mla_index_topk(splits=None)` gives: 1, the one-workgroup kernel, for
+    every launch whose rows it keeps in LDS (max_seqlen_k <= 32768) and wherever the split kernels'
+    limits cannot be met (splits in [2, 16], splits * topk <= 32768, a chunk of at most 32768
+    columns); else one per MLA_INDEX_TOPK_SPLIT_CHUNK columns, fewer where `rows` of them would be
+    more than MLA_INDEX_TOPK_SPLIT_WORKGROUPS workgroups, never fewer than the chunk limit asks for."""
+    stage = paged_attn._mla_index_topk_stage
+    if max_seqlen_k <= stage:
+        return 1
+    least = -(-max_seqlen_k // stage)
+    splits = max(least, min(-(-max_seqlen_k // MLA_INDEX_TOPK_SPLIT_CHUNK), MLA_INDEX_TOPK_SPLIT_WORKGROUPS // max(rows, 1)))
+    return splits if splits <= min(16, stage // max(topk, 1)) else 1
+
+
 def mla_index_topk(logits, block_table, context_lens, topk, seqlen_q=1, page_block_size=64, max_seqlen_k=None,
-                   out=None, num_blocks=None):
-    """The indexer's choice as `flash_mla_with_kvcache(indices=...)` takes it, in one HIP launch
-    (`paged_attn.mla_index_topk`: an exact radix select, no scratch, no host sync, graph-capturable,
-    bitwise reproducible): int32 [b, seqlen_q, topk] of physical slots from `mla_index_logits`' result.
+                   out=None, num_blocks=None, splits=None):
+    """The indexer's choice as `flash_mla_with_kvcache(indices=...)` takes it, in HIP
+    (`paged_attn.mla_index_topk`: an exact radix select, no host sync, graph-capturable, bitwise
+    reproducible): int32 [b, seqlen_q, topk] of physical slots from `mla_index_logits`' result.
+    One launch and no scratch with one workgroup a row; `splits` >= 2 cuts every row over that many
+    workgroups (`paged_attn.mla_index_topk_split`: two launches and scratch from the library's
+    per-stream pool) - the result is the same, bit for bit.  splits=1 forces the one-workgroup
+    kernel; None chooses (`mla_index_topk_splits`): rows the kernel keeps in LDS, max_seqlen_k <=
+    32768, stay on it, longer ones are split.
 
     Row b * seqlen_q + i selects among the columns position i may see (bottom-right causal within
     min(context_lens[b], max_seqlen_k); nothing behind them is read, so they need not hold -inf).
@@ -448,11 +471,12 @@ def mla_index_topk(logits, block_table, context_lens, topk, seqlen_q=1, page_blo
     range of a slot bounds a table entry (INT32_MAX // page_block_size is passed down); out: int32
     [b, seqlen_q, topk], rows may lie further apart than topk (the rest of them is not touched).
     Returns the indices.  Not differentiable."""
+    max_k = int(logits.shape[1] if max_seqlen_k is None else max_seqlen_k)
+    splits = mla_index_topk_splits(max_k, int(topk), logits.shape[0]) if splits is None else int(splits)
+    args = (logits.detach(), block_table, context_lens, int(topk), int(seqlen_q), int(page_block_size), max_k,
+            -1 if num_blocks is None else int(num_blocks), out)
     with torch.no_grad():
-        return paged_attn.mla_index_topk(logits.detach(), block_table, context_lens, int(topk), int(seqlen_q),
-                                         int(page_block_size),
-                                         int(logits.shape[1] if max_seqlen_k is None else max_seqlen_k),
-                                         -1 if num_blocks is None else int(num_blocks), out)
+        return paged_attn.mla_index_topk(*args) if splits == 1 else paged_attn.mla_index_topk_split(*args, splits)
 
 
 def mla_index_topk_ragged(logits, ks, ke, topk, slots=None, out=None):
