@@ -127,7 +127,7 @@ void fmha_set_rng_state(uint64_t seed, uint64_t offset);
 void fmha_set_rng_state_device(const int64_t* seed_ptr, const int64_t* offset_ptr,
                                uint64_t offset_add, int64_t* rng_out);
 
-/* Library version / build identification, e.g. "xf-fmha-gfx950 2.18".  2.0 (round 3) changed
+/* Library version / build identification, e.g. "xf-fmha-gfx950 2.19".  2.0 (round 3) changed
  * argument lists of existing symbols; 2.1 exports those under _v2 names (see INTEGRATION.md
  * "ABI history"). */
 const char* fmha_version(void);
@@ -801,6 +801,44 @@ void fmha_mla_index_topk_ragged(const void* logits, int64_t logits_row_stride, c
                                 const void* slots /* may be NULL */, void* indices, int64_t indices_row_stride,
                                 int32_t topk, int32_t num_rows /* M */, int32_t num_keys /* N */,
                                 hipStream_t stream);
+
+/* --------------------------- Sparse MLA attention over new tokens: the V3.2 prefill (2.19) */
+
+/* fmha_mla_sparse_fwd: the attention step after fmha_mla_index_topk_ragged (FlashMLA's
+ * flash_mla_sparse_fwd): every one of s_q new tokens attends over exactly its selected rows of kv,
+ * gathered inside the kernel.  One launch of fmha_mla_sparse_fwd_kernel - a workgroup is one
+ * position and 64 heads, whose four waves share one gathered image of each 32-key tile; grid
+ * s_q * ceil(ceil(heads / 16) / 4) x 256 threads (fmha_last_kernel() names both) - no key split,
+ * no scratch, no combine, no atomics, no host sync (capturable in a graph).
+ *   q          [s_q, heads, 576], bf16 or fp16; strides[4] = {q row, q head, o row, o head} in
+ *              ELEMENTS, last dimension contiguous, 16-byte aligned rows
+ *   kv         [s_kv, 1, 576] of q's type by kv_row_stride (elements, >= 576, a multiple of 8).  A
+ *              paged 16-bit latent cache viewed flat is valid input (s_kv = num_blocks *
+ *              page_block_size, the entries physical slots: what fmha_mla_index_topk_ragged emits
+ *              with slots = the slot mapping).  kv may be larger than 4 GiB.
+ *   indices    int32 [s_q, topk] by indices_row_stride (elements, non-negative), last dimension
+ *              contiguous, 4-byte aligned; topk >= 1
+ *   o          [s_q, heads, 512] of q's type, by strides
+ *   lse        fp32 [s_q, heads] contiguous, NATURAL log, or NULL
+ *   max_logits fp32 [s_q, heads] contiguous, or NULL: the largest scaled score of the row
+ * An entry is valid iff 0 <= entry < s_kv; every other value (-1, the padding; INT32_MIN;
+ * INT32_MAX; s_kv) contributes nothing and is never turned into an address: no index value produces
+ * a load outside [kv, kv + s_kv * kv_row_stride).  For query (pos, head), K is the rows at the valid
+ * entries of indices[pos, :], in that order, duplicates as often as they occur, V = K[:, :512]:
+ * S = scale q K^T (all 576 features), O = softmax(S) V, LSE = logsumexp(S), max_logits = max(S).
+ * A row whose entries are all invalid gives O = 0, LSE = +inf and max_logits = -inf.  Per-row topk
+ * lengths are expressed by padding with -1.  O and LSE equal fmha_mla_decode_sparse's at batch 1,
+ * seqlen_q = s_q and num_splits = 1 bit for bit.
+ * s_q == 0 validates in full, launches nothing and succeeds.  Refused with an error, outputs
+ * untouched: a NULL q / kv / o / indices / strides, (d, dv) other than (576, 512), topk < 1,
+ * s_kv < 1, heads < 1, a negative s_q, q / o strides that are no multiples of 8 (the output's not
+ * positive), kv_row_stride below 576 or no multiple of 8, pointers that are not 16-byte aligned
+ * (indices, lse, max_logits: 4-byte), a negative indices stride, a launch larger than one grid. */
+void fmha_mla_sparse_fwd(void* q, void* kv, void* o, void* lse /* nullable */, void* max_logits /* nullable */,
+                         void* indices, int64_t indices_row_stride, int32_t topk, int32_t s_q, int64_t s_kv,
+                         int32_t heads, int32_t d /* 576 */, int32_t dv /* 512 */, int64_t kv_row_stride,
+                         const int64_t* strides /* q row, q head, o row, o head */, float scale,
+                         bool is_fp16, hipStream_t stream);
 
 /* ------------------------- MLA prefill: head size 192 for Q K^T, 128 for V (2.12) */
 

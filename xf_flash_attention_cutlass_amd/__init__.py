@@ -45,6 +45,7 @@ from .interface import (  # noqa: E402
     flash_attn_varlen_func,
     flash_attn_varlen_kvpacked_func,
     flash_attn_with_kvcache,
+    flash_mla_sparse_fwd,
     flash_mla_with_kvcache,
     merge_attn_states,
     mla_cache_append_fp8,
@@ -70,6 +71,7 @@ __all__ = [
     "flash_attn_varlen_kvpacked_func",
     "flash_attn_with_kvcache",
     "flash_mla_with_kvcache",
+    "flash_mla_sparse_fwd",
     "flash_attn_mla_func",
     "flash_attn_mla_varlen_func",
     "mla_cache_append_fp8",

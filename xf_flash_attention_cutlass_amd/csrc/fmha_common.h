@@ -262,6 +262,23 @@ struct MlaParams {
     int topk;
 };
 
+// fmha_mla_sparse_fwd (fmha_mla_sparse_fwd_kernel.h): sparse MLA attention over s_q new tokens.
+// A block of its own, so that the MLA decode kernels' arguments stay where they are.
+struct MlaSparseFwdParams {
+    const void* q;             // [s_q, h, 576] by q_row, q_head
+    const void* kv;            // [s_kv, 1, 576] by kv_row
+    void* o;                   // [s_q, h, 512] by o_row, o_head
+    float* lse;                // [s_q, h] or null, natural log
+    float* max_logits;         // [s_q, h] or null
+    const int* indices;        // int32 [s_q, topk] by ind_row: rows of kv, valid iff 0 <= entry < s_kv
+    int64_t q_row, q_head, o_row, o_head, kv_row, ind_row;    // in elements
+    int64_t s_kv;
+    int s_q, h, topk;
+    int groups;                // workgroups per position: ceil(ceil(h / 16) / 4)
+    float scale_log2;
+    int device;
+};
+
 struct BwdParams {
     const void* q; const void* k; const void* v; const void* o; const void* dout;
     const float* lse;

@@ -1189,6 +1189,57 @@ mha_mla_decode_sparse(const at::Tensor& q, const at::Tensor& kv_cache, const at:
     return {out, lse};
 }
 
+// Sparse MLA attention over new tokens (fmha_mla_sparse_fwd): q [s_q, heads, 576], kv [s_kv, 1, 576]
+// by its row stride, indices int32 [s_q, topk] (or [s_q, 1, topk]) of rows of kv.  Returns {out [s_q,
+// heads, 512], max_logits [s_q, heads], lse [s_q, heads]}.  Nothing is copied or synchronised.
+std::vector<at::Tensor>
+mha_mla_sparse_fwd(const at::Tensor& q, const at::Tensor& kv, const at::Tensor& indices, const float sm_scale,
+                   const int d_v, const OptTensor& out_) {
+    auto dt = q.dtype();
+    TORCH_CHECK(dt == torch::kFloat16 || dt == torch::kBFloat16, "mla_sparse_fwd takes fp16 or bf16 q");
+    CHECK_DEVICE(q); CHECK_DEVICE(kv); CHECK_DEVICE(indices);
+    TORCH_CHECK(q.dim() == 3 && q.size(2) == 576, "q must be (s_q, heads, 576)");
+    TORCH_CHECK(q.size(1) >= 1, "q must have at least one head");
+    TORCH_CHECK(q.stride(-1) == 1 && aligned16(q), "q must have contiguous last dimension and 16-byte aligned rows");
+    TORCH_CHECK(kv.dtype() == dt, "kv must have the dtype of q");
+    TORCH_CHECK(kv.device() == q.device() && indices.device() == q.device(), "kv and indices must be on q's device");
+    TORCH_CHECK(kv.dim() == 3 && kv.size(1) == 1 && kv.size(2) == 576, "kv must be (s_kv, 1, 576)");
+    TORCH_CHECK(kv.size(0) >= 1, "kv must hold at least one row");
+    TORCH_CHECK(kv.stride(-1) == 1 && aligned16(kv), "kv must have contiguous last dimension and 16-byte aligned rows");
+    TORCH_CHECK(d_v == 512, "mla_sparse_fwd takes d_v 512, got ", d_v);
+    TORCH_CHECK(indices.dtype() == torch::kInt32, "indices must have dtype int32");
+    const bool three = indices.dim() == 3;
+    TORCH_CHECK((indices.dim() == 2 || (three && indices.size(1) == 1)) && indices.size(0) == q.size(0),
+                "indices must be (s_q, topk) or (s_q, 1, topk) with q's s_q");
+    const int64_t topk = indices.size(-1);
+    TORCH_CHECK(topk >= 1 && topk <= 0x7fffffff, "indices must hold at least one entry per query position (topk >= 1)");
+    TORCH_CHECK(indices.stride(-1) == 1 || topk == 1, "indices must have contiguous last dimension");
+    TORCH_CHECK(indices.stride(0) >= 0, "indices must have non-negative strides");
+    const int s_q = q.size(0), heads = q.size(1);
+    const std::vector<int64_t> shape = {s_q, heads, d_v};
+    at::Tensor out;
+    if (out_.has_value()) {
+        out = out_.value();
+        TORCH_CHECK(out.dtype() == dt, "Output must have the same dtype as inputs");
+        TORCH_CHECK(out.is_cuda() && out.device() == q.device(), "out must be on q's device");
+        TORCH_CHECK(out.sizes() == at::IntArrayRef(shape), "out must have shape ", at::IntArrayRef(shape));
+        TORCH_CHECK(out.stride(-1) == 1, "Output tensor must have contiguous last dimension");
+        TORCH_CHECK(aligned16(out), "out must be 16-byte aligned with strides that are multiples of 16 bytes");
+    } else {
+        out = torch::empty(shape, q.options());
+    }
+    at::Tensor max_logits = torch::empty({s_q, heads}, q.options().dtype(torch::kFloat32));
+    at::Tensor lse = torch::empty({s_q, heads}, q.options().dtype(torch::kFloat32));
+    if (s_q == 0) return {out, max_logits, lse};
+    const c10::DeviceGuard device_guard(q.device());
+    const int64_t st[4] = {q.stride(0), q.stride(1), out.stride(0), out.stride(1)};
+    fmha_mla_sparse_fwd(q.data_ptr(), kv.data_ptr(), out.data_ptr(), lse.data_ptr(), max_logits.data_ptr(),
+                        indices.data_ptr(), indices.stride(0), (int)topk, s_q, kv.size(0), heads, 576, d_v,
+                        kv.stride(0), st, sm_scale, dt == torch::kFloat16, cur_stream());
+    raise_if_failed("mla_sparse_fwd");
+    return {out, max_logits, lse};
+}
+
 // Append tokens to the fp8 latent cache (fmha_mla_cache_append_fp8): latent [tokens, 512] and k_pe
 // [tokens, 64] by their own row strides (views of one 576-wide tensor are fine), slot_mapping int64.
 void mha_mla_cache_append_fp8(const at::Tensor& latent, const at::Tensor& k_pe, at::Tensor& kv_cache,
@@ -1733,6 +1784,10 @@ PYBIND11_MODULE(paged_attn, m) {
     m.def("_mla_decode_sparse_fp8", &mha_mla_decode_sparse<true>, "MLA decode over index-selected tokens of an fp8 paged latent KV cache",
           py::arg("q"), py::arg("kv_cache"), py::arg("indices"), py::arg("head_dim_v") = 512,
           py::arg("softmax_scale") = 0.041666666666666664f, py::arg("num_splits") = 0, py::arg("out") = py::none());
+    // ... and the sparse attention over new tokens
+    m.def("_mla_sparse_fwd", &mha_mla_sparse_fwd, "Sparse MLA attention over new tokens (index-selected rows of kv)",
+          py::arg("q"), py::arg("kv"), py::arg("indices"), py::arg("sm_scale") = 0.041666666666666664f,
+          py::arg("d_v") = 512, py::arg("out") = py::none());
     // ... and the MLA indexer: the index-key cache append and the fused index logits
     m.def("_mla_index_cache_append_fp8", &mha_mla_index_cache_append_fp8, "Append tokens to an fp8 paged index-key cache",
           py::arg("k"), py::arg("index_cache"), py::arg("slot_mapping"), py::arg("scale_fmt") = 0);
@@ -1788,6 +1843,7 @@ PYBIND11_MODULE(paged_attn, m) {
         if (name == "mla_cache_append_fp8") return self.attr("_mla_cache_append_fp8");
         if (name == "mla_decode_sparse") return self.attr("_mla_decode_sparse");
         if (name == "mla_decode_sparse_fp8") return self.attr("_mla_decode_sparse_fp8");
+        if (name == "mla_sparse_fwd") return self.attr("_mla_sparse_fwd");
         if (name == "mla_index_cache_append_fp8") return self.attr("_mla_index_cache_append_fp8");
         if (name == "mla_index_logits") return self.attr("_mla_index_logits");
         if (name == "mla_index_topk") return self.attr("_mla_index_topk");

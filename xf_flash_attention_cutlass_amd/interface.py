@@ -320,6 +320,41 @@ def flash_mla_with_kvcache(q, kv_cache, block_table, cache_seqlens, head_dim_v=5
     return o, lse
 
 
+def flash_mla_sparse_fwd(q, kv, indices, sm_scale=None, d_v=512, out=None):
+    """Sparse attention of multi-head latent attention over s_q new tokens (DeepSeek-V3.2's prefill;
+    FlashMLA's function of this name): one HIP launch (`paged_attn.mla_sparse_fwd`), no key split,
+    no scratch, no copies, no host sync.  A workgroup serves one token and 64 heads, so a selected
+    row is gathered once per 64 heads.
+
+    q: [s_q, heads, 576] bf16 or fp16 (a view is fine: last dimension contiguous, 16-byte aligned
+    rows); kv: [s_kv, 1, 576] of q's dtype, any row stride that is a multiple of 8 elements - a
+    paged 16-bit latent cache viewed flat, `kv_cache.view(-1, 1, 576)`, is valid input, its
+    indices physical slots (what `mla_index_topk_ragged(slots=slot_mapping)` emits); indices: int32
+    [s_q, 1, topk] (or [s_q, topk]), last dimension contiguous.  Token i attends over exactly the
+    rows of kv at the valid entries of indices[i], in that order; an entry is valid iff
+    0 <= entry < s_kv, every other value (-1 is the usual padding; pad rows of differing lengths with
+    it) contributes nothing, and the kernel checks every entry.  The value is the first d_v = 512
+    features of the row.  sm_scale defaults to 576 ** -0.5 (pass the model's own).
+
+    Returns (out [s_q, heads, 512], max_logits fp32 [s_q, heads], lse fp32 [s_q, heads]): lse is the
+    NATURAL-log sum of exponentials of the scaled scores, max_logits their maximum.  A token whose
+    entries are all invalid gives out = 0, lse = +inf and max_logits = -inf.  out and lse equal
+    `flash_mla_with_kvcache(q[None], cache, None, None, indices=indices[None], num_splits=1)` bit
+    for bit.  Not differentiable.
+
+    When to prefer the decode route (`flash_mla_with_kvcache(..., indices=...)`, which splits the
+    keys and combines): at up to 16 heads.  There only one of a workgroup's four waves
+    has products to do and this call took 2.5 to 3.3 times the decode route's time; at 64 and 128
+    heads it took 0.95 of it (MI355X, bf16, s_kv 32768, topk 2048, s_q 512 and 4096:
+    DESIGN.md §3.10.3, profiles/mla_sparse_fwd_ab.log)."""
+    if sm_scale is None:
+        sm_scale = q.shape[-1] ** (-0.5)
+    with torch.no_grad():
+        o, max_logits, lse = paged_attn.mla_sparse_fwd(q.detach(), kv.detach(), indices, float(sm_scale),
+                                                       int(d_v), out)
+    return o, max_logits, lse
+
+
 def mla_cache_append_fp8(latent, k_pe, kv_cache, slot_mapping):
     """Append tokens to an fp8 paged latent KV cache (the layout `flash_mla_with_kvcache` reads:
     rows of `mla_fp8_cache_row_bytes` = 656 bytes), one HIP launch, no host sync.
@@ -502,7 +537,7 @@ def mla_index_topk_ragged(logits, ks, ke, topk, slots=None, out=None):
 
         logits = mla_index_logits_ragged(q8, weights, k8, k_scale, ks, ke)
         idx = mla_index_topk_ragged(logits, ks, ke, topk, slots=slots)
-        out, lse = flash_mla_with_kvcache(q[None], kv_cache, None, None, indices=idx[None])
+        out, max_logits, lse = flash_mla_sparse_fwd(q, kv_cache.view(-1, 1, 576), idx, sm_scale)
 
     Returns the indices.  Not differentiable."""
     with torch.no_grad():
