@@ -127,7 +127,7 @@ void fmha_set_rng_state(uint64_t seed, uint64_t offset);
 void fmha_set_rng_state_device(const int64_t* seed_ptr, const int64_t* offset_ptr,
                                uint64_t offset_add, int64_t* rng_out);
 
-/* Library version / build identification, e.g. "xf-fmha-gfx950 2.19".  2.0 (round 3) changed
+/* Library version / build identification, e.g. "xf-fmha-gfx950 2.20". 2.0 (round 3) changed
  * argument lists of existing symbols; 2.1 exports those under _v2 names (see INTEGRATION.md
  * "ABI history"). */
 const char* fmha_version(void);
@@ -839,6 +839,33 @@ void fmha_mla_sparse_fwd(void* q, void* kv, void* o, void* lse /* nullable */, v
                          int32_t heads, int32_t d /* 576 */, int32_t dv /* 512 */, int64_t kv_row_stride,
                          const int64_t* strides /* q row, q head, o row, o head */, float scale,
                          bool is_fp16, hipStream_t stream);
+
+/* fmha_mla_sparse_fwd_fp8 (2.20): fmha_mla_sparse_fwd straight over the fp8 latent cache of 2.10 -
+ * no 16-bit copy of the selected rows.  One launch of fmha_mla_sparse_fwd_fp8_kernel, the same
+ * mapping and grid (fmha_last_kernel() names both): a selected row is gathered and dequantised
+ * once per 64 heads.  Everything is as fmha_mla_sparse_fwd but for kv:
+ *   kv         BYTES [s_kv, 1, 656] by kv_row_stride, which is in BYTES (>= 656, a multiple of 16):
+ *              the rows fmha_mla_cache_append_fp8 writes - 512 e4m3fn latent features, four fp32
+ *              descales (one per 128 features), the 64 rotary features in q's type.  A paged fp8
+ *              latent cache viewed flat is valid input (s_kv = num_blocks * page_block_size, the
+ *              entries physical slots).  K is the dequantised row: feature i < 512 is
+ *              T(float(e4m3[i]) * descale[i / 128]), one fp32 product rounded once to q's type T;
+ *              V = K[:, :512].  kv may be larger than 4 GiB.
+ * A row of an invalid entry never reaches the products, whatever slot 0 dequantises to (NaN
+ * included); no index value produces a load outside [kv, kv + s_kv * kv_row_stride).  O and LSE
+ * equal fmha_mla_decode_sparse_fp8's at batch 1, seqlen_q = s_q and num_splits = 1 bit for bit.
+ * s_q == 0 validates in full, launches nothing and succeeds.  Refused with an error, outputs
+ * untouched: a NULL q / kv / o / indices / strides, (d, dv) other than (576, 512), topk < 1,
+ * s_kv < 1, heads < 1, a negative s_q, q / o strides that are no multiples of 8 elements (the
+ * output's not positive), kv_row_stride below 656 bytes or no multiple of 16, pointers that are not
+ * 16-byte aligned (indices, lse, max_logits: 4-byte), a negative indices stride, a launch larger
+ * than one grid. */
+void fmha_mla_sparse_fwd_fp8(void* q, void* kv /* bytes */, void* o, void* lse /* nullable */,
+                             void* max_logits /* nullable */, void* indices, int64_t indices_row_stride,
+                             int32_t topk, int32_t s_q, int64_t s_kv, int32_t heads, int32_t d /* 576 */,
+                             int32_t dv /* 512 */, int64_t kv_row_stride /* bytes */,
+                             const int64_t* strides /* q row, q head, o row, o head */, float scale,
+                             bool is_fp16, hipStream_t stream);
 
 /* ------------------------- MLA prefill: head size 192 for Q K^T, 128 for V (2.12) */
 

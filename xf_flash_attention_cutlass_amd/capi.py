@@ -76,6 +76,8 @@ _SIGS = {
                                    i32, i32, C.POINTER(C.c_int64), f32, i32, b_, vp],
     "fmha_mla_sparse_fwd": [vp, vp, vp, vp, vp, vp, C.c_int64, i32, i32, C.c_int64, i32, i32, i32, C.c_int64,
                             C.POINTER(C.c_int64), f32, b_, vp],
+    "fmha_mla_sparse_fwd_fp8": [vp, vp, vp, vp, vp, vp, C.c_int64, i32, i32, C.c_int64, i32, i32, i32, C.c_int64,
+                                C.POINTER(C.c_int64), f32, b_, vp],
     "fmha_mla_index_cache_append_fp8": [vp, C.c_int64, vp, vp, i32, i32, i32, i32, b_, vp],
     "fmha_mla_index_logits": [vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32,
                               C.POINTER(C.c_int64), C.c_int64, vp],

@@ -525,7 +525,7 @@ const char* fmha_last_error(void) { return g_err.c_str(); }
 int fmha_last_status(void) { return g_status; }
 int fmha_last_num_splits(void) { return g_last_splits; }
 const char* fmha_last_kernel(void) { return g_last_kernel; }
-const char* fmha_version(void) { return XFA_VARIANTS ? "xf-fmha-gfx950 2.19 (variants)" : "xf-fmha-gfx950 2.19"; }
+const char* fmha_version(void) { return XFA_VARIANTS ? "xf-fmha-gfx950 2.20 (variants)" : "xf-fmha-gfx950 2.20"; }
 
 void fmha_set_rng_state(uint64_t seed, uint64_t offset) {
     g_seed = seed;
@@ -1655,6 +1655,61 @@ void mla_sparse_run(const char* entry, bool fp8, void* q, void* kv_cache, void* 
     }
 }
 
+// The one body of fmha_mla_sparse_fwd and fmha_mla_sparse_fwd_fp8 (sparse MLA attention over s_q new
+// tokens, fmha_mla_sparse_fwd_kernel.h and fmha_mla_sparse_fwd_fp8_kernel.h): every check and the one
+// launch.  kv_row_stride is in elements of q's type, or in bytes for the fp8 cache.  The indices are
+// not read here (no sync): the kernel validates every entry against s_kv.
+void mla_sparse_fwd_run(const char* entry, bool fp8, void* q, void* kv, void* o, void* lse, void* max_logits,
+                        void* indices, int64_t indices_row_stride, int32_t topk, int32_t s_q, int64_t s_kv,
+                        int32_t heads, int32_t d, int32_t dv, int64_t kv_row_stride, const int64_t* strides,
+                        float scale, bool is_fp16, hipStream_t stream) {
+    try {
+        begin_fwd();
+        REQUIRE(q && kv && o, "q, kv and o must be non-null device pointers");
+        REQUIRE(indices, "the sparse MLA forward reads its keys through indices: it must be non-null");
+        REQUIRE(strides, "strides must be a non-null pointer (q row, q head, o row, o head)");
+        REQUIRE(d == 576 && dv == 512, "the sparse MLA forward supports (d, dv) = (576, 512) only (got (%d, %d))", d, dv);
+        REQUIRE(topk >= 1, "topk must be at least 1 (got %d)", topk);
+        REQUIRE(s_kv >= 1, "s_kv must be at least 1 (got %lld)", (long long)s_kv);
+        REQUIRE(heads >= 1 && s_q >= 0, "heads must be at least 1 and s_q non-negative (got %d, %d)", heads, s_q);
+        const int ext[2] = {s_q, heads};
+        for (int i = 0; i < 4; ++i)
+            REQUIRE(strides[i] >= 0 && (ext[i % 2] <= 1 || strides[i] % 8 == 0) &&
+                        (i < 2 || ext[i % 2] <= 1 || strides[i] > 0),
+                    "strides must be non-negative multiples of 8 elements (16 bytes), the output's "
+                    "positive: stride %d is %lld", i, (long long)strides[i]);
+        if (fp8)
+            REQUIRE(kv_row_stride >= 656 && kv_row_stride % 16 == 0,
+                    "kv_row_stride must be at least 656 and a multiple of 16 bytes (got %lld)", (long long)kv_row_stride);
+        else
+            REQUIRE(kv_row_stride >= 576 && kv_row_stride % 8 == 0,
+                    "kv_row_stride must be at least 576 and a multiple of 8 elements (got %lld)", (long long)kv_row_stride);
+        REQUIRE(indices_row_stride >= 0, "the indices row stride must be non-negative (got %lld)",
+                (long long)indices_row_stride);
+        REQUIRE(!((((uintptr_t)q) | ((uintptr_t)kv) | ((uintptr_t)o)) & 15),
+                "q, kv and o must be 16-byte aligned device pointers");
+        REQUIRE(!((((uintptr_t)indices) | ((uintptr_t)lse) | ((uintptr_t)max_logits)) & 3),
+                "indices, lse and max_logits must be 4-byte aligned device pointers");
+        const int64_t groups = ((heads + 15) / 16 + 3) / 4;
+        REQUIRE((int64_t)s_q * groups <= 0x7fffffffLL && (int64_t)s_q * heads <= 0x7fffffffLL,
+                "s_q * heads = %lld is more than one launch covers", (long long)s_q * heads);
+        if (s_q == 0) return;
+        MlaSparseFwdParams p{};
+        p.q = q; p.kv = kv; p.o = o; p.lse = (float*)lse; p.max_logits = (float*)max_logits;
+        p.indices = (const int*)indices; p.ind_row = indices_row_stride;
+        p.q_row = strides[0]; p.q_head = strides[1]; p.o_row = strides[2]; p.o_head = strides[3];
+        p.kv_row = kv_row_stride; p.s_kv = s_kv;
+        p.s_q = s_q; p.h = heads; p.topk = topk; p.groups = (int)groups;
+        p.scale_log2 = scale * kLog2e;
+        p.device = current_device();
+        g_last_splits = 1;
+        hip_ok(fp8 ? launch_mla_sparse_fwd_fp8(p, is_fp16, stream) : launch_mla_sparse_fwd(p, is_fp16, stream),
+               "sparse MLA forward launch");
+    } catch (...) {
+        fail(9, "internal error in %s", entry);
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -1681,52 +1736,20 @@ void fmha_mla_decode_sparse_fp8(void* q, void* kv_cache8, void* o, void* softmax
                    head_size_v, num_blocks, page_block_size, strides, softmax_scale, num_splits, is_fp16, stream);
 }
 
-// Sparse MLA attention over s_q new tokens (fmha_mla_sparse_fwd_kernel.h): every check and the one
-// launch.  The indices are not read here (no sync): the kernel validates every entry against s_kv.
 void fmha_mla_sparse_fwd(void* q, void* kv, void* o, void* lse, void* max_logits, void* indices,
                          int64_t indices_row_stride, int32_t topk, int32_t s_q, int64_t s_kv, int32_t heads,
                          int32_t d, int32_t dv, int64_t kv_row_stride, const int64_t* strides, float scale,
                          bool is_fp16, hipStream_t stream) {
-    try {
-        begin_fwd();
-        REQUIRE(q && kv && o, "q, kv and o must be non-null device pointers");
-        REQUIRE(indices, "the sparse MLA forward reads its keys through indices: it must be non-null");
-        REQUIRE(strides, "strides must be a non-null pointer (q row, q head, o row, o head)");
-        REQUIRE(d == 576 && dv == 512, "the sparse MLA forward supports (d, dv) = (576, 512) only (got (%d, %d))", d, dv);
-        REQUIRE(topk >= 1, "topk must be at least 1 (got %d)", topk);
-        REQUIRE(s_kv >= 1, "s_kv must be at least 1 (got %lld)", (long long)s_kv);
-        REQUIRE(heads >= 1 && s_q >= 0, "heads must be at least 1 and s_q non-negative (got %d, %d)", heads, s_q);
-        const int ext[2] = {s_q, heads};
-        for (int i = 0; i < 4; ++i)
-            REQUIRE(strides[i] >= 0 && (ext[i % 2] <= 1 || strides[i] % 8 == 0) &&
-                        (i < 2 || ext[i % 2] <= 1 || strides[i] > 0),
-                    "strides must be non-negative multiples of 8 elements (16 bytes), the output's "
-                    "positive: stride %d is %lld", i, (long long)strides[i]);
-        REQUIRE(kv_row_stride >= 576 && kv_row_stride % 8 == 0,
-                "kv_row_stride must be at least 576 and a multiple of 8 elements (got %lld)", (long long)kv_row_stride);
-        REQUIRE(indices_row_stride >= 0, "the indices row stride must be non-negative (got %lld)",
-                (long long)indices_row_stride);
-        REQUIRE(!((((uintptr_t)q) | ((uintptr_t)kv) | ((uintptr_t)o)) & 15),
-                "q, kv and o must be 16-byte aligned device pointers");
-        REQUIRE(!((((uintptr_t)indices) | ((uintptr_t)lse) | ((uintptr_t)max_logits)) & 3),
-                "indices, lse and max_logits must be 4-byte aligned device pointers");
-        const int64_t groups = ((heads + 15) / 16 + 3) / 4;
-        REQUIRE((int64_t)s_q * groups <= 0x7fffffffLL && (int64_t)s_q * heads <= 0x7fffffffLL,
-                "s_q * heads = %lld is more than one launch covers", (long long)s_q * heads);
-        if (s_q == 0) return;
-        MlaSparseFwdParams p{};
-        p.q = q; p.kv = kv; p.o = o; p.lse = (float*)lse; p.max_logits = (float*)max_logits;
-        p.indices = (const int*)indices; p.ind_row = indices_row_stride;
-        p.q_row = strides[0]; p.q_head = strides[1]; p.o_row = strides[2]; p.o_head = strides[3];
-        p.kv_row = kv_row_stride; p.s_kv = s_kv;
-        p.s_q = s_q; p.h = heads; p.topk = topk; p.groups = (int)groups;
-        p.scale_log2 = scale * kLog2e;
-        p.device = current_device();
-        g_last_splits = 1;
-        hip_ok(launch_mla_sparse_fwd(p, is_fp16, stream), "sparse MLA forward launch");
-    } catch (...) {
-        fail(9, "internal error in fmha_mla_sparse_fwd");
-    }
+    mla_sparse_fwd_run("fmha_mla_sparse_fwd", false, q, kv, o, lse, max_logits, indices, indices_row_stride, topk,
+                       s_q, s_kv, heads, d, dv, kv_row_stride, strides, scale, is_fp16, stream);
+}
+
+void fmha_mla_sparse_fwd_fp8(void* q, void* kv, void* o, void* lse, void* max_logits, void* indices,
+                             int64_t indices_row_stride, int32_t topk, int32_t s_q, int64_t s_kv, int32_t heads,
+                             int32_t d, int32_t dv, int64_t kv_row_stride, const int64_t* strides, float scale,
+                             bool is_fp16, hipStream_t stream) {
+    mla_sparse_fwd_run("fmha_mla_sparse_fwd_fp8", true, q, kv, o, lse, max_logits, indices, indices_row_stride,
+                       topk, s_q, s_kv, heads, d, dv, kv_row_stride, strides, scale, is_fp16, stream);
 }
 
 // ---- MLA indexer: the append into the fp8 index-key cache and the fused index logits ---------

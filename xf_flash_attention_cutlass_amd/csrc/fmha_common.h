@@ -272,6 +272,7 @@ struct MlaSparseFwdParams {
     float* max_logits;         // [s_q, h] or null
     const int* indices;        // int32 [s_q, topk] by ind_row: rows of kv, valid iff 0 <= entry < s_kv
     int64_t q_row, q_head, o_row, o_head, kv_row, ind_row;    // in elements
+    // (fmha_mla_sparse_fwd_fp8: kv is [s_kv, 1, 656] bytes and kv_row is in BYTES)
     int64_t s_kv;
     int s_q, h, topk;
     int groups;                // workgroups per position: ceil(ceil(h / 16) / 4)

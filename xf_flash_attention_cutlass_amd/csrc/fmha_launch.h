@@ -282,6 +282,9 @@ hipError_t launch_mla_decode_sparse(const MlaParams& p, bool fp8, bool fp16, hip
 // Sparse MLA attention over new tokens (fmha_mla_sparse_fwd_kernel.h): one workgroup per position
 // and 64 heads, one launch
 hipError_t launch_mla_sparse_fwd(const MlaSparseFwdParams& p, bool fp16, hipStream_t st);
+// ... and over the fp8 latent cache (p.kv: rows of 656 bytes, p.kv_row in BYTES,
+// fmha_mla_sparse_fwd_fp8_kernel.h)
+hipError_t launch_mla_sparse_fwd_fp8(const MlaSparseFwdParams& p, bool fp16, hipStream_t st);
 
 // MLA prefill (fmha_fwd_mla.hip): the forward at head size 192 for Q K^T and 128 for V; one pass
 // (p.num_splits = 1), none of the score features, p.d unused

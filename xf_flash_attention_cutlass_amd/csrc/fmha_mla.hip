@@ -2,7 +2,8 @@
 // (fmha_mla_decode_kernel.h) for bf16 and fp16, its twin over an fp8 latent cache
 // (fmha_mla_decode_fp8, fmha_mla_decode_fp8_kernel.h), the two over index-selected tokens
 // (fmha_mla_decode_sparse[_fp8], fmha_mla_decode_sparse[_fp8]_kernel.h), the sparse attention over
-// new tokens (fmha_mla_sparse_fwd, fmha_mla_sparse_fwd_kernel.h), and the split combine at head size 512
+// new tokens (fmha_mla_sparse_fwd, fmha_mla_sparse_fwd_kernel.h) and its twin over the fp8 latent cache
+// (fmha_mla_sparse_fwd_fp8, fmha_mla_sparse_fwd_fp8_kernel.h), and the split combine at head size 512
 // (fmha_combine_kernel<512, T>, the forward's template, instantiated here).  A translation unit of
 // its own: the kernels run one wave per SIMD with 147,456 B of LDS, unlike anything in
 // fmha_fwd.hip.
@@ -12,6 +13,7 @@
 #include "fmha_mla_decode_sparse_kernel.h"
 #include "fmha_mla_decode_sparse_fp8_kernel.h"
 #include "fmha_mla_sparse_fwd_kernel.h"
+#include "fmha_mla_sparse_fwd_fp8_kernel.h"
 #include "fmha_launch.h"
 
 namespace xfa {
@@ -75,6 +77,19 @@ static hipError_t launch_mla_sparse_fwd_t(const MlaSparseFwdParams& p, hipStream
 
 hipError_t launch_mla_sparse_fwd(const MlaSparseFwdParams& p, bool fp16, hipStream_t st) {
     return fp16 ? launch_mla_sparse_fwd_t<_Float16>(p, st) : launch_mla_sparse_fwd_t<__bf16>(p, st);
+}
+
+template <typename T>
+static hipError_t launch_mla_sparse_fwd_fp8_t(const MlaSparseFwdParams& p, hipStream_t st) {
+    allow_lds<fmha_mla_sparse_fwd_fp8_kernel<T>>(p.device, kMlaFwdSmem);
+    const dim3 grid((unsigned)((int64_t)p.s_q * p.groups));
+    note_launch("fmha_mla_sparse_fwd_fp8_kernel", 0, 0, grid.x, grid.y, grid.z, kMlaWaves * 64);
+    hipLaunchKernelGGL(fmha_mla_sparse_fwd_fp8_kernel<T>, grid, dim3(kMlaWaves * 64), kMlaFwdSmem, st, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_mla_sparse_fwd_fp8(const MlaSparseFwdParams& p, bool fp16, hipStream_t st) {
+    return fp16 ? launch_mla_sparse_fwd_fp8_t<_Float16>(p, st) : launch_mla_sparse_fwd_fp8_t<__bf16>(p, st);
 }
 
 }  // namespace xfa

@@ -1192,6 +1192,9 @@ mha_mla_decode_sparse(const at::Tensor& q, const at::Tensor& kv_cache, const at:
 // Sparse MLA attention over new tokens (fmha_mla_sparse_fwd): q [s_q, heads, 576], kv [s_kv, 1, 576]
 // by its row stride, indices int32 [s_q, topk] (or [s_q, 1, topk]) of rows of kv.  Returns {out [s_q,
 // heads, 512], max_logits [s_q, heads], lse [s_q, heads]}.  Nothing is copied or synchronised.
+// kFp8 (fmha_mla_sparse_fwd_fp8): kv is the fp8 latent cache viewed flat, uint8 or float8_e4m3fn
+// [s_kv, 1, 656] by its row stride in bytes.
+template <bool kFp8>
 std::vector<at::Tensor>
 mha_mla_sparse_fwd(const at::Tensor& q, const at::Tensor& kv, const at::Tensor& indices, const float sm_scale,
                    const int d_v, const OptTensor& out_) {
@@ -1201,9 +1204,15 @@ mha_mla_sparse_fwd(const at::Tensor& q, const at::Tensor& kv, const at::Tensor& 
     TORCH_CHECK(q.dim() == 3 && q.size(2) == 576, "q must be (s_q, heads, 576)");
     TORCH_CHECK(q.size(1) >= 1, "q must have at least one head");
     TORCH_CHECK(q.stride(-1) == 1 && aligned16(q), "q must have contiguous last dimension and 16-byte aligned rows");
-    TORCH_CHECK(kv.dtype() == dt, "kv must have the dtype of q");
+    if (kFp8) {
+        TORCH_CHECK(kv.dtype() == torch::kUInt8 || kv.dtype() == at::kFloat8_e4m3fn,
+                    "an fp8 kv must have dtype uint8 or float8_e4m3fn");
+    } else {
+        TORCH_CHECK(kv.dtype() == dt, "kv must have the dtype of q");
+    }
     TORCH_CHECK(kv.device() == q.device() && indices.device() == q.device(), "kv and indices must be on q's device");
-    TORCH_CHECK(kv.dim() == 3 && kv.size(1) == 1 && kv.size(2) == 576, "kv must be (s_kv, 1, 576)");
+    TORCH_CHECK(kv.dim() == 3 && kv.size(1) == 1 && kv.size(2) == (kFp8 ? 656 : 576),
+                kFp8 ? "an fp8 kv must be (s_kv, 1, 656) bytes" : "kv must be (s_kv, 1, 576)");
     TORCH_CHECK(kv.size(0) >= 1, "kv must hold at least one row");
     TORCH_CHECK(kv.stride(-1) == 1 && aligned16(kv), "kv must have contiguous last dimension and 16-byte aligned rows");
     TORCH_CHECK(d_v == 512, "mla_sparse_fwd takes d_v 512, got ", d_v);
@@ -1233,10 +1242,11 @@ mha_mla_sparse_fwd(const at::Tensor& q, const at::Tensor& kv, const at::Tensor& 
     if (s_q == 0) return {out, max_logits, lse};
     const c10::DeviceGuard device_guard(q.device());
     const int64_t st[4] = {q.stride(0), q.stride(1), out.stride(0), out.stride(1)};
-    fmha_mla_sparse_fwd(q.data_ptr(), kv.data_ptr(), out.data_ptr(), lse.data_ptr(), max_logits.data_ptr(),
-                        indices.data_ptr(), indices.stride(0), (int)topk, s_q, kv.size(0), heads, 576, d_v,
-                        kv.stride(0), st, sm_scale, dt == torch::kFloat16, cur_stream());
-    raise_if_failed("mla_sparse_fwd");
+    (kFp8 ? fmha_mla_sparse_fwd_fp8 : fmha_mla_sparse_fwd)(
+        q.data_ptr(), kv.data_ptr(), out.data_ptr(), lse.data_ptr(), max_logits.data_ptr(),
+        indices.data_ptr(), indices.stride(0), (int)topk, s_q, kv.size(0), heads, 576, d_v,
+        kv.stride(0), st, sm_scale, dt == torch::kFloat16, cur_stream());
+    raise_if_failed(kFp8 ? "mla_sparse_fwd_fp8" : "mla_sparse_fwd");
     return {out, max_logits, lse};
 }
 
@@ -1785,7 +1795,11 @@ PYBIND11_MODULE(paged_attn, m) {
           py::arg("q"), py::arg("kv_cache"), py::arg("indices"), py::arg("head_dim_v") = 512,
           py::arg("softmax_scale") = 0.041666666666666664f, py::arg("num_splits") = 0, py::arg("out") = py::none());
     // ... and the sparse attention over new tokens
-    m.def("_mla_sparse_fwd", &mha_mla_sparse_fwd, "Sparse MLA attention over new tokens (index-selected rows of kv)",
+    m.def("_mla_sparse_fwd", &mha_mla_sparse_fwd<false>, "Sparse MLA attention over new tokens (index-selected rows of kv)",
+          py::arg("q"), py::arg("kv"), py::arg("indices"), py::arg("sm_scale") = 0.041666666666666664f,
+          py::arg("d_v") = 512, py::arg("out") = py::none());
+    m.def("_mla_sparse_fwd_fp8", &mha_mla_sparse_fwd<true>,
+          "Sparse MLA attention over new tokens (index-selected rows of an fp8 latent cache viewed flat)",
           py::arg("q"), py::arg("kv"), py::arg("indices"), py::arg("sm_scale") = 0.041666666666666664f,
           py::arg("d_v") = 512, py::arg("out") = py::none());
     // ... and the MLA indexer: the index-key cache append and the fused index logits
@@ -1844,6 +1858,7 @@ PYBIND11_MODULE(paged_attn, m) {
         if (name == "mla_decode_sparse") return self.attr("_mla_decode_sparse");
         if (name == "mla_decode_sparse_fp8") return self.attr("_mla_decode_sparse_fp8");
         if (name == "mla_sparse_fwd") return self.attr("_mla_sparse_fwd");
+        if (name == "mla_sparse_fwd_fp8") return self.attr("_mla_sparse_fwd_fp8");
         if (name == "mla_index_cache_append_fp8") return self.attr("_mla_index_cache_append_fp8");
         if (name == "mla_index_logits") return self.attr("_mla_index_logits");
         if (name == "mla_index_topk") return self.attr("_mla_index_topk");

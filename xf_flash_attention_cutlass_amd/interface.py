@@ -336,6 +336,14 @@ def flash_mla_sparse_fwd(q, kv, indices, sm_scale=None, d_v=512, out=None):
     it) contributes nothing, and the kernel checks every entry.  The value is the first d_v = 512
     features of the row.  sm_scale defaults to 576 ** -0.5 (pass the model's own).
 
+    An fp8 latent cache - kv of dtype uint8 or float8_e4m3fn, [s_kv, 1, 656] bytes
+    (`mla_fp8_cache_row_bytes`; rows any multiple of 16 bytes apart), as `mla_cache_append_fp8`
+    writes it: `kv_cache8.view(-1, 1, 656)` is valid input - takes `paged_attn.mla_sparse_fwd_fp8`:
+    the call dispatches on kv.dtype, as `flash_mla_with_kvcache` does.  A selected row is gathered
+    and dequantised to q's dtype (one fp32 product, rounded once) once per 64 heads, inside the
+    kernel: no 16-bit copy of the cache or of the selected rows.  Everything else is as above; out
+    and lse equal the fp8 cache's decode route at num_splits=1 bit for bit.
+
     Returns (out [s_q, heads, 512], max_logits fp32 [s_q, heads], lse fp32 [s_q, heads]): lse is the
     NATURAL-log sum of exponentials of the scaled scores, max_logits their maximum.  A token whose
     entries are all invalid gives out = 0, lse = +inf and max_logits = -inf.  out and lse equal
@@ -346,12 +354,17 @@ def flash_mla_sparse_fwd(q, kv, indices, sm_scale=None, d_v=512, out=None):
     keys and combines): at up to 16 heads.  There only one of a workgroup's four waves
     has products to do and this call took 2.5 to 3.3 times the decode route's time; at 64 and 128
     heads it took 0.95 of it (MI355X, bf16, s_kv 32768, topk 2048, s_q 512 and 4096:
-    DESIGN.md §3.10.3, profiles/mla_sparse_fwd_ab.log)."""
+    DESIGN.md §3.10.3, profiles/mla_sparse_fwd_ab.log).  Over the fp8 cache the same holds, more
+    sharply: at 16 heads this call took 2.3 to 2.7 times the fp8 decode route's time, at 64 and 128
+    heads 0.73 of it (the decode route converts every selected row once per 16 heads), and 1.12 to 1.15
+    times the 16-bit call's over a bf16 copy of the cache (same shapes: DESIGN.md §3.10.4,
+    profiles/mla_sparse_fwd_fp8_ab.log)."""
     if sm_scale is None:
         sm_scale = q.shape[-1] ** (-0.5)
+    fp8 = kv.dtype in (torch.uint8, torch.float8_e4m3fn)
+    op = paged_attn.mla_sparse_fwd_fp8 if fp8 else paged_attn.mla_sparse_fwd
     with torch.no_grad():
-        o, max_logits, lse = paged_attn.mla_sparse_fwd(q.detach(), kv.detach(), indices, float(sm_scale),
-                                                       int(d_v), out)
+        o, max_logits, lse = op(q.detach(), kv.detach(), indices, float(sm_scale), int(d_v), out)
     return o, max_logits, lse
 
 
